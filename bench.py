@@ -12,10 +12,16 @@ gradients are all-reduced per backward pass on a side stream, underneath the res
   child, rank 0 of which prints the JSON line, and exits with the child's code.
 * started BY torchrun (RANK / LOCAL_RANK / WORLD_SIZE set): one rank of the job.
 
-Prints ONE JSON line on rank 0.  Extra objects: "roofline" for the dominant kernel of the step (tools/roofline.py),
-"families" (ms/step per kernel family), "encoder_fwd*" (ViT encoder forward alone vs the bf16 MFMA peak) and
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times EXACTLY --steps steps (one window) and prints the
+headline.  --full adds the legs that need runs or timings of their own: the median of --windows windows (default 5) instead
+of one, and the extra objects "roofline" for the dominant kernel of the step (tools/roofline.py), "families" (ms/step per
+kernel family), "encoder_fwd*" (ViT encoder forward alone vs the bf16 MFMA peak), "parity_mode" (the bf16x3 step) and
 "cpu_baseline" (the CPU oracle = the reference's operator graph in plain PyTorch, timed on the host cores on a bounded
 sample; rank 0, N=1 only -- the only place bench.py touches oracle/).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last step handed its caller as float32 .npy files: the loss
+(loss.npy) and a fixed, seeded sample of the updated weights (params_sample.npy; --stub: param.npy).  Inputs and initial
+weights are seeded, so two builds run with the same arguments can be compared output for output.
 
 --config c2 (default) | c4 (160^3, encoder activation checkpointing, batch 1) | c5 (ranking pre-training step at 96^3:
 [4,1,96^3] batch, 'feat' then 'recon' stage of unetr_ranking_pretraining_3d.py:238-296, all three slice axes).
@@ -66,10 +72,17 @@ def parse(argv=None):
     ap.add_argument("--no-parity-mode", action="store_true", help="skip the bf16x3 (tolerance-grade) leg reported as parity_mode")
     ap.add_argument("--cpu-steps", type=int, default=10, help="timed CPU-oracle steps (after 3 warm-up steps; SURVEY 8d)")
     ap.add_argument("--cpu-warmup", type=int, default=3)
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of exactly --steps steps each; the reported ms_per_step / value are "
-                    "the MEDIAN window's (min / max beside it): one 0.1 s window moves by more than most single optimisations")
+    ap.add_argument("--windows", type=int, default=None, help="timed windows of exactly --steps steps each (default 1; 5 with --full); the reported "
+                    "ms_per_step / value are the MEDIAN window's (min / max beside it): one 0.1 s window moves by more than most single optimisations")
+    ap.add_argument("--full", action="store_true", help="also run the legs beyond the headline: 5 windows, roofline / families / encoder_fwd, "
+                    "cpu_baseline, parity_mode (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's loss and a seeded sample of the updated "
+                    "weights to DIR/<name>.npy (float32)")
     ap.add_argument("--stub", action="store_true", help="CPU/gloo stub step (launcher + schedule test, no GPU)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
+    return args
 
 
 def log(msg):
@@ -129,6 +142,10 @@ def stub_rank(args, rank, world, real_stdout):
                 param[lo:hi] -= 1e-2 * grad[lo:hi] / world
     dist.barrier()
     dt = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "param.npy"), param.numpy())
     t = torch.tensor([dt], dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     cs = torch.tensor([param.double().sum().item()], dtype=torch.float64)
@@ -287,7 +304,9 @@ def run_supervised(args, pkg, dev, rank, world, dist, ddp_on, synthetic_volume):
                    "grad_comm_dtype": (str(comm_dtype).replace("torch.", "") if ddp_on else None),
                    "first_step_loss": first_loss, "final_loss": float(step.loss.item()), "graph_capture_error": graph_err},
     }
-    if rank == 0 and not args.no_roofline and args.config == "c2" and not ddp_on:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step.loss, model)
+    if rank == 0 and args.full and not args.no_roofline and args.config == "c2" and not ddp_on:
         try:
             from tools import roofline as rl
             out.update(rl.step_report(pkg, step, batch, args.precision, ms_per_step))
@@ -299,10 +318,11 @@ def run_supervised(args, pkg, dev, rank, world, dist, ddp_on, synthetic_volume):
         except Exception as e:  # noqa: BLE001
             out["encoder_fwd"] = {"error": f"{type(e).__name__}: {e}"}
         log("roofline done")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, cfg, batch, first_loss)
         log("cpu baseline done")
-    if rank == 0 and world == 1 and args.config == "c2" and args.precision == "bf16" and not args.no_parity_mode and not args.no_roofline:
+    if rank == 0 and world == 1 and args.full and args.config == "c2" and args.precision == "bf16" and not args.no_parity_mode \
+            and not args.no_roofline:
         try:
             out["parity_mode"] = parity_mode(args, pkg, dev, cfg, batch, synthetic_volume)
         except Exception as e:  # noqa: BLE001
@@ -434,6 +454,8 @@ def run_c5(args, pkg, dev, rank, world, dist=None):
             dt = t.item()
         wins.append(dt)
     dt = sorted(wins)[len(wins) // 2]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, model)
     return {"metric": "ranking pre-training volumes/sec (96^3)", "value": round(world * 4 * 6 * args.steps / dt, 3), "unit": "volumes/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
@@ -442,6 +464,24 @@ def run_c5(args, pkg, dev, rank, world, dist=None):
                                    f"fwd/BT-loss/bwd/AdamW passes per step, {launch}",
                        "final_loss": float(loss.item()),
                        "graph_capture_error": graph_err}}
+
+
+DUMP_SAMPLE = 1 << 22         # weights written by --dump-outputs: 16 MB of float32
+
+
+def dump_outputs(path, loss, model):
+    """--dump-outputs: what the caller of the timed step holds after its last step -- the loss, and the updated weights as a
+    fixed sample (seed 0, DUMP_SAMPLE indices drawn over model.named_parameters() concatenated in order; the whole set is
+    ~370 MB) -- as float32 .npy files under ``path``."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    w = torch.cat([p.detach().reshape(-1).float() for _, p in model.named_parameters()])
+    idx = torch.randint(0, w.numel(), (min(DUMP_SAMPLE, w.numel()),), generator=torch.Generator().manual_seed(0))
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().cpu().numpy())
+    np.save(os.path.join(path, "params_sample.npy"), w[idx.to(w.device)].cpu().numpy())
+    log(f"outputs written to {path}")
 
 
 _CPU_REF = {}

@@ -222,6 +222,29 @@ def test_bench_launcher_starts_n_ranks_gloo_stub(config):
     assert ("c5" in out["config"]["workload"]) == (config == "c5")      # config 5: six passes per step, the frozen ones on one piece
 
 
+def test_bench_dump_outputs_gloo_stub(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed step computed as float32 .npy files, and two runs with the
+    same arguments write the same arrays (seeded inputs) -- exercised on the CPU stub step."""
+    import subprocess
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    got = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--stub", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        files = sorted(os.listdir(d))
+        assert files and all(f.endswith(".npy") for f in files), files
+        arrs = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        got.append(arrs)
+    assert got[0].keys() == got[1].keys()
+    for f in got[0]:
+        np.testing.assert_array_equal(got[0][f], got[1][f])
+
+
 def test_stage_ranges_and_piece_plan():
     """UNETR.stage_ranges tile the arena in backward-completion order and TrainStep's piece plan cuts AdamW runs at piece
     boundaries (host logic only: arenas are faked on CPU tensors)."""

@@ -3,7 +3,7 @@
 V=$1; shift
 for r in 1 2 3; do
   for x in "$@"; do
-    env $V=$x python bench.py --no-cpu-baseline --windows 3 2>/dev/null | python -c "
+    env $V=$x python bench.py --full --no-cpu-baseline --windows 3 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 fam='${FAM:-}'

@@ -2,7 +2,7 @@
 V=$1; A=$2; B=$3; F=$4
 for r in 1 2; do
   for x in $A $B; do
-    env $V=$x python bench.py --no-cpu-baseline --windows 3 2>/dev/null | python -c "
+    env $V=$x python bench.py --full --no-cpu-baseline --windows 3 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$V=$x', d['ms_per_step'], [(f['family'][:28], round(f['ms_per_step'],4)) for f in d['families'] if '$F' in f['family']])"
