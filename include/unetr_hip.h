@@ -35,7 +35,7 @@ extern "C" {
 /* Bumped whenever an exported signature or a descriptor struct changes.  A binding (3dmedicalimagesegmentation_amd/_capi.py, or a
  * C caller) must compare unetr_abi_version() with the UNETR_ABI_VERSION it was written against before its first call: a stale
  * .so would otherwise shift arguments silently (a stream pointer in an int slot). */
-#define UNETR_ABI_VERSION 17
+#define UNETR_ABI_VERSION 18
 int unetr_abi_version(void);
 
 /* ---- generic MFMA GEMM: C[M,N] = epilogue(A[M,K] * B[K,N]) ------------------------------------------
@@ -407,6 +407,16 @@ int unetr_sw_accumulate(const float* seg, const float* importance, float* out, f
 int unetr_sw_finalize(float* out, const float* count, int B, int C, long V, void* stream);
 int unetr_dice_counts(const float* pred, const float* y, int B, int C, long V, int from_logits, double* counts,
                       float* ws, size_t ws_bytes, void* stream);
+/* unetr_hausdorff: monai.metrics.HausdorffDistanceMetric (MONAI 0.6.0, distance_metric="euclidean", :495-496) per item and
+ * class: out[b][c - c0] (float64, [B][C-c0]) for the classes c0 <= c < C (c0 = 1: include_background=False).  pred / y as in
+ * unetr_dice_counts (from_logits fuses argmax + one-hot; otherwise a voxel is in a mask where its value == 1).  use_percentile = 0
+ * takes the max, 1 takes np.percentile(q * 100) (linear); directed = 1 returns d(pred -> gt) only.  Volumes [B,C,D,H,W] with
+ * C <= 32, D, H, W <= 512.  ws holds unetr_hausdorff_workspace_bytes(B, C, D, H, W, group, use_percentile) bytes: 8 B per voxel
+ * of the batch plus, per slot of the (b, c) group processed together, 9 B per voxel of one volume (8 B more per histogram bin
+ * with percentiles, (D-1)^2+(H-1)^2+(W-1)^2+1 bins).  No host synchronisation. */
+size_t unetr_hausdorff_workspace_bytes(int B, int C, int D, int H, int W, int group, int use_percentile);
+int unetr_hausdorff(const float* pred, const float* y, int B, int C, int D, int H, int W, int c0, int from_logits,
+                    int use_percentile, double q, int directed, double* out, void* ws, size_t ws_bytes, int group, void* stream);
 
 /* ---- ranking pre-training losses (unetr_ranking_pretraining_3d.py:59-133 triplet construction, :202-217 BTLoss,
  * :219-236 ContrastiveLoss), fused: feat is the NCDHW feature map [4, C, S1, S2, S3] (2 volumes x 2 transforms: enc4 in
