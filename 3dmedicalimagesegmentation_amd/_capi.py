@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("UNETR_AMD_LIB") or os.path.join(_HERE, "libunetr_hip.
 PREC_F32 = 0
 PREC_BF16 = 1
 PREC_BF16X3 = 2      # fp32 storage, operands split into bf16 (hi, lo) pairs inside the kernels (csrc/common.hpp: PrecBF16x3)
-ABI_VERSION = 18       # = UNETR_ABI_VERSION of include/unetr_hip.h this table of signatures was written against
+ABI_VERSION = 19       # = UNETR_ABI_VERSION of include/unetr_hip.h this table of signatures was written against
 
 _ERR = {1: "invalid argument", 2: "kernel launch failed", 3: "unsupported shape/configuration",
         4: "workspace too small"}
@@ -77,6 +77,13 @@ class SplitProblem(ctypes.Structure):
 
 class ColsumProblem(ctypes.Structure):
     _fields_ = [("x", c_void_p), ("out", c_void_p), ("ld", c_long), ("M", c_int), ("N", c_int), ("x_bf16", c_int)]
+
+
+class AugDesc(ctypes.Structure):
+    _fields_ = [("B", c_int), ("num_samples", c_int), ("C", c_int), ("L", c_int), ("S0", c_int), ("S1", c_int), ("S2", c_int),
+                ("sampling", c_int), ("ax0", c_int), ("ax1", c_int), ("max_k", c_int), ("normalize", c_int),
+                ("pos_ratio", c_double), ("flip_prob", c_double * 3), ("rot90_prob", c_double), ("shift_prob", c_double),
+                ("shift_lo", c_double), ("shift_hi", c_double), ("seed", ctypes.c_uint64)]
 
 
 P = c_void_p
@@ -155,6 +162,12 @@ _SIGNATURES = {
     "unetr_sw_finalize": [P, P, c_int, c_int, c_long, P],
     "unetr_dice_counts": [P, P, c_int, c_int, c_long, c_int, P, P, c_size_t, P],
     "unetr_hausdorff": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, P, P, c_size_t, c_int, P],
+    "unetr_aug_prep": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, P, P, P],
+    "unetr_aug_crop": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P],
+    "unetr_aug_index_count": [P, P, c_int, c_int, c_long, c_float, P, c_size_t, P],
+    "unetr_aug_index_scatter": [P, P, c_int, c_int, c_long, c_float, P, c_size_t, P, P, P],
+    "unetr_aug_sample": [ctypes.POINTER(AugDesc), P, c_int, P, P, P, P],
+    "unetr_aug_gather": [ctypes.POINTER(AugDesc), P, c_int, P, P, P, P, c_size_t, P],
     "unetr_ranking_loss_fwd": [P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P, P, P, c_size_t, P],
     "unetr_ranking_loss_bwd": [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P],
     "unetr_adamw": [P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_float, P, P, P],
@@ -162,7 +175,8 @@ _SIGNATURES = {
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + ("unetr_conv3_packed_bytes", "unetr_conv3_packed_1x1_bytes", "unetr_ranking_workspace_floats",
-                                            "unetr_conv3_wgrad_rows", "unetr_tconv2_wgrad_rows", "unetr_outconv_in_bwd_rows", "unetr_hausdorff_workspace_bytes")
+                                            "unetr_conv3_wgrad_rows", "unetr_tconv2_wgrad_rows", "unetr_outconv_in_bwd_rows", "unetr_hausdorff_workspace_bytes",
+                                            "unetr_aug_index_ws_ints", "unetr_aug_gather_ws_bytes")
 
 _lib = None
 
@@ -200,6 +214,10 @@ def load():
     lib.unetr_ranking_workspace_floats.restype = c_size_t
     lib.unetr_hausdorff_workspace_bytes.argtypes = [c_int] * 7
     lib.unetr_hausdorff_workspace_bytes.restype = c_size_t
+    lib.unetr_aug_index_ws_ints.argtypes = [c_long]
+    lib.unetr_aug_index_ws_ints.restype = c_long
+    lib.unetr_aug_gather_ws_bytes.argtypes = [ctypes.POINTER(AugDesc)]
+    lib.unetr_aug_gather_ws_bytes.restype = c_size_t
     _lib = lib
     return lib
 

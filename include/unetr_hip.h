@@ -35,7 +35,7 @@ extern "C" {
 /* Bumped whenever an exported signature or a descriptor struct changes.  A binding (3dmedicalimagesegmentation_amd/_capi.py, or a
  * C caller) must compare unetr_abi_version() with the UNETR_ABI_VERSION it was written against before its first call: a stale
  * .so would otherwise shift arguments silently (a stream pointer in an int slot). */
-#define UNETR_ABI_VERSION 18
+#define UNETR_ABI_VERSION 19
 int unetr_abi_version(void);
 
 /* ---- generic MFMA GEMM: C[M,N] = epilogue(A[M,K] * B[K,N]) ------------------------------------------
@@ -428,6 +428,43 @@ int unetr_ranking_loss_fwd(const float* feat, int C, int S1, int S2, int S3, int
                            float temperature, int kind, float* loss, float* W, float* ws, size_t ws_floats, void* stream);
 int unetr_ranking_loss_bwd(const float* feat, int C, int S1, int S2, int S3, int slice_dim, int init_idx,
                            const float* W, const float* dloss, float* dfeat, void* stream);
+
+/* ---- GPU-resident training augmentation (csrc/augment.hip; unetr_segmentation_3d.py:322-476) ----
+ * VolumeCache.add: unetr_aug_prep scales img [C,D,H,W] in place (scale_mode 1: ScaleIntensityRanged(clip=True) with the float32
+ * constants a_min, a_range = a_max - a_min, b_range = b_max - b_min, b_min, b_max; 2: img - a_min; 0: none), folds the bounding
+ * box of any_c(img > 0) into box[6] (z0, y0, x0, z1, y1, x1 inclusive; caller fills 0x7fffffff x3, -1 x3) when do_box, and sets
+ * *flag where a value of lbl [L,D,H,W] is not an integer in 0..255.  unetr_aug_crop copies a box: image float32, label uint8.
+ * unetr_aug_index_count / _scatter: the foreground (any_l(lbl != 0)) and background (!fg && any_c(img > thr)) voxel lists of
+ * monai map_binary_to_indices, int32 in ascending ravel order; count writes the totals to ws[ws_ints - 2 .. ws_ints - 1].
+ * RandCropAugment: vols is a DEVICE table of int64 rows (img ptr, lbl ptr, fg ptr, nfg, bg ptr, nbg, C, L, D, H, W, 0);
+ * state (DEVICE int64: call counter, cursor, len(order), 0) is advanced by unetr_aug_sample, which writes params [B][8] (int32:
+ * volume, corner z, y, x, flip mask, k, shift flag, offset as float bits) from Philox4x64-10 draws.  unetr_aug_gather maps every
+ * voxel of x [B,C,S0,S1,S2] and y [B,L,S0,S1,S2] (float32) back to the volume; normalize adds NormalizeIntensity(nonzero=True,
+ * channel_wise=True) per sample with ws of unetr_aug_gather_ws_bytes.  No host synchronisation. */
+typedef struct {
+    int B, num_samples, C, L, S0, S1, S2;
+    int sampling;                     /* 0 RandCropByPosNegLabeld, 1 RandSpatialCropSamplesd */
+    int ax0, ax1;                     /* rot90 spatial axes (S[ax0] == S[ax1]) */
+    int max_k, normalize;
+    double pos_ratio;                 /* pos / (pos + neg) */
+    double flip_prob[3];
+    double rot90_prob, shift_prob, shift_lo, shift_hi;
+    unsigned long long seed;
+} UnetrAugDesc;
+long unetr_aug_index_ws_ints(long V);
+int unetr_aug_prep(float* img, const float* lbl, int C, int L, int D, int H, int W, int scale_mode, float a_min, float a_range,
+                   float b_range, float b_min, float b_max, int do_box, int* box, int* flag, void* stream);
+int unetr_aug_crop(const float* img, const float* lbl, int C, int L, int D, int H, int W, int z0, int y0, int x0, int d, int h,
+                   int w, float* oimg, unsigned char* olbl, void* stream);
+int unetr_aug_index_count(const float* img, const unsigned char* lbl, int C, int L, long V, float thr, int* ws, size_t ws_ints,
+                          void* stream);
+int unetr_aug_index_scatter(const float* img, const unsigned char* lbl, int C, int L, long V, float thr, const int* ws,
+                            size_t ws_ints, int* fg, int* bg, void* stream);
+int unetr_aug_sample(const UnetrAugDesc* d, const long long* vols, int nvol, const int* order, long long* state, int* params,
+                     void* stream);
+size_t unetr_aug_gather_ws_bytes(const UnetrAugDesc* d);
+int unetr_aug_gather(const UnetrAugDesc* d, const long long* vols, int nvol, const int* params, float* x, float* y, void* ws,
+                     size_t ws_bytes, void* stream);
 
 /* ---- fused AdamW over one flat fp32 buffer (torch.optim.AdamW semantics; unetr_segmentation_3d.py:522) */
 int unetr_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
