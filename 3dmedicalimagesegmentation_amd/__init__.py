@@ -11,9 +11,10 @@ from .inference import DiceMetric, sliding_window_inference  # noqa: F401
 from .metrics import ConfusionMatrixMetric, HausdorffDistanceMetric  # noqa: F401
 from .train_step import TrainStep  # noqa: F401
 from .augment import RandCropAugment, VolumeCache  # noqa: F401
+from .preprocess import resample_orient  # noqa: F401
 from .functional import invalidate_weight_shadows  # noqa: F401
-from . import _capi, augment, ddp, functional, inference, metrics, train_step  # noqa: F401
+from . import _capi, augment, ddp, functional, inference, metrics, preprocess, train_step  # noqa: F401
 
 __all__ = ["UNETR", "UNETRLogits", "DiceCELoss", "ranking_loss", "AdamW", "default_precision", "sliding_window_inference",
            "DiceMetric", "ConfusionMatrixMetric", "HausdorffDistanceMetric", "TrainStep", "invalidate_weight_shadows",
-           "VolumeCache", "RandCropAugment"]
+           "VolumeCache", "RandCropAugment", "resample_orient"]

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("UNETR_AMD_LIB") or os.path.join(_HERE, "libunetr_hip.
 PREC_F32 = 0
 PREC_BF16 = 1
 PREC_BF16X3 = 2      # fp32 storage, operands split into bf16 (hi, lo) pairs inside the kernels (csrc/common.hpp: PrecBF16x3)
-ABI_VERSION = 19       # = UNETR_ABI_VERSION of include/unetr_hip.h this table of signatures was written against
+ABI_VERSION = 20       # = UNETR_ABI_VERSION of include/unetr_hip.h this table of signatures was written against
 
 _ERR = {1: "invalid argument", 2: "kernel launch failed", 3: "unsupported shape/configuration",
         4: "workspace too small"}
@@ -168,6 +168,7 @@ _SIGNATURES = {
     "unetr_aug_index_scatter": [P, P, c_int, c_int, c_long, c_float, P, c_size_t, P, P, P],
     "unetr_aug_sample": [ctypes.POINTER(AugDesc), P, c_int, P, P, P, P],
     "unetr_aug_gather": [ctypes.POINTER(AugDesc), P, c_int, P, P, P, P, c_size_t, P],
+    "unetr_resample_orient": [P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_double), c_int, c_int, c_int, P, P, P],
     "unetr_ranking_loss_fwd": [P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P, P, P, c_size_t, P],
     "unetr_ranking_loss_bwd": [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P],
     "unetr_adamw": [P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_float, P, P, P],

@@ -16,6 +16,7 @@ from typing import Optional, Sequence, Tuple, Union
 import torch
 
 from . import functional as Fn
+from . import preprocess
 from ._capi import AugDesc, call, load
 
 PARAM_COLS = 8          # params row: volume, corner z, y, x, flip mask (bit a = spatial axis a), k, shift flag, offset (float bits)
@@ -39,6 +40,7 @@ class VolumeCache:
         self.image_threshold = float(image_threshold)
         self._vols = []          # (image, label, fg, bg)
         self.shapes = []         # (C, L, D, H, W) per volume
+        self._affines = {}       # volume id -> 4x4 affine after add_raw's Spacing -> Orientation
         self._table = None
 
     def __len__(self):
@@ -103,6 +105,26 @@ class VolumeCache:
         self.shapes.append((C, L, d, h, w))
         self._table = None
         return len(self._vols) - 1
+
+    def add_raw(self, image: torch.Tensor, label: torch.Tensor, affine, pixdim: Sequence[float] = (1.0, 1.0, 1.0),
+                axcodes: str = "RAS", label_converter: Optional[str] = None, scale_range: Optional[Sequence[float]] = None,
+                crop_foreground: bool = False) -> int:
+        """A volume as LoadImaged leaves it (image [C, d0, d1, d2] float32 or int16, label [L, d0, d1, d2], both on the
+        device, and the file's 4x4 affine): Spacingd(pixdim, mode=("bilinear", "nearest")) -> Orientationd(axcodes), with
+        label_converter="brats" ConvertToMultiChannelBasedOnBratsClassesd on the label (preprocess.resample_orient), then add()."""
+        img, lbl, new_affine = preprocess.resample_orient(image, label, affine, pixdim, axcodes, label_converter)
+        i = self.add(img, lbl, scale_range=scale_range, crop_foreground=crop_foreground)
+        self._affines[i] = new_affine
+        return i
+
+    def affine(self, i: int):
+        """4x4 float64 affine of a volume added with add_raw, as Orientationd leaves it: MONAI 0.6.0's CropForegroundd does
+        not update the affine, so it describes the grid before the foreground crop."""
+        if not 0 <= i < len(self._vols):
+            raise IndexError(f"volume {i} out of range")
+        if i not in self._affines:
+            raise ValueError(f"volume {i} was added with add(): no affine is known")
+        return self._affines[i].copy()
 
     def image(self, i: int) -> torch.Tensor:
         return self._vols[i][0].unsqueeze(0)

@@ -35,7 +35,7 @@ extern "C" {
 /* Bumped whenever an exported signature or a descriptor struct changes.  A binding (3dmedicalimagesegmentation_amd/_capi.py, or a
  * C caller) must compare unetr_abi_version() with the UNETR_ABI_VERSION it was written against before its first call: a stale
  * .so would otherwise shift arguments silently (a stream pointer in an int slot). */
-#define UNETR_ABI_VERSION 19
+#define UNETR_ABI_VERSION 20
 int unetr_abi_version(void);
 
 /* ---- generic MFMA GEMM: C[M,N] = epilogue(A[M,K] * B[K,N]) ------------------------------------------
@@ -465,6 +465,17 @@ int unetr_aug_sample(const UnetrAugDesc* d, const long long* vols, int nvol, con
 size_t unetr_aug_gather_ws_bytes(const UnetrAugDesc* d);
 int unetr_aug_gather(const UnetrAugDesc* d, const long long* vols, int nvol, const int* params, float* x, float* y, void* ws,
                      size_t ws_bytes, void* stream);
+
+/* ---- per-volume resampling and reorientation (csrc/preprocess.hip; unetr_segmentation_3d.py:326-331) ----
+ * Spacingd(mode=("bilinear", "nearest")) -> Orientationd [-> ConvertToMultiChannelBasedOnBratsClassesd] as one gather: output voxel
+ * (j0, j1, j2) of oimg [C,D,H,W] (float32) / olbl [L,D,H,W] (uint8) reads the source [C|L, n0, n1, n2] at
+ * clamp(mat @ (j0, j1, j2, 1), 0, n - 1); mat is a HOST array of 12 doubles (3x4 row-major, preprocess.plan), evaluated in fp64 on
+ * the device.  Image: float32 source, or int16 when img_int16; trilinear with fp32 weights, or one tap when every entry of mat is
+ * an integer (a pure flip / transpose: values returned bit for bit).  Label: round-half-even nearest; lbl may be NULL (image
+ * only); brats = 1 reads a one-channel label and writes the L = 4 channels ==0, 2|3, 1|2|3, ==3.  1 <= C, L <= 8.
+ * UNETR_ERR_UNSUPPORTED for 2^31 or more source or output voxels.  No host synchronisation. */
+int unetr_resample_orient(const void* img, int img_int16, const unsigned char* lbl, int C, int L, int brats, int n0, int n1, int n2,
+                          const double* mat, int D, int H, int W, float* oimg, unsigned char* olbl, void* stream);
 
 /* ---- fused AdamW over one flat fp32 buffer (torch.optim.AdamW semantics; unetr_segmentation_3d.py:522) */
 int unetr_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
