@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("UNETR_AMD_LIB") or os.path.join(_HERE, "libunetr_hip.
 PREC_F32 = 0
 PREC_BF16 = 1
 PREC_BF16X3 = 2      # fp32 storage, operands split into bf16 (hi, lo) pairs inside the kernels (csrc/common.hpp: PrecBF16x3)
-ABI_VERSION = 20       # = UNETR_ABI_VERSION of include/unetr_hip.h this table of signatures was written against
+ABI_VERSION = 21       # = UNETR_ABI_VERSION of include/unetr_hip.h this table of signatures was written against
 
 _ERR = {1: "invalid argument", 2: "kernel launch failed", 3: "unsupported shape/configuration",
         4: "workspace too small"}
@@ -41,15 +41,6 @@ class GemmBf16Desc(ctypes.Structure):
         ("pre", c_void_p), ("aux", c_void_p), ("ldaux", c_long),
         ("act", c_int), ("accumulate", c_int), ("alpha", c_float),
         ("tc_d", c_int), ("tc_h", c_int), ("tc_w", c_int), ("tc_cout", c_int), ("x3", c_int),
-    ]
-
-
-class LnGemmDesc(ctypes.Structure):
-    _fields_ = [
-        ("x", c_void_p), ("ldx", c_long), ("gamma", c_void_p), ("beta", c_void_p), ("eps", c_float),
-        ("W", c_void_p), ("ldw", c_long), ("bias", c_void_p), ("act", c_int),
-        ("pre", c_void_p), ("ldpre", c_long), ("Cb", c_void_p), ("ldcb", c_long), ("C", c_void_p), ("ldc", c_long),
-        ("xn", c_void_p), ("mean", c_void_p), ("rstd", c_void_p), ("M", c_int), ("N", c_int), ("K", c_int),
     ]
 
 
@@ -97,7 +88,6 @@ _SIGNATURES = {
     "unetr_split_words": [P, P, c_long, P],
     "unetr_split_stack_bf16": [P, P, c_long, c_long, c_int, P],
     "unetr_split_stack_bf16_grouped": [ctypes.POINTER(SplitProblem), c_int, P],
-    "unetr_ln_gemm_bf16": [ctypes.POINTER(LnGemmDesc), P],
     "unetr_attention_bf16_fwd": [P, P, P, P, c_int, c_int, c_int, c_int, c_float, P],
     "unetr_attention_bf16_bwd": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P],
     "unetr_gemm_grouped_wgrad": [ctypes.POINTER(GroupedProblem), c_int, c_int, P],

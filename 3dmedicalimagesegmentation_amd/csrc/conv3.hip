@@ -1344,47 +1344,37 @@ __global__ void conv3_pack_1x1_kernel(const float* __restrict__ w3, T* __restric
 }
 
 // -------------------------------------------------------------------------------------- weight grad
-// workgroup = (voxel-tile group, ci slab of CIS 16-channel tiles, 16-channel co tile); 27*CIS (tap, ci-tile) units over
-// 4 waves.  CIS = 1 for <= 16 input channels (the 96^3 layers): half the window bytes in LDS, half the transposing reads
-// and MFMAs of the 32-channel slab (whose upper ci-tile would be all zeros there).
-template <class P, bool HAS3 = false, int CIS = 2> struct WgCfg {
+// workgroup = (voxel-tile group, 16-channel ci slab, 16-channel co tile); 27 tap units over 4 waves.
+template <class P, bool HAS3 = false> struct WgCfg {
     typedef typename ElemOf<P>::type T;
     static constexpr int ES = sizeof(T);
-    // image pitches: 16 B of padding when it is free; with the second dy image (HAS3) in bf16 the padding is dropped
-    // so that two workgroups still fit a CU (measured: 76 KB per workgroup = one workgroup per CU, 1.35x slower)
-    // FLIP: the bf16 16-channel slab (every weight gradient of the network by default): unpadded 32-byte voxels in the
-    // LAY 2 column order -- both transposing reads conflict-free (tools/lds_conflicts.py), 29 KB per workgroup
-    static constexpr bool FLIP = ES == 2 && CIS == 1;
-    static constexpr int PX = FLIP ? 32 : 16 * CIS * ES + ((HAS3 && ES == 2) ? 0 : 16);   // halo image pitch (16*CIS channels)
-    static constexpr int PY = FLIP ? 32 : 16 * ES + ((HAS3 && ES == 2) ? 8 : 16);        // dy image pitch (16 channels)
+    // FLIP: the bf16 slab: unpadded 32-byte voxels in the LAY 2 column order -- both transposing reads conflict-free
+    // (tools/lds_conflicts.py), 29 KB per workgroup; 4-byte elements: 16 B of padding per voxel
+    static constexpr bool FLIP = ES == 2;
+    static constexpr int PX = FLIP ? 32 : 16 * ES + 16;       // halo image pitch (16 channels)
+    static constexpr int PY = FLIP ? 32 : 16 * ES + 16;       // dy image pitch (16 channels)
     static constexpr int LAY = FLIP ? 2 : 0;
     static constexpr int KV = 4 * P::CH;      // voxels per MFMA k-block (32 bf16 / 16 f32)
     static constexpr int NKB = NVOX / KV;
-    static constexpr int NU = 27 * CIS;                       // (tap, ci-tile) units
-    static constexpr int NUX = NU + (HAS3 ? CIS : 0);         // + centre-tap units fed by dy3 (the 1x1x1 conv)
+    static constexpr int NU = 27;                             // tap units
+    static constexpr int NUX = NU + (HAS3 ? 1 : 0);           // + the centre-tap unit fed by dy3 (the 1x1x1 conv)
     static constexpr int UPW = (NUX + 3) / 4;                 // units per wave
 };
 
 // XMX: storage of x (see stage_halo); dy / dy3 are feature-map gradients: ActOf<P> (bf16 in bf16 mode -- VECY is then moot:
 // a 16-channel dy row is two 16-byte pieces)
-// resident weight-gradient workgroups per CU for the 16-channel slab: with the software-pipelined unit loop and the staging plans two
+// resident weight-gradient workgroups per CU: with the software-pipelined unit loop and the staging plans two
 // workgroups of <= 181 registers beat three with spills (5.17 vs 5.26 ms per step); the host sizes the grid to match
 #ifndef WG_LB
 #define WG_LB 2
 #endif
-template <int V> struct IntC { static constexpr int value = V; };
-// NSL = 16-channel input slabs per workgroup (1 or 2; 2 only on the bf16 / conflict-free-layout / planned-staging path): the dy
-// (and dy3) tile is staged ONCE per voxel tile and serves both slabs -- with one slab per workgroup the 32-channel layers staged it
-// twice, the 64-channel ones four times (PMC: 1.73x the algorithmic bytes for the family).  Per tile: window of slab 0 + dy ->
-// MFMAs of slab 0 (the window of slab 1 in flight) -> window of slab 1 over the same image -> MFMAs of slab 1 (the next tile's
-// slab-0 window + dy in flight); two accumulator sets.
-template <class P, int XMX, bool VECY, bool HAS3, int CIS, bool PIPE_OK, int NSL = 1>
-__global__ void __launch_bounds__(256, CIS == 1 ? ((HAS3 && !WgCfg<P, HAS3, CIS>::FLIP) ? 2 : WG_LB) : 1)   // CIS = 1: WG_LB workgroups per CU
+template <class P, int XMX, bool VECY, bool HAS3>
+__global__ void __launch_bounds__(256, (HAS3 && !WgCfg<P, HAS3>::FLIP) ? 2 : WG_LB)
 conv3_wgrad_kernel(const void* __restrict__ x, long ldx, const typename ActOf<P>::type* __restrict__ dy, long lddy, float* __restrict__ part,
                    const typename ActOf<P>::type* __restrict__ dy3, long lddy3, float* __restrict__ part3,
                    int D, int H, int W, int Cin, int Cout, int ntx, int nty, int ntz, int ntiles) {
     typedef typename ActOf<P>::type GT;
-    using C = WgCfg<P, HAS3, CIS>;
+    using C = WgCfg<P, HAS3>;
     typedef typename C::T T;
     constexpr int CH = P::CH, WG_UNITS = C::NU, WG_UPW = C::UPW;
     // dy3 != nullptr: also accumulate the 1x1x1 conv's weight gradient dw3[co][ci] = sum_v dy3[v,co] x[v,ci] of the
@@ -1395,8 +1385,7 @@ conv3_wgrad_kernel(const void* __restrict__ x, long ldx, const typename ActOf<P>
     char* y3img = yimg + NVOX * C::PY;
     constexpr int nunits = C::NUX;
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), c = lane & 15, g = lane >> 4;
-    static_assert(NSL == 1 || (CIS == 1 && PIPE_OK && XMX == 2 && sizeof(typename ElemOf<P>::type) == 2), "two slabs: fast path only");
-    const int ci0 = blockIdx.y * 16 * CIS * NSL, co0 = blockIdx.z * 16;
+    const int ci0 = blockIdx.y * 16, co0 = blockIdx.z * 16;
     // per-unit LDS byte offsets of the shifted window (wave-uniform)
     // FLIP layout: the column part of the address is per lane AND per tap column dx (the LAY 2 permutation is not a shift):
     // the three candidates of this lane's two voxel rows are formed once (they do not depend on the k-block: v & 15 is
@@ -1405,9 +1394,9 @@ conv3_wgrad_kernel(const void* __restrict__ x, long ldx, const typename ActOf<P>
 #pragma unroll
     for (int ui = 0; ui < WG_UPW; ++ui) {
         int u = wv + 4 * ui;
-        int tap = u >= WG_UNITS ? 13 : (u / CIS), cit = u >= WG_UNITS ? u - WG_UNITS : u % CIS;
+        int tap = u >= WG_UNITS ? 13 : u;
         int dz = tap / 9, rem = tap - dz * 9, dyy = rem / 3, dx = rem - dyy * 3;
-        uoff[ui] = ((dz * HY + dyy) * HX + (C::FLIP ? 0 : dx)) * C::PX + cit * 16 * C::ES;
+        uoff[ui] = ((dz * HY + dyy) * HX + (C::FLIP ? 0 : dx)) * C::PX;
     }
     // unit ui of wave wv handles tap wv + 4 ui, i.e. tap column dx = (wv + ui) % 3: the three column offsets are rotated
     // ONCE by the wave's phase, so unit ui simply takes entry ui % 3 (a compile-time index), and every per-lane address part
@@ -1431,11 +1420,9 @@ conv3_wgrad_kernel(const void* __restrict__ x, long ldx, const typename ActOf<P>
         ylane0 = lay_flip(8 * g + q) * C::PY + 8 * p;
         ylane1 = lay_flip(8 * g + q + 4) * C::PY + 8 * p;
     }
-    f32x4 acc[NSL][WG_UPW];
+    f32x4 acc[WG_UPW];
 #pragma unroll
-    for (int sl = 0; sl < NSL; ++sl)
-#pragma unroll
-        for (int ui = 0; ui < WG_UPW; ++ui) acc[sl][ui] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int ui = 0; ui < WG_UPW; ++ui) acc[ui] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     // dy tile(s): 256 voxels x 16 channels
     constexpr int YCH = 16 / CH, YIT = NVOX * YCH / 256, NQ = CH / 4;
@@ -1476,7 +1463,7 @@ conv3_wgrad_kernel(const void* __restrict__ x, long ldx, const typename ActOf<P>
             const int id = threadIdx.x + j * 256;
             const int v = id / YCH, ch = id - v * YCH;
             if constexpr (CH == 8) {
-                *(u32x4*)(img + (C::FLIP ? lay_flip(v) : v) * C::PY + ch * 16) = __builtin_bit_cast(u32x4, buf[j][0]);
+                *(u32x4*)(img + lay_flip(v) * C::PY + ch * 16) = __builtin_bit_cast(u32x4, buf[j][0]);
             } else {
                 float vals[CH];
 #pragma unroll
@@ -1485,16 +1472,15 @@ conv3_wgrad_kernel(const void* __restrict__ x, long ldx, const typename ActOf<P>
             }
         }
     };
-    // PIPE (16-channel slab only: the prefetch registers fit next to two resident workgroups per CU): the window and dy
-    // tile of the NEXT tile are loaded into registers while the MFMAs of the current one run.
-    constexpr bool PIPE = CIS == 1 && PIPE_OK;
-    HaloRegs<P, PIPE ? 16 / CH : 1> R;
+    // the window and dy tile of the NEXT tile are loaded into registers while the MFMAs of the current one run (the prefetch
+    // registers fit next to two resident workgroups per CU)
+    HaloRegs<P, 16 / CH> R;
     f32x4 ybuf[YIT][NQ], y3buf[HAS3 ? YIT : 1][NQ];
     TileTable tt;
     int kt = 0, tx = 0, ty = 0, tz = 0, b = 0;
     if ((int)blockIdx.x < ntiles) tt.get(0, ntiles, ntx, nty, ntz, tx, ty, tz, b);
     // tile-invariant staging plans (see HaloPlan): window pieces of x, and the two 16-byte pieces of the dy tile per thread
-    constexpr bool PLAN = PIPE && XMX == 2;
+    constexpr bool PLAN = XMX == 2;
     HaloPlan<PLAN ? 16 / CH : 1> xplan;
     int dyrel[YIT], dyrel3[HAS3 ? YIT : 1], dylo[YIT];
     if constexpr (PLAN) {
@@ -1506,16 +1492,14 @@ conv3_wgrad_kernel(const void* __restrict__ x, long ldx, const typename ActOf<P>
             const int vz = v >> 6, vy = (v >> 4) & 3, vx = v & 15;
             dyrel[j] = ((vz * H + vy) * W + vx) * (int)lddy + co0 + ch * CH;
             if constexpr (HAS3) dyrel3[j] = ((vz * H + vy) * W + vx) * (int)lddy3 + co0 + ch * CH;
-            dylo[j] = (C::FLIP ? lay_flip(v) : v) * C::PY + ch * 16;
+            dylo[j] = lay_flip(v) * C::PY + ch * 16;
         }
     }
     const long xitem = (long)D * H * W * ldx;
     // window + dy tile(s) of tile (b_, z_, y_, x_) into the prefetch registers
-    auto tile_load = [&](int b_, int z_, int y_, int x_, int c0_ = -1, bool with_dy = true) {
-        if (c0_ < 0) c0_ = ci0;
+    auto tile_load = [&](int b_, int z_, int y_, int x_) {
         if constexpr (PLAN) {
-            halo_load_planned<P, 16 / CH>(R, xplan, (const uint16_t*)x + b_ * xitem, (int)ldx, z_, y_, x_, D, H, W, c0_, Cin);
-            if (!with_dy) return;
+            halo_load_planned<P, 16 / CH>(R, xplan, (const uint16_t*)x + b_ * xitem, (int)ldx, z_, y_, x_, D, H, W, ci0, Cin);
             const bool interior = z_ + TZ <= D && y_ + TY <= H && x_ + TX <= W && co0 + 16 <= Cout;      // wave-uniform
             const long vb = (((long)b_ * D + z_) * H + y_) * W + x_;
             const GT* __restrict__ pdy = dy + vb * lddy;
@@ -1530,50 +1514,35 @@ conv3_wgrad_kernel(const void* __restrict__ x, long ldx, const typename ActOf<P>
                 ybuf[j][0] = __builtin_bit_cast(f32x4, act_chunk<P>(pdy + (ok ? dyrel[j] : 0), ok));
                 if constexpr (HAS3) y3buf[j][0] = __builtin_bit_cast(f32x4, act_chunk<P>(pdy3 + (ok ? dyrel3[j] : 0), ok));
             }
-        } else if constexpr (PIPE) {
+        } else {
             halo_load<P, 16 / CH, XMX>(R, x, ldx, b_, z_, y_, x_, D, H, W, ci0, Cin);
             load_dy(dy, lddy, b_, z_, y_, x_, ybuf);
             if constexpr (HAS3) load_dy(dy3, lddy3, b_, z_, y_, x_, y3buf);
         }
     };
-    if constexpr (PIPE) {
-        if ((int)blockIdx.x < ntiles) {
-            tile_load(b, tz * TZ, ty * TY, tx * TX);
-        }
-    }
+    if ((int)blockIdx.x < ntiles) tile_load(b, tz * TZ, ty * TY, tx * TX);
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x, ++kt) {
         int ax = tx, ay = ty, az = tz, ab = b;            // the next tile's coordinates
         if (tile + (int)gridDim.x < ntiles) tt.get(kt + 1, ntiles, ntx, nty, ntz, ax, ay, az, ab);
-        const int x0 = tx * TX, y0 = ty * TY, z0 = tz * TZ;
         __syncthreads();
-        if constexpr (PIPE) {
-            if constexpr (PLAN) {
-                halo_store_planned<P, 16 / CH>(R, xplan, ximg);
+        if constexpr (PLAN) {
+            halo_store_planned<P, 16 / CH>(R, xplan, ximg);
 #pragma unroll
-                for (int j = 0; j < YIT; ++j) {
-                    *(u32x4*)(yimg + dylo[j]) = __builtin_bit_cast(u32x4, ybuf[j][0]);
-                    if constexpr (HAS3) *(u32x4*)(y3img + dylo[j]) = __builtin_bit_cast(u32x4, y3buf[j][0]);
-                }
-            } else {
-                halo_store<P, 16 / CH, XMX, C::LAY>(R, C::PX, ximg);
-                store_dy(ybuf, yimg);
-                if constexpr (HAS3) store_dy(y3buf, y3img);
+            for (int j = 0; j < YIT; ++j) {
+                *(u32x4*)(yimg + dylo[j]) = __builtin_bit_cast(u32x4, ybuf[j][0]);
+                if constexpr (HAS3) *(u32x4*)(y3img + dylo[j]) = __builtin_bit_cast(u32x4, y3buf[j][0]);
             }
-            __syncthreads();
-            const int nt = tile + gridDim.x;
-            if constexpr (NSL == 2) tile_load(b, z0, y0, x0, ci0 + 16, false);      // this tile's second slab: window only
-            else if (nt < ntiles) tile_load(ab, az * TZ, ay * TY, ax * TX);
         } else {
-            stage_halo<P, 16 * CIS / CH, XMX, C::LAY>(x, ldx, b, z0, y0, x0, D, H, W, ci0, Cin, C::PX, ximg);
-            load_dy(dy, lddy, b, z0, y0, x0, ybuf);
+            halo_store<P, 16 / CH, XMX, C::LAY>(R, C::PX, ximg);
             store_dy(ybuf, yimg);
-            if constexpr (HAS3) { load_dy(dy3, lddy3, b, z0, y0, x0, y3buf); store_dy(y3buf, y3img); }
-            __syncthreads();
+            if constexpr (HAS3) store_dy(y3buf, y3img);
         }
+        __syncthreads();
+        const int nt = tile + gridDim.x;
+        if (nt < ntiles) tile_load(ab, az * TZ, ay * TY, ax * TX);
 
-        auto fast_compute = [&](auto slc) __attribute__((always_inline)) {
-            constexpr int SLAB = decltype(slc)::value;
-            // bf16, 16-channel slab, conflict-free layout: every per-lane address part is k-block independent (formed once before
+        if constexpr (CH == 8 && XMX == 2) {
+            // bf16, conflict-free layout: every per-lane address part is k-block independent (formed once before
             // the loop: ylane0/1, xs0/1[3]); per read one add of a wave-uniform (k-block, unit) offset.  The NKB x UPW (k-block,
             // unit) steps run as ONE straight line, software-pipelined: the x fragments of the next DPT steps and the dy fragment
             // of the next k-block are in flight while a step's MFMA runs (as a guarded loop every MFMA waited for its own two
@@ -1609,27 +1578,14 @@ conv3_wgrad_kernel(const void* __restrict__ x, long ldx, const typename ActOf<P>
                 const s16x4 blo = rlo[st % DPT], bhi = rhi[st % DPT];
                 s16x8 b8 = {blo[0], blo[1], blo[2], blo[3], bhi[0], bhi[1], bhi[2], bhi[3]};
                 const bool ext1 = HAS3 && ui == WG_UPW - 1 && wv + 4 * ui >= WG_UNITS;
-                P::mma(acc[SLAB][ui], ext1 ? af3 : af[kb & 1], __builtin_bit_cast(u32x4, b8));
+                P::mma(acc[ui], ext1 ? af3 : af[kb & 1], __builtin_bit_cast(u32x4, b8));
                 if (st + DPT < NST) bread(st + DPT, rlo[st % DPT], rhi[st % DPT]);
                 __builtin_amdgcn_sched_barrier(0);
             }
-        };
-        if constexpr (CH == 8 && C::FLIP && XMX == 2) {
-            fast_compute(IntC<0>{});
-            if constexpr (NSL == 2) {
-                // second slab of the same voxel tile: its window replaces the first one's (the dy images stay), and the next tile's
-                // first-slab window + dy tiles go in flight under its MFMAs
-                __syncthreads();
-                halo_store_planned<P, 16 / CH>(R, xplan, ximg);
-                __syncthreads();
-                if (tile + (int)gridDim.x < ntiles) tile_load(ab, az * TZ, ay * TY, ax * TX);
-                fast_compute(IntC<NSL - 1>{});
-            }
         } else
         for (int kb = 0; kb < C::NKB; ++kb) {
-            if constexpr (CH == 8 && C::FLIP) {
-                // bf16, 16-channel slab, conflict-free layout: every per-lane address part is k-block independent (formed once
-                // before the loop: ylane0/1, xs0/1[3]); per read one add of a wave-uniform (k-block, unit) offset
+            if constexpr (CH == 8) {
+                // bf16 on the fp32-stored image, conflict-free layout: the same addressing as a guarded loop
                 typedef short s16x8 __attribute__((ext_vector_type(8)));
                 const int ykb = kb * 32 * C::PY;
                 s16x4 alo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(yimg + ykb + ylane0));
@@ -1652,36 +1608,7 @@ conv3_wgrad_kernel(const void* __restrict__ x, long ldx, const typename ActOf<P>
                         s16x4 blo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(ximg + uo + (ext1 ? xc0 : xs0[ui % 3])));
                         s16x4 bhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(ximg + uo + (ext1 ? xc1 : xs1[ui % 3])));
                         s16x8 b8 = {blo[0], blo[1], blo[2], blo[3], bhi[0], bhi[1], bhi[2], bhi[3]};
-                        P::mma(acc[0][ui], ext1 ? afrag3 : afrag, __builtin_bit_cast(u32x4, b8));
-                    }
-                }
-            } else if constexpr (CH == 8) {
-                // bf16: k-block = 32 voxels; lane (c = 4q+p, g) addresses voxel rows 8g+q and 8g+4+q
-                const int q = c >> 2, p = c & 3;
-                const int v0 = kb * 32 + 8 * g + q, v1 = v0 + 4;
-                LDS_AS s16x4* ya0 = (LDS_AS s16x4*)(yimg + v0 * C::PY + 8 * p);
-                LDS_AS s16x4* ya1 = (LDS_AS s16x4*)(yimg + v1 * C::PY + 8 * p);
-                s16x4 alo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(ya0);
-                s16x4 ahi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(ya1);
-                typedef short s16x8 __attribute__((ext_vector_type(8)));
-                s16x8 a8 = {alo[0], alo[1], alo[2], alo[3], ahi[0], ahi[1], ahi[2], ahi[3]};
-                const u32x4 afrag = __builtin_bit_cast(u32x4, a8);
-                u32x4 afrag3 = afrag;
-                if constexpr (HAS3) {
-                    s16x4 clo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(y3img + v0 * C::PY + 8 * p));
-                    s16x4 chi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(y3img + v1 * C::PY + 8 * p));
-                    s16x8 c8 = {clo[0], clo[1], clo[2], clo[3], chi[0], chi[1], chi[2], chi[3]};
-                    afrag3 = __builtin_bit_cast(u32x4, c8);
-                }
-                const int h0 = (((v0 >> 6) * HY + ((v0 >> 4) & 3)) * HX + (v0 & 15)) * C::PX + 8 * p;
-                const int h1 = (((v1 >> 6) * HY + ((v1 >> 4) & 3)) * HX + (v1 & 15)) * C::PX + 8 * p;
-#pragma unroll
-                for (int ui = 0; ui < WG_UPW; ++ui) {
-                    if (wv + 4 * ui < nunits) {
-                        s16x4 blo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(ximg + h0 + uoff[ui]));
-                        s16x4 bhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(ximg + h1 + uoff[ui]));
-                        s16x8 b8 = {blo[0], blo[1], blo[2], blo[3], bhi[0], bhi[1], bhi[2], bhi[3]};
-                        P::mma(acc[0][ui], (ui == WG_UPW - 1 && wv + 4 * ui >= WG_UNITS) ? afrag3 : afrag, __builtin_bit_cast(u32x4, b8));
+                        P::mma(acc[ui], ext1 ? afrag3 : afrag, __builtin_bit_cast(u32x4, b8));
                     }
                 }
             } else {
@@ -1703,7 +1630,7 @@ conv3_wgrad_kernel(const void* __restrict__ x, long ldx, const typename ActOf<P>
                         u32x4 bv;
 #pragma unroll
                         for (int tt = 0; tt < 4; ++tt) bv[tt] = *(const uint32_t*)(ximg + hb[tt] + uoff[ui]);
-                        P::mma(acc[0][ui], ext ? av3 : av, bv);
+                        P::mma(acc[ui], ext ? av3 : av, bv);
                     }
                 }
             }
@@ -1712,19 +1639,16 @@ conv3_wgrad_kernel(const void* __restrict__ x, long ldx, const typename ActOf<P>
     }
     // partial sums: part[blockIdx.x][co][ci][tap]
 #pragma unroll
-    for (int sl = 0; sl < NSL; ++sl)
-#pragma unroll
     for (int ui = 0; ui < WG_UPW; ++ui) {
         int u = wv + 4 * ui;
         if (u < nunits) {
-            int tap = u / CIS, cit = u >= WG_UNITS ? u - WG_UNITS : u % CIS;
-            int ci = ci0 + sl * 16 + cit * 16 + c;
+            int ci = ci0 + c;
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
                 int co = co0 + 4 * g + rr;
                 if (ci < Cin && co < Cout) {
-                    if (u < WG_UNITS) part[(((long)blockIdx.x * Cout + co) * Cin + ci) * 27 + tap] = acc[sl][ui][rr];
-                    else part3[((long)blockIdx.x * Cout + co) * Cin + ci] = acc[sl][ui][rr];
+                    if (u < WG_UNITS) part[(((long)blockIdx.x * Cout + co) * Cin + ci) * 27 + u] = acc[ui][rr];
+                    else part3[((long)blockIdx.x * Cout + co) * Cin + ci] = acc[ui][rr];
                 }
             }
         }
@@ -1740,7 +1664,7 @@ conv3_wgrad_kernel(const void* __restrict__ x, long ldx, const typename ActOf<P>
 // and runs the bf16 kernel's software-pipelined (k-block, unit) line with three MFMAs per step,
 //     dw += dy_hi x_hi + dy_hi x_lo + dy_lo x_hi        (v_mfma_f32_16x16x32_bf16, fp32 accumulate; the lo-lo term is 2^-16 of the sum)
 // four ds_read_b64_tr_b16 per 3 MFMAs over 32 voxels instead of eight ds_read_b32 per 4 MFMAs.  16-channel input slab, 16-channel
-// output tile, one partial row per workgroup -- grid and partial layout of conv3_wgrad_kernel<P, ., ., HAS3, 1, .>.
+// output tile, one partial row per workgroup -- grid and partial layout of conv3_wgrad_kernel.
 // XS: fewer than four input channels (the image in front of encoder1): the window is read channel by channel.
 template <bool HAS3, bool XS = false>
 __global__ void __launch_bounds__(256, 2)
@@ -2106,10 +2030,6 @@ __global__ void tr16_probe_kernel(const uint16_t* __restrict__ in, uint16_t* __r
 
 // the pair layout is used for bf16 with <= 16 contraction channels (K = Cin forward, Cout for the data gradient)
 template <class P> inline bool use_pair(int K) { return P::CH == 8 && K <= 16; }
-inline int conv_pipe_enabled() {   // tuning hook: UNETR_CONV_PIPE=0 selects the one-tile-per-workgroup kernel
-    const char* e = getenv("UNETR_CONV_PIPE");
-    return e ? atoi(e) : 1;
-}
 
 // ---- all weight re-packs of a step in ONE launch (run by the optimizer right after the update) ---------------------------
 // kind 0 / 1: 3x3x3 forward / data-gradient layout (pair layout when the contraction has <= 16 channels in bf16),
@@ -2200,7 +2120,7 @@ template <class P>
 int pack_t(const float* w, void* wp, int Cin, int Cout, int mode, hipStream_t st) {
     typedef typename ElemOf<P>::type T;
     const int SL = 4 * P::CH, K = mode ? Cout : Cin, N = mode ? Cin : Cout;
-    if (use_pair<P>(K) && conv_pipe_enabled()) {
+    if (use_pair<P>(K)) {
         long total = 14L * N * 32;
         hipLaunchKernelGGL(conv3_pack_pair_kernel, dim3((int)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, st, w,
                            (uint16_t*)wp, Cin, Cout, mode);
@@ -2237,15 +2157,20 @@ int fwd_t(const void* x, long ldx, const void* wp, void* yv, long ldy, int accum
     }
     if (B16 && fz && fz->k3 > 0 && ((fz->ldy3 & 7) || ((uintptr_t)fz->y3 & 15) || (fz->k3 & 7))) return UNETR_ERR_UNSUPPORTED;
     if ((long)D * H * W * ldx >= (1L << 31)) return UNETR_ERR_UNSUPPORTED;      // 32-bit in-item offsets (halo_load)
+    // persistent grid: at most cap resident workgroups (UNETR_TEST_MAX_WG: test hook, long tile walks).  A workgroup that walks several
+    // tiles must see them in non-decreasing batch order (the fused statistics are flushed when the batch item changes): tile_coords
+    // guarantees that for grids that are multiples of the 8 XCDs
+    auto grid_x = [&](long cap) {
+        if (const char* e = getenv("UNETR_TEST_MAX_WG")) { if (atoi(e) > 0) cap = std::min<long>(cap, atoi(e)); }
+        if (cap < spatial) cap = std::max<long>(8, cap / 8 * 8);
+        return (unsigned)std::min<long>(spatial, cap);
+    };
     if constexpr (B16) {
         // the single-channel image -> 16 channels with fused statistics (and the 1x1x1 branch): the dedicated one-MFMA kernel
-        if (conv_pipe_enabled() && x_f32 && Cin == 1 && Cout == 16 && ldx == 1 && fz && fz->k3 == 0 && !accumulate && use_pair<P>(Cin) &&
+        if (x_f32 && Cin == 1 && Cout == 16 && ldx == 1 && fz && fz->k3 == 0 && !accumulate && use_pair<P>(Cin) &&
             ntx < 256 && nty < 256 && ntz < 256 && B < 256 && (ldy & 3) == 0 && ((uintptr_t)y & 7) == 0 && (long)D * H * W < (1L << 31) &&
             (!fz->y3 || (((uintptr_t)fz->y3 & 7) == 0 && fz->ldy3 == ldy)) && !getenv("UNETR_CONV_C1_OFF")) {
-            long cap = 1024;
-            if (const char* e = getenv("UNETR_TEST_MAX_WG")) { if (atoi(e) > 0) cap = std::min<long>(cap, atoi(e)); }
-            if (cap < spatial) cap = std::max<long>(8, cap / 8 * 8);
-            const unsigned gx = (unsigned)std::min<long>(spatial, cap);
+            const unsigned gx = grid_x(1024);
             fz->rows = (int)gx;
             hipLaunchKernelGGL(conv3_c1_fwd_kernel, dim3(gx), dim3(256), 0, st, (const float*)x, (const uint16_t*)wp, (uint16_t*)y, ldy, D, H, W,
                                ntx, nty, ntz, (int)spatial, fz->part, (const uint16_t*)fz->wp3, (uint16_t*)fz->y3, fz->part3);
@@ -2254,20 +2179,17 @@ int fwd_t(const void* x, long ldx, const void* wp, void* yv, long ldy, int accum
     }
     if constexpr (std::is_same<P, PrecBF16x3>::value) {
         // bf16x3: the same single-channel form on split operands
-        if (conv_pipe_enabled() && Cin == 1 && Cout == 16 && ldx == 1 && fz && fz->k3 == 0 && !accumulate && ntx < 256 && nty < 256 && ntz < 256 &&
+        if (Cin == 1 && Cout == 16 && ldx == 1 && fz && fz->k3 == 0 && !accumulate && ntx < 256 && nty < 256 && ntz < 256 &&
             B < 256 && (ldy & 3) == 0 && ((uintptr_t)y & 15) == 0 && (long)D * H * W < (1L << 31) &&
             (!fz->y3 || (((uintptr_t)fz->y3 & 15) == 0 && fz->ldy3 == ldy)) && !getenv("UNETR_CONV_C1_OFF")) {
-            long cap = 1024;
-            if (const char* e = getenv("UNETR_TEST_MAX_WG")) { if (atoi(e) > 0) cap = std::min<long>(cap, atoi(e)); }
-            if (cap < spatial) cap = std::max<long>(8, cap / 8 * 8);
-            const unsigned gx = (unsigned)std::min<long>(spatial, cap);
+            const unsigned gx = grid_x(1024);
             fz->rows = (int)gx;
             hipLaunchKernelGGL(conv3_c1_fwd_x3_kernel, dim3(gx), dim3(256), 0, st, (const float*)x, (const uint32_t*)wp, (float*)y, ldy, D, H, W,
                                ntx, nty, ntz, (int)spatial, fz->part, (const uint32_t*)fz->wp3, (float*)fz->y3, fz->part3);
             return unetr_check_launch();
         }
     }
-    if (conv_pipe_enabled() && ntb <= 4 && ntx < 256 && nty < 256 && ntz < 256 && B < 256) {      // (TileTable packs the coordinates in bytes)
+    if (ntb <= 4 && ntx < 256 && nty < 256 && ntz < 256 && B < 256) {      // (TileTable packs the coordinates in bytes)
         // persistent, software-pipelined kernel: a few resident workgroups per CU walk the tiles
         const bool pair = use_pair<P>(Cin);
         if (B16 && xm != 2 && !pair) return UNETR_ERR_UNSUPPORTED;   // fp32 input in bf16 mode = the image: pair layout only
@@ -2279,14 +2201,8 @@ int fwd_t(const void* x, long ldx, const void* wp, void* yv, long ldy, int accum
         int wl = pair ? 0 : (nslab == 1 ? 1 : 2);
         if (!pair && NHALO * 64 + wl * 27 * ntb * 1024 > 160 * 1024) wl = 0;
         const bool two = pair || NHALO * 64 + wl * 27 * ntb * 1024 <= 80 * 1024;
-        long cap = two ? 512 : 256;   // resident workgroups (VGPR / LDS-limited); more would queue behind them
-        if (const char* e = getenv("UNETR_CONV_CAP")) { if (pair && atoi(e) > 0) cap = atoi(e); }      // tuning hook (pair layout)
-        if (const char* e = getenv("UNETR_CONV_CAP_SLAB")) { if (!pair && two && atoi(e) > 0) cap = atoi(e); }
-        if (const char* e = getenv("UNETR_TEST_MAX_WG")) { if (atoi(e) > 0) cap = std::min<long>(cap, atoi(e)); }   // test hook: long tile walks
-        // a workgroup that walks several tiles must see them in non-decreasing batch order (the fused statistics are flushed when
-        // the batch item changes): tile_coords guarantees that for grids that are multiples of the 8 XCDs
-        if (cap < spatial) cap = std::max<long>(8, cap / 8 * 8);
-        dim3 pgrid((unsigned)std::min<long>(spatial, cap), ntn / ntb);
+        // resident workgroups (VGPR / LDS-limited); more would queue behind them
+        dim3 pgrid(grid_x(two ? 512 : 256), ntn / ntb);
 #define LAUNCH_PIPE_F(NTB_, PAIR_, XM_, FUSE_, WL_)                                                                               \
     hipLaunchKernelGGL((conv3_fwd_pipe_kernel<P, NTB_, PAIR_, XM_, FUSE_, WL_>), pgrid, dim3(256), 0, st, x, ldx, (const char*)wp, y, ldy, \
                        accumulate, D, H, W, Cin, Cout, ntx, nty, ntz, (int)spatial, fz ? fz->part : nullptr,                       \
@@ -2371,26 +2287,37 @@ int wgrad_t(const void* x, long ldx, const void* dyv, long lddy, float* dw, cons
     if (ntx > 255 || nty > 255 || ntz > 255 || B > 255) return UNETR_ERR_UNSUPPORTED;     // TileTable packs the coordinates in bytes
     if ((long)D * H * W * lddy >= (1L << 31) || (dy3 && (long)D * H * W * lddy3 >= (1L << 31))) return UNETR_ERR_UNSUPPORTED;   // 32-bit in-tile offsets
     // 16-channel slabs everywhere (measured: 32->16 @ 96^3 200 -> 170 us, 64->32 @ 48^3 133 -> 88 us, step -0.16 ms): the dy tile is
-    // re-staged once per slab, but three pipelined workgroups per CU beat two with the 32-channel window.  UNETR_WG_CIS1 = largest
-    // Cin that still takes the 16-channel variant (tuning hook).
+    // re-staged once per slab, but three pipelined workgroups per CU beat two with the 32-channel window.
+    // common tail of the three forms: G partial rows of n (+ n3 for the 1x1x1 branch) floats in ws, launch(G, ws3), reduction
+    auto finish = [&](long G, long n, long n3, bool shrink, auto&& launch) -> int {
+        if (rows_only) { *rows_only = G; return UNETR_OK; }
+        while (shrink && G > 1 && (size_t)G * (n + n3) * sizeof(float) > ws_bytes) G >>= 1;
+        if (!ws || (size_t)G * (n + n3) * sizeof(float) > ws_bytes) return UNETR_ERR_WORKSPACE;
+        if (rows_used) *rows_used = G;
+        float* ws3 = ws + (size_t)G * n;
+        if (const int rc = launch(G, ws3)) return rc;
+        const int blocks = (int)std::min<long>((n + 31) / 32, 16384);
+        const int blocks3 = dy3 ? (int)std::min<long>((n3 + 31) / 32, 16384) : 0;
+        if (!parts_only)
+            hipLaunchKernelGGL(conv3_wgrad_reduce_kernel, dim3(blocks + blocks3), dim3(256), 0, st, ws, (int)G, n, dw, blocks,
+                               (const float*)ws3, n3, dw3);
+        return unetr_check_launch();
+    };
+    auto max_wg = [](long G) {          // test hook: long tile walks
+        if (const char* e = getenv("UNETR_TEST_MAX_WG")) { if (atoi(e) > 0) G = std::min<long>(G, atoi(e)); }
+        return G;
+    };
+    const int nci = cdiv(Cin, 16), nco = cdiv(Cout, 16);
+    const long n = 27L * Cin * Cout, n3 = dy3 ? (long)Cin * Cout : 0;
     if constexpr (B16) {
         // the single-channel image (encoder1's first conv + its 1x1x1 branch): the dedicated tap-column kernel
         if (x_f32 && Cin == 1 && Cout == 16 && ldx == 1 && ((uintptr_t)dy & 15) == 0 && (lddy & 7) == 0 &&
-            (!dy3 || (((uintptr_t)dy3 & 15) == 0 && (lddy3 & 7) == 0)) && (long)D * H * W < (1L << 31) && !getenv("UNETR_CONV_C1_OFF")) {
-            long G = std::min<long>(1024, ntiles);
-            if (const char* e = getenv("UNETR_TEST_MAX_WG")) { if (atoi(e) > 0) G = std::min<long>(G, atoi(e)); }
-            if (rows_only) { *rows_only = G; return UNETR_OK; }
-            const long n1 = 27L * 16, n31 = dy3 ? 16 : 0, rows = G;
-            if (!ws || (size_t)rows * (n1 + n31) * sizeof(float) > ws_bytes) return UNETR_ERR_WORKSPACE;
-            if (rows_used) *rows_used = rows;
-            float* wsb = ws + (size_t)rows * n1;
-            hipLaunchKernelGGL(conv3_c1_wgrad_kernel, dim3((unsigned)G), dim3(256), 0, st, (const float*)x, (const uint16_t*)dy, lddy, (const uint16_t*)dy3, lddy3,
-                               ws, wsb, D, H, W, ntx, nty, ntz, (int)ntiles);
-            const int blocks = (int)cdiv(n1, 32), blocks3 = dy3 ? 1 : 0;
-            if (!parts_only)
-                hipLaunchKernelGGL(conv3_wgrad_reduce_kernel, dim3(blocks + blocks3), dim3(256), 0, st, ws, (int)rows, n1, dw, blocks, (const float*)wsb, n31, dw3);
-            return unetr_check_launch();
-        }
+            (!dy3 || (((uintptr_t)dy3 & 15) == 0 && (lddy3 & 7) == 0)) && (long)D * H * W < (1L << 31) && !getenv("UNETR_CONV_C1_OFF"))
+            return finish(max_wg(std::min<long>(1024, ntiles)), n, n3, false, [&](long G, float* ws3) {
+                hipLaunchKernelGGL(conv3_c1_wgrad_kernel, dim3((unsigned)G), dim3(256), 0, st, (const float*)x, (const uint16_t*)dy, lddy,
+                                   (const uint16_t*)dy3, lddy3, ws, ws3, D, H, W, ntx, nty, ntz, (int)ntiles);
+                return UNETR_OK;
+            });
     }
     if constexpr (std::is_same<P, PrecBF16x3>::value) {
         // bf16x3: the (hi, lo) bf16-image kernel (conv3_wgrad_x3_kernel) wherever rows of x / dy / dy3 are whole 16-byte quads of channels
@@ -2399,88 +2326,49 @@ int wgrad_t(const void* x, long ldx, const void* dyv, long lddy, float* dw, cons
         const bool yq16 = (((uintptr_t)dy | (uintptr_t)dy3) & 15) == 0 && (lddy & 3) == 0 && (Cout & 3) == 0 && (!dy3 || (lddy3 & 3) == 0);
         const bool xq16 = ((uintptr_t)x & 15) == 0 && (ldx & 3) == 0 && (Cin & 3) == 0;
         const bool xs = Cin < 4;                 // the image: scalar window loads
-        if (yq16 && (xq16 || xs) && !(e && atoi(e) == 0)) {
-            const int nci = cdiv(Cin, 16), nco = cdiv(Cout, 16);
-            const long n = 27L * Cin * Cout, n3 = dy3 ? (long)Cin * Cout : 0;
-            long G = std::min<long>(ntiles, std::max<long>(1, 512 / ((long)nci * nco)));
-            if (const char* t = getenv("UNETR_TEST_MAX_WG")) { if (atoi(t) > 0) G = std::min<long>(G, atoi(t)); }
-            if (rows_only) { *rows_only = G; return UNETR_OK; }
-            while (G > 1 && (size_t)G * (n + n3) * sizeof(float) > ws_bytes) G >>= 1;
-            if (!ws || (size_t)G * (n + n3) * sizeof(float) > ws_bytes) return UNETR_ERR_WORKSPACE;
-            if (nci > 65535 || nco > 65535) return UNETR_ERR_ARG;
-            if (rows_used) *rows_used = G;
-            float* ws3 = ws + (size_t)G * n;
+        if (yq16 && (xq16 || xs) && !(e && atoi(e) == 0))
+            return finish(max_wg(std::min<long>(ntiles, std::max<long>(1, 512 / ((long)nci * nco)))), n, n3, true, [&](long G, float* ws3) {
+                if (nci > 65535 || nco > 65535) return UNETR_ERR_ARG;
 #define X3W_GO(H3_, XS_) hipLaunchKernelGGL((conv3_wgrad_x3_kernel<H3_, XS_>), dim3((unsigned)G, nci, nco), dim3(256), 0, st, (const float*)x, ldx, (const float*)dy, lddy, ws, \
                                             (const float*)dy3, lddy3, ws3, D, H, W, Cin, Cout, ntx, nty, ntz, (int)ntiles)
-            if (dy3) { if (xs) X3W_GO(true, true); else X3W_GO(true, false); }
-            else { if (xs) X3W_GO(false, true); else X3W_GO(false, false); }
+                if (dy3) { if (xs) X3W_GO(true, true); else X3W_GO(true, false); }
+                else { if (xs) X3W_GO(false, true); else X3W_GO(false, false); }
 #undef X3W_GO
-            const int blocks = (int)std::min<long>((n + 31) / 32, 16384);
-            const int blocks3 = dy3 ? (int)std::min<long>((n3 + 31) / 32, 16384) : 0;
-            if (!parts_only)
-                hipLaunchKernelGGL(conv3_wgrad_reduce_kernel, dim3(blocks + blocks3), dim3(256), 0, st, ws, (int)G, n, dw, blocks, (const float*)ws3, n3, dw3);
-            return unetr_check_launch();
+                return UNETR_OK;
+            });
+    }
+    // persistent workgroups: all of them resident at once
+    const long G0 = std::min(std::max<long>(1, ((dy3 && !B16) ? 512 : 256 * WG_LB) / ((long)nci * nco)), ntiles);
+    return finish(max_wg(G0), n, n3, true, [&](long G, float* ws3) {
+        const int vecy3 = (dy3 && ((uintptr_t)dy3 & 15) == 0 && (lddy3 & 3) == 0 && (Cout & 3) == 0) ? 1 : 0;
+        if (nci > 65535 || nco > 65535) return UNETR_ERR_ARG;
+        int vecx = (((uintptr_t)x & 15) == 0 && (ldx & 3) == 0 && (Cin & 3) == 0) ? 1 : 0;      // XMX
+        const int vecy = (((uintptr_t)dy & 15) == 0 && (lddy & 3) == 0 && (Cout & 3) == 0) ? 1 : 0;
+        const bool vy = vecy && (!dy3 || vecy3);
+        if (B16) {
+            // bf16-stored gradients (and input, unless it is the fp32 image): whole 16-byte pieces of 8 channels
+            if (((uintptr_t)dy & 15) || (lddy & 7) || (Cout & 7) || (dy3 && (((uintptr_t)dy3 & 15) || (lddy3 & 7)))) return UNETR_ERR_UNSUPPORTED;
+            if (!x_f32) {
+                if (((uintptr_t)x & 15) || (ldx & 7) || (Cin & 7)) return UNETR_ERR_UNSUPPORTED;
+                vecx = 2;
+            }
         }
-    }
-    const int cis = Cin <= (getenv("UNETR_WG_CIS1") ? atoi(getenv("UNETR_WG_CIS1")) : (1 << 30)) ? 1 : 2;
-    // UNETR_WG_NSL=2: two 16-channel slabs per workgroup (the dy / dy3 tile staged once for both) where the fast path applies and the
-    // slabs pair up.  OFF by default: measured SLOWER on MI355X (same box, three interleaved rounds: 5.03 / 5.12 / 5.03 ms per step
-    // against 4.93 / 4.92 / 4.91) -- the kernel is bound by latency and instruction issue, not by the 22 % of bytes this saves, and
-    // half as many workgroups share a tile's work.  (The same verdict as the 32-channel window of round 2.)
-    const int nsl = (B16 && cis == 1 && !x_f32 && Cin % 32 == 0 && getenv("UNETR_WG_NSL") && atoi(getenv("UNETR_WG_NSL")) == 2) ? 2 : 1;
-    const int nci = cdiv(Cin, 16 * cis * nsl), nco = cdiv(Cout, 16);
-    const long n = 27L * Cin * Cout;
-    // persistent workgroups: all of them resident at once (3 per CU with the 16-channel slab, else 2 rounds of 2 per CU)
-    long G = std::max<long>(1, (cis == 1 ? ((dy3 && !B16) ? 512 : 256 * WG_LB) : 1024) / ((long)nci * nco));
-    G = std::min(G, ntiles);
-    if (const char* e = getenv("UNETR_TEST_MAX_WG")) { if (atoi(e) > 0) G = std::min<long>(G, atoi(e)); }   // test hook: long tile walks
-    const long n3 = dy3 ? (long)Cin * Cout : 0;
-    if (rows_only) { *rows_only = G; return UNETR_OK; }
-    while (G > 1 && (size_t)G * (n + n3) * sizeof(float) > ws_bytes) G >>= 1;
-    if (!ws || (size_t)G * (n + n3) * sizeof(float) > ws_bytes) return UNETR_ERR_WORKSPACE;
-    if (rows_used) *rows_used = G;
-    float* ws3 = ws + (size_t)G * n;
-    const int vecy3 = (dy3 && ((uintptr_t)dy3 & 15) == 0 && (lddy3 & 3) == 0 && (Cout & 3) == 0) ? 1 : 0;
-    if (nci > 65535 || nco > 65535) return UNETR_ERR_ARG;
-    int vecx = (((uintptr_t)x & 15) == 0 && (ldx & 3) == 0 && (Cin & 3) == 0) ? 1 : 0;      // XMX
-    const int vecy = (((uintptr_t)dy & 15) == 0 && (lddy & 3) == 0 && (Cout & 3) == 0) ? 1 : 0;
-    const bool vy = vecy && (!dy3 || vecy3);
-    if (B16) {
-        // bf16-stored gradients (and input, unless it is the fp32 image): whole 16-byte pieces of 8 channels
-        if (((uintptr_t)dy & 15) || (lddy & 7) || (Cout & 7) || (dy3 && (((uintptr_t)dy3 & 15) || (lddy3 & 7)))) return UNETR_ERR_UNSUPPORTED;
-        if (!x_f32) {
-            if (((uintptr_t)x & 15) || (ldx & 7) || (Cin & 7)) return UNETR_ERR_UNSUPPORTED;
-            vecx = 2;
+#define LAUNCH_WG_C(VX_, VY_, H3_)                                                                                                \
+    hipLaunchKernelGGL((conv3_wgrad_kernel<P, VX_, VY_, H3_>), dim3((unsigned)G, nci, nco), dim3(256), 0, st, x, ldx, dy, lddy,   \
+                       ws, dy3, lddy3, ws3, D, H, W, Cin, Cout, ntx, nty, ntz, (int)ntiles)
+#define LAUNCH_WG(VX_, VY_) do { if (dy3) LAUNCH_WG_C(VX_, VY_, true); else LAUNCH_WG_C(VX_, VY_, false); } while (0)
+        if constexpr (B16) {
+            if (vecx == 2) LAUNCH_WG(2, true);
+            else if (vecx == 1) LAUNCH_WG(1, true);
+            else LAUNCH_WG(0, true);
+        } else {
+            if (vecx && vy) LAUNCH_WG(1, true);
+            else if (vecx) LAUNCH_WG(1, false);
+            else if (vy) LAUNCH_WG(0, true);
+            else LAUNCH_WG(0, false);
         }
-    }
-#define LAUNCH_WG_C(VX_, VY_, H3_, CIS_)                                                                                          \
-    hipLaunchKernelGGL((conv3_wgrad_kernel<P, VX_, VY_, H3_, CIS_, (CIS_ == 1)>), dim3((unsigned)G, nci, nco), dim3(256), 0, st, x, ldx, dy, lddy, \
-                       ws, dy3, lddy3, ws3, D, H, W, Cin, Cout, ntx, nty, ntz, (int)ntiles)
-#define LAUNCH_WG_2(H3_)                                                                                                          \
-    hipLaunchKernelGGL((conv3_wgrad_kernel<P, 2, true, H3_, 1, true, 2>), dim3((unsigned)G, nci, nco), dim3(256), 0, st, x, ldx, dy, lddy, \
-                       ws, dy3, lddy3, ws3, D, H, W, Cin, Cout, ntx, nty, ntz, (int)ntiles)
-#define LAUNCH_WG(VX_, VY_)                                                                                                        \
-    do {                                                                                                                           \
-        if (dy3) { if (cis == 1) LAUNCH_WG_C(VX_, VY_, true, 1); else LAUNCH_WG_C(VX_, VY_, true, 2); }                            \
-        else { if (cis == 1) LAUNCH_WG_C(VX_, VY_, false, 1); else LAUNCH_WG_C(VX_, VY_, false, 2); }                              \
-    } while (0)
-    if constexpr (B16) {
-        if (vecx == 2 && nsl == 2) { if (dy3) LAUNCH_WG_2(true); else LAUNCH_WG_2(false); }
-        else if (vecx == 2) LAUNCH_WG(2, true);
-        else if (vecx == 1) LAUNCH_WG(1, true);
-        else LAUNCH_WG(0, true);
-    } else {
-        if (vecx && vy) LAUNCH_WG(1, true);
-        else if (vecx) LAUNCH_WG(1, false);
-        else if (vy) LAUNCH_WG(0, true);
-        else LAUNCH_WG(0, false);
-    }
-    const int blocks = (int)std::min<long>((n + 31) / 32, 16384);
-    const int blocks3 = dy3 ? (int)std::min<long>((n3 + 31) / 32, 16384) : 0;
-    if (!parts_only)
-        hipLaunchKernelGGL(conv3_wgrad_reduce_kernel, dim3(blocks + blocks3), dim3(256), 0, st, ws, (int)G, n, dw, blocks,
-                           (const float*)ws3, n3, dw3);
-    return unetr_check_launch();
+        return UNETR_OK;
+    });
 }
 
 }  // namespace
@@ -2609,7 +2497,7 @@ extern "C" int unetr_conv3_pack_grouped(const unetr_pack_problem* probs, int n, 
                 continue;
             }
             const int K = (q.kind == 0 || q.kind == 2) ? q.Cin : q.Cout, N = (q.kind == 0 || q.kind == 2) ? q.Cout : q.Cin;
-            const int pair = (prec == UNETR_PREC_BF16 && q.kind != 3 && K <= 16 && conv_pipe_enabled()) ? 1 : 0;
+            const int pair = (prec == UNETR_PREC_BF16 && q.kind != 3 && K <= 16) ? 1 : 0;
             long total;
             if (q.kind <= 1) total = pair ? 14L * N * 32 : 27L * ((K + SL - 1) / SL) * N * SL;
             else total = pair ? (long)N * 32 : (long)((K + SL - 1) / SL) * N * SL;
@@ -2628,7 +2516,7 @@ extern "C" int unetr_conv3_pack_grouped(const unetr_pack_problem* probs, int n, 
 static int pack_1x1(const float* w3, void* w3pack, int K, int N, int prec, int allow_pair, int transposed, hipStream_t st) {
     // rows n < N, contraction index k < K
     if (prec == UNETR_PREC_BF16) {
-        const int pair = (allow_pair && use_pair<PrecBF16>(K) && conv_pipe_enabled()) ? 1 : 0;
+        const int pair = (allow_pair && use_pair<PrecBF16>(K)) ? 1 : 0;
         hipLaunchKernelGGL((conv3_pack_1x1_kernel<uint16_t>), dim3(cdiv((long)((K + 31) / 32) * N * 32, 256)), dim3(256), 0, st, w3,
                            (uint16_t*)w3pack, K, N, pair, 32, transposed);
     } else if (prec == UNETR_PREC_BF16X3) {

@@ -361,7 +361,7 @@ int launch_bf16(int M, int N, int K, const typename std::conditional<X3 != 0, fl
     int splits = 1;
     // few tiles (batch-2 token counts): the kernel is latency-bound, one workgroup's time is ~ its K steps, so long K
     // ranges are cut into slabs of >= 12 steps (shorter slabs cost more in the reduce launch than they save)
-    const int min_steps = (X3 != 0 && getenv("UNETR_X3_SPLIT_K768") == nullptr) ? 48 : 24;       // (X3: 32-element stages; K = 768 stays whole as in bf16 mode)
+    const int min_steps = X3 != 0 ? 48 : 24;       // (X3: 32-element stages; K = 768 stays whole as in bf16 mode)
     if (tiles < 192 && ksteps >= min_steps) splits = std::min(ksteps / (min_steps / 2), (int)((512 + tiles - 1) / tiles));
     if (const char* e = getenv("UNETR_GEMM_SPLITS")) { int v = atoi(e); if (v > 0) splits = std::min(v, ksteps); }
     while (splits > 1 && (size_t)splits * M * N * sizeof(float) > ws_bytes) --splits;
@@ -944,11 +944,10 @@ static int gemm_bf16_impl(const unetr_gemm_bf16_desc* d, const void* A, const vo
             d->pre, d->aux, d->ldaux, d->act, d->accumulate, d->alpha, d->tc_d, d->tc_h, d->tc_w, d->tc_cout > 0 ? d->tc_cout : 0};
     const uint16_t* a = (const uint16_t*)A;
     const uint16_t* b = (const uint16_t*)B;
-    const int env_cfg = getenv("UNETR_GEMM_CFG") ? atoi(getenv("UNETR_GEMM_CFG")) : 0;   // tuning hooks
-    const int env_ns = getenv("UNETR_GEMM_STAGES") ? atoi(getenv("UNETR_GEMM_STAGES")) : 0;
+    const int env_cfg = getenv("UNETR_GEMM_CFG") ? atoi(getenv("UNETR_GEMM_CFG")) : 0;   // tuning hook
     // (short reductions with few 128 x 128 tiles -- the GEMM-form transposed convs at 12^3 x 2 = 3456 voxels: [3456 x 128 x 512] is 27
     // tiles, [3456 x 512 x 64 / 128] 108 -- take the small-M tiles: 20-24 us per launch on 27-108 workgroups with the 128 x 128 family)
-    const bool few128 = K <= 512 && (long)cdiv(M, 128) * cdiv(N, 128) < 128 && !getenv("UNETR_GEMM_FEW128_OFF");
+    const bool few128 = K <= 512 && (long)cdiv(M, 128) * cdiv(N, 128) < 128;
     const bool big = env_cfg == 128 || (env_cfg == 0 && M >= 1024 && N >= 128 && !few128);
     // the 256 x 256 ping-pong kernel: many rows, weights as stored ([N, K]); K tiles of 64 (checked above).  Narrow outputs
     // (N = 768 at 6912 rows: 81 tiles for 256 CUs) keep the 128 x 128 tile, which fills the chip
@@ -985,22 +984,16 @@ static int gemm_bf16_impl(const unetr_gemm_bf16_desc* d, const void* A, const vo
         }
     }
     if (!d->b_kn) {
-        if (big) { if (env_ns == 3) BF16_GO(4, 4, false, 3); if (env_ns == 4) BF16_GO(4, 4, false, 4); BF16_GO(4, 4, false, 2); }
-        if (cfg == 6432) { if (env_ns == 6) BF16_GO(2, 1, false, 6); if (env_ns == 8) BF16_GO(2, 1, false, 8); if (env_ns == 12) BF16_GO(2, 1, false, 12); BF16_GO(2, 1, false, 4); }
-        if (cfg == 3264) { if (env_ns == 6) BF16_GO(1, 2, false, 6); if (env_ns == 8) BF16_GO(1, 2, false, 8); BF16_GO(1, 2, false, 4); }
+        if (big) BF16_GO(4, 4, false, 2);
+        if (cfg == 6432) BF16_GO(2, 1, false, 4);
+        if (cfg == 3264) BF16_GO(1, 2, false, 4);
         if (cfg == 64128) BF16_GO(2, 4, false, 3);
         if (cfg == 6496) BF16_GO(2, 3, false, 3);
-        if (env_ns == 2) BF16_GO(2, 2, false, 2);
-        if (env_ns == 6) BF16_GO(2, 2, false, 6);
-        if (env_ns == 8) BF16_GO(2, 2, false, 8);
         BF16_GO(2, 2, false, 4);
     }
-    if (big) { if (env_ns == 3) BF16_GO(4, 4, true, 3); if (env_ns == 4) BF16_GO(4, 4, true, 4); BF16_GO(4, 4, true, 2); }
-    if (cfg == 3264) { if (env_ns == 6) BF16_GO(1, 2, true, 6); if (env_ns == 8) BF16_GO(1, 2, true, 8); if (env_ns == 12) BF16_GO(1, 2, true, 12); BF16_GO(1, 2, true, 4); }
+    if (big) BF16_GO(4, 4, true, 2);
+    if (cfg == 3264) BF16_GO(1, 2, true, 4);
     if (cfg == 64128) BF16_GO(2, 4, true, 3);
-    if (env_ns == 2) BF16_GO(2, 2, true, 2);
-    if (env_ns == 6) BF16_GO(2, 2, true, 6);
-    if (env_ns == 8) BF16_GO(2, 2, true, 8);
     BF16_GO(2, 2, true, 4);
 #undef BF16_GO
 }

@@ -2022,13 +2022,10 @@ extern "C" int unetr_instnorm_apply_fin(const void* x, long ldx, const float* pa
     long vpb; int nchunk;
     hipStream_t st = (hipStream_t)stream;
     if (x2) {
-        int u = 2;                           // voxels in flight per thread (2 / 3 / 4 measured inside the step: 63.7 / 66.4 / 63.4 us per step)
-        if (const char* e = getenv("UNETR_IN_U_FWD2")) { const int v = atoi(e); if (v >= 2 && v <= 4) u = v; }
-        in_chunks(V, B, u * (IN_FIN_NT / cvn), IN_FIN_BLOCKS, vpb, nchunk);
-#define FWD2(U_) ACT_DISPATCH(act16, hipLaunchKernelGGL((in_apply_fin_kernel<AT, true, U_>), dim3(nchunk, B), dim3(IN_FIN_NT), 0, st, (const AT*)x, ldx, part_a, rows_a, \
-                                                       (const AT*)x2, ldx2, part_b, rows_b, stats_a, stats_b, eps, (AT*)y, ldy, V, vpb, C, lrelu))
-        if (u == 2) FWD2(2); else if (u == 3) FWD2(3); else FWD2(4);
-#undef FWD2
+        // 2 voxels in flight per thread (2 / 3 / 4 measured inside the step: 63.7 / 66.4 / 63.4 us per step)
+        in_chunks(V, B, 2 * (IN_FIN_NT / cvn), IN_FIN_BLOCKS, vpb, nchunk);
+        ACT_DISPATCH(act16, hipLaunchKernelGGL((in_apply_fin_kernel<AT, true, 2>), dim3(nchunk, B), dim3(IN_FIN_NT), 0, st, (const AT*)x, ldx, part_a, rows_a,
+                                               (const AT*)x2, ldx2, part_b, rows_b, stats_a, stats_b, eps, (AT*)y, ldy, V, vpb, C, lrelu));
     } else {
         in_chunks(V, B, 4 * (IN_FIN_NT / cvn), IN_FIN_BLOCKS, vpb, nchunk);
         ACT_DISPATCH(act16, hipLaunchKernelGGL((in_apply_fin_kernel<AT, false, 4>), dim3(nchunk, B), dim3(IN_FIN_NT), 0, st, (const AT*)x, ldx, part_a, rows_a,
@@ -2123,10 +2120,7 @@ extern "C" int unetr_instnorm_bwd(const void* dy, long lddy, const void* x, long
     // about three blocks per CU, each at least two full iterations of its threads (a fixed 1024-voxel block left the 12^3 x
     // 128-channel layer on TWO blocks: 51 us for 0.9 MB); offsets inside a block are 32-bit
     const int cvn = C / W, nphase = 256 / cvn;
-    int UD = 2;                                  // voxels in flight per thread: dual / single form
-    const int US = 4;
-    if (const char* e = getenv("UNETR_IN_U_RED2")) { const int v = atoi(e); if (v >= 2 && v <= 4) UD = v; }
-    const long step = (long)(x2 ? UD : US) * nphase;
+    const long step = (long)(x2 ? 2 : 4) * nphase;      // voxels in flight per thread: dual / single form
     long vpb = std::max<long>(2 * step, cdiv(cdiv((long)V * B, 768L), step) * step);
     const long ldmax = std::max(std::max(lddy, ldx), x2 ? ldx2 : 0L);
     while (vpb > 2 * step && (vpb + 256) * ldmax * 4 >= (1L << 31)) vpb -= step;
@@ -2139,7 +2133,7 @@ extern "C" int unetr_instnorm_bwd(const void* dy, long lddy, const void* x, long
     const size_t lds_bytes = (size_t)3 * nphase * C * 4;
 #define IN_RED(DUAL_, U_) ACT_DISPATCH(act16, hipLaunchKernelGGL((in_bwd_reduce_kernel<AT, DUAL_, U_>), dim3(nchunk, B), dim3(256), lds_bytes, st, (const AT*)dy, lddy, \
                                                                  (const AT*)x, ldx, sa, (const AT*)x2, ldx2, sb, V, vpb, C, lrelu, ws))
-    if (x2) { if (UD == 2) IN_RED(true, 2); else if (UD == 3) IN_RED(true, 3); else IN_RED(true, 4); } else IN_RED(false, 4);
+    if (x2) IN_RED(true, 2); else IN_RED(false, 4);
 #undef IN_RED
     // the finalize of the partial sums rides in the prologue of the apply kernel where that form exists (UNETR_IN_FIN=0: the
     // separate finalize launch, kept for A/B measurements and as the route for shapes the folded form declines)

@@ -376,11 +376,6 @@ tconv2_dgrad_kernel(const typename Elem<P>::type* __restrict__ dy, long lddy, co
     }
 }
 
-inline bool tconv2_enabled() {
-    const char* e = getenv("UNETR_AMD_TCONV2");      // tuning hook: 0 = generic GEMM family only
-    return !e || atoi(e) != 0;
-}
-
 template <class P, int RT, int CTW>
 void launch_wgrad(int G, int NG, const typename Elem<P>::type* x, long ldx, const typename Elem<P>::type* dy, long lddy, float* ws, int M, int D, int H, int W,
                   int Cin, int Cout, int ntiles, hipStream_t st) {
@@ -455,11 +450,11 @@ int dgrad2(const typename Elem<P>::type* dy, long lddy, const float* w, typename
 // eligibility: volume large enough for the persistent walk to pay, channels in the range the register / LDS budgets were
 // sized for, 16-byte aligned rows.  Anything else stays on the generic GEMM family (same results).
 extern "C" int unetr_tconv2_wgrad_supported(long M, int Cin, int Cout, long ldx, long lddy) {
-    return tconv2_enabled() && M >= 2048 && M < (1L << 27) && Cin % 16 == 0 && Cin >= 16 && Cin <= 64 && Cout % 8 == 0 && Cout >= 8 &&
+    return M >= 2048 && M < (1L << 27) && Cin % 16 == 0 && Cin >= 16 && Cin <= 64 && Cout % 8 == 0 && Cout >= 8 &&
            Cout <= 64 && ldx % 4 == 0 && lddy % 4 == 0;
 }
 extern "C" int unetr_tconv2_fwd_supported(long M, int Cin, int Cout, long ldx, long ldy) {
-    return tconv2_enabled() && M >= 2048 && M < (1L << 27) && Cin % 8 == 0 && Cin >= 8 && Cin <= 64 && (Cout == 8 || Cout == 16 || Cout == 32) &&
+    return M >= 2048 && M < (1L << 27) && Cin % 8 == 0 && Cin >= 8 && Cin <= 64 && (Cout == 8 || Cout == 16 || Cout == 32) &&
            ldx % 4 == 0 && ldy % 4 == 0;
 }
 
@@ -520,7 +515,7 @@ extern "C" int unetr_tconv2_dgrad(const void* dy, long lddy, const float* w, voi
                                   int B, int D, int H, int W, int Cin, int Cout, int prec, float* ws, size_t ws_bytes, void* stream) {
     if (!dy || !w || !dx) return UNETR_ERR_ARG;
     const long M = (long)B * D * H * W;
-    if (accumulate || !tconv2_enabled() || M < 2048 || M >= (1L << 27) || Cin < 8 || Cin > 64 || Cout % 8 || Cout < 8 || Cout > 32 ||
+    if (accumulate || M < 2048 || M >= (1L << 27) || Cin < 8 || Cin > 64 || Cout % 8 || Cout < 8 || Cout > 32 ||
         (lddy & 3) || ((uintptr_t)dy & 15) || (Cin & 3) || (ldx & 3) || ((uintptr_t)dx & (prec == UNETR_PREC_BF16 ? 7 : 15)))
         return UNETR_ERR_UNSUPPORTED;
     if (prec == UNETR_PREC_BF16) {

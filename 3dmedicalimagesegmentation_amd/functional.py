@@ -195,11 +195,6 @@ def colsum_or_defer(x, M, N, ld, b, view_shape=None):
     return _ret(b, out, deferred=True)
 
 
-def reduce_defer_enabled():
-    """UNETR_AMD_REDUCE_DEFER=0 (A/B hook): every conv weight-gradient kernel launches its own partial-sum reduction again"""
-    return os.environ.get("UNETR_AMD_REDUCE_DEFER", "1") != "0"
-
-
 def _launch_reduces(rq):
     """every queued weight-gradient reduction (dst[i] = sum over rows of part[row][i]) in ONE launch"""
     arr = (_capi.ReduceProblem * len(rq))()
@@ -233,7 +228,7 @@ def _launch_deferred(wq, cq, wbq=(), prec=0, fuse=None):
             arr[i].dy, arr[i].x, arr[i].dw = dyb.data_ptr(), xb.data_ptr(), out.data_ptr()
             arr[i].M, arr[i].N, arr[i].K = dyb.shape[0], dyb.shape[1], xb.shape[1]
         call("unetr_gemm_bf16_grouped_wgrad", arr, len(wbq), _stream())
-    if wq and prec == _capi.PREC_BF16X3 and os.environ.get("UNETR_AMD_X3_WGRAD_STACK", "1") != "0":
+    if wq and prec == _capi.PREC_BF16X3:
         # bf16x3: dW = dY^T X over (hi, lo) halves is the bf16 kernel's contraction over three times the rows of the stacks
         # [dYh; dYh; dYl] / [Xh; Xl; Xh] (two streaming split launches per problem) -- the generic fp32-storage grouped kernel spends
         # 2.2 ms per step on these 76 GF, the bf16 kernel 0.2 ms per 432 rows; with an optimizer epilogue armed it rides here too
@@ -394,32 +389,6 @@ def gemm_bf16(A, B, M, N, K, *, b_kn=False, C=None, Cb=None, lda=None, ldb=None,
          Cb.data_ptr() if Cb is not None else None, ws.data_ptr(), ws.numel() * 4, _stream())
 
 
-def ln_gemm_bf16(x, gamma, beta, Wb, *, bias=None, act=0, C=None, Cb=None, pre=None, xn=None, mean=None, rstd=None):
-    """C / Cb [M,N] = act(LayerNorm(x)[M,K] @ Wb[N,K]^T + bias) in one launch (csrc/encoder.hip); optionally keeps the
-    normalised rows `xn` (bf16), `mean`, `rstd` and the pre-activation `pre` for backward"""
-    M, K = x.shape
-    N = Wb.shape[0]
-    d = _capi.LnGemmDesc()
-    d.x, d.ldx, d.gamma, d.beta, d.eps = x.data_ptr(), K, gamma.data_ptr(), beta.data_ptr(), LN_EPS
-    d.W, d.ldw, d.bias, d.act = Wb.data_ptr(), K, _p(bias), act
-    d.pre, d.ldpre, d.Cb, d.ldcb, d.C, d.ldc = _p(pre), N, _p(Cb), N, _p(C), N
-    d.xn, d.mean, d.rstd = _p(xn), _p(mean), _p(rstd)
-    d.M, d.N, d.K = M, N, K
-    call("unetr_ln_gemm_bf16", ctypes.byref(d), _stream())
-
-
-def fused_ln_enabled():
-    """LayerNorm as the prologue of the consuming GEMM (unetr_ln_gemm_bf16).  Off by default: measured on MI355X at 432
-    rows it LOSES to LayerNorm kernel + bf16 GEMM (13.3 vs 3.1 + 6.6 us for qkv, 17.5 vs 3.1 + 10.5 us for linear1): a CU
-    pulls ~70 GB/s from L2, and the fused tile reads its 64 fp32 rows (2x the bytes of the bf16 rows the GEMM alone reads)
-    once per column tile -- 36 times per row tile."""
-    return os.environ.get("UNETR_AMD_FUSED_LN", "0") == "1"
-
-
-def bf16_attention_enabled():
-    return os.environ.get("UNETR_AMD_BF16_ATTENTION", "1") != "0"
-
-
 # ---- bf16 operand storage (bf16 precision mode) ---------------------------------------------------------------
 # The encoder's Linear layers read bf16-STORED operands through unetr_gemm_bf16: activations are emitted as bf16 by
 # the producing kernels (LayerNorm, attention, GELU epilogue), weights come from a bf16 shadow.  A shadow is fresh when
@@ -445,10 +414,6 @@ def mark_flat_maintained(params, state=None):
             ent[1], ent[3] = w._version, True
     if state is not None:
         state.unmaintained = 0
-
-
-def bf16_storage_enabled():
-    return os.environ.get("UNETR_AMD_BF16_STORAGE", "1") != "0"
 
 
 def invalidate_weight_shadows():
@@ -627,7 +592,7 @@ def shadow_ptr_for_update(w):
 
 
 def _bf16_path(prec, *kdims):
-    return prec == _capi.PREC_BF16 and bf16_storage_enabled() and all(k % 64 == 0 for k in kdims)
+    return prec == _capi.PREC_BF16 and all(k % 64 == 0 for k in kdims)
 
 
 def _twin(t):
@@ -895,20 +860,13 @@ def attention_bf16_bwd(qkvb, outb, doutb, lse, B, L, heads, dh, dqkv=None):
     return dqkvb
 
 
-def _use_gemm_conv():
-    """UNETR_AMD_CONV=gemm routes 3x3x3 convs through the generic im2col-loader GEMM family instead of the
-    dedicated LDS-halo kernels (kept for cross-checking one HIP path against the other)."""
-    import os
-    return os.environ.get("UNETR_AMD_CONV", "halo") == "gemm"
-
-
 def conv3(x, ldx, w, dims, prec, mode=0, out=None, ldo=None, accumulate=False):
     """3x3x3 conv (mode 0: w[Cout,Cin,3,3,3] applied to x with Cin channels) or its data gradient
     (mode 1: x carries Cout channels, result has Cin channels)."""
     B, D, H, W = dims
     cout_w, cin_w = w.shape[0], w.shape[1]
     cin, cout = (cin_w, cout_w) if mode == 0 else (cout_w, cin_w)
-    if _use_gemm_conv() or cout % 16 != 0:
+    if cout % 16 != 0:
         return conv_fwd(x, ldx, conv_pack(w, mode), dims, cin, cout, 3, prec, out=out, ldo=ldo, accumulate=accumulate)
     wp = conv_pack_get(w, mode, prec)
     if out is None:
@@ -924,8 +882,7 @@ def conv3_fused(x, ldx, w, w3, dims, prec):
     (c, stats, c3, stats3) or None when the shape has to take the unfused kernels."""
     B, D, H, W = dims
     cout, cin = w.shape[0], w.shape[1]
-    level = int(os.environ.get("UNETR_AMD_CONV_FUSE", "2"))     # tuning hook: 0 unfused, 1 statistics only, 2 + 1x1x1 conv
-    if _use_gemm_conv() or cout % 16 != 0 or level == 0 or (w3 is not None and level < 2):
+    if cout % 16 != 0:
         return None
     dev = x.device
     wp = conv_pack_get(w, 0, prec)
@@ -956,18 +913,13 @@ def in_fuse_level():
     return int(os.environ.get("UNETR_AMD_IN_FUSE", "3"))
 
 
-def img_branch_enabled():
-    """UNETR_AMD_IMG_BRANCH=0 (A/B hook): the residual block on the image stores and re-reads its 1x1x1 branch like every other block"""
-    return os.environ.get("UNETR_AMD_IMG_BRANCH", "1") != "0"
-
-
 def conv3_parts(x, ldx, w, w3, dims, prec, store3=True):
     """conv3_fused without the statistics finalize: returns (c, part, c3, part3, rows) -- part* = InstanceNorm partial rows
     [B, rows, 2, Cout] that instnorm_apply_fin reduces in its prologue -- or None when the shape takes another route.
     store3=False: the 1x1x1 branch is not stored (c3 is None), only its statistics rows are formed."""
     B, D, H, W = dims
     cout, cin = w.shape[0], w.shape[1]
-    if _use_gemm_conv() or cout % 16 != 0 or cout > 128 or int(os.environ.get("UNETR_AMD_CONV_FUSE", "2")) < 2:
+    if cout % 16 != 0 or cout > 128:
         return None
     dev = x.device
     wp = conv_pack_get(w, 0, prec)
@@ -1032,7 +984,7 @@ def conv3_dgrad_stats(dy, w, xn, stats, dims, prec):
     lrelu'd output the conv read): returns (da, part, rows) or None when the shape takes the unfused route"""
     B, D, H, W = dims
     cout, cin = w.shape[0], w.shape[1]
-    if _use_gemm_conv() or cin % 16 != 0 or cin > 128 or xn.stride(-2) != cin:
+    if cin % 16 != 0 or cin > 128 or xn.stride(-2) != cin:
         return None
     wp = conv_pack_get(w, 1, prec)
     da = torch.empty(B, D, H, W, cin, dtype=act_dtype(prec), device=dy.device)
@@ -1104,7 +1056,7 @@ def conv3_dgrad_fused(dc1, dc3, w1, w3, dx, dims, prec):
     returns False when the shape has to take the two-kernel route."""
     B, D, H, W = dims
     cout, cin = w1.shape[0], w1.shape[1]
-    if _use_gemm_conv() or cin % 16 != 0 or int(os.environ.get("UNETR_AMD_CONV_FUSE", "2")) < 2:
+    if cin % 16 != 0:
         return False
     wp = conv_pack_get(w1, 1, prec)
     w3t = conv_pack_get(w3, 3, prec)
@@ -1119,17 +1071,10 @@ def conv3_wgrad(x, ldx, dy, lddy, dims, cin, cout, prec, out=None, dy3=None, out
     defer = the ArenaState owning `out` (and `out3`): returns (dw, True) when the reduction of the partial sums was queued for the
     end-of-backward grouped launch; plain calls return dw."""
     want = defer is not None                 # such callers get (dw, queued)
-    if _use_gemm_conv():
-        if dy3 is not None:
-            x32 = x if x.dtype == torch.float32 else x.float().contiguous()
-            gemm(dy3.float() if dy3.dtype != torch.float32 else dy3, x32, out3, cout, cin, dims[0] * dims[1] * dims[2] * dims[3], lda=cout,
-                 ldb=x32.stride(-2), ldc=cin, prec=_capi.PREC_F32, a_trans=True, b_trans=True)
-        r = conv_wgrad(x, ldx, dy, lddy, dims, cin, cout, 3, prec, out=out)
-        return (r, False) if want else r
     B, D, H, W = dims
     dw = out if out is not None else torch.empty(cout, cin, 3, 3, 3, dtype=torch.float32, device=x.device)
     x_f32 = int(prec == _capi.PREC_BF16 and x.dtype == torch.float32)
-    if defer is not None and reduce_defer_enabled():
+    if defer is not None:
         # arena mode: the kernel leaves its per-workgroup partial sums in a buffer of its own and the reduction joins the ONE grouped
         # reduce launch at the end of the backward pass (functional.flush_deferred)
         rows = _capi.load().unetr_conv3_wgrad_rows(B, D, H, W, cin, cout, prec, x_f32, int(dy3 is not None))
@@ -1230,8 +1175,7 @@ def instnorm_bwd(dy, lddy, x, sa, B, V, C, lrelu, x2=None, sb=None):
 def _tconv_as_gemm(prec, M, cin, cout, ld_in):
     """the small transposed convs (768 channels at 6^3, 64 / 128 at 12^3) go through the bf16-storage GEMM: few voxels, many
     channels -- exactly where the dedicated voxel-tile kernels decline and the gather-loader GEMM family was 3-6x slower"""
-    return (prec == _capi.PREC_BF16 and bf16_storage_enabled() and os.environ.get("UNETR_AMD_TCONV_GEMM", "1") != "0"
-            and cin % 64 == 0 and M % 8 == 0 and ld_in == cin and M < 8192)
+    return (prec == _capi.PREC_BF16 and cin % 64 == 0 and M % 8 == 0 and ld_in == cin and M < 8192)
 
 
 def tconv_fwd(x, ldx, w, dims, cin, cout, prec, out=None, ldo=None):
@@ -1243,7 +1187,7 @@ def tconv_fwd(x, ldx, w, dims, cin, cout, prec, out=None, ldo=None):
     M = B * D * H * W
     if _tconv_as_gemm(prec, M, cin, cout, ldx):
         xb = _twin(x).view(M, cin)             # (a bf16 feature map is its own operand; tokens bring their bf16 twin)
-        if out.dtype == torch.bfloat16 and cout % 4 == 0 and ldo % 4 == 0 and os.environ.get("UNETR_AMD_TCONV_SCATTER", "1") != "0":
+        if out.dtype == torch.bfloat16 and cout % 4 == 0 and ldo % 4 == 0:
             # tap-major weight pack [Cin][tap][Cout] (re-packed with the conv weights after every update): the GEMM's epilogue
             # writes each (voxel, tap) row of Cout channels straight to its output voxel -- no fp32 [M, 8 Cout] intermediate, no
             # pixel-shuffle launch
@@ -1300,7 +1244,7 @@ def tconv_bwd(x, ldx, xb, dy, lddy, w, dims, cin, cout, prec, need_dx):
     dx = tconv_dgrad(dy, lddy, w, dims, cin, cout, prec) if need_dx else None
     gw = _gout(w)
     st = _GRAD_SINK.get(w.data_ptr()) if gw is not None else None
-    if st is not None and reduce_defer_enabled():
+    if st is not None:
         # arena mode: the partial sums of the weight gradient stay in a buffer of their own; their reduction joins the grouped launch
         # at the end of the backward pass
         rows = _capi.load().unetr_tconv2_wgrad_rows(B, D, H, W, cin, cout)
@@ -1401,23 +1345,16 @@ def _tblock_forward(x, n1w, n1b, wqkv, wp, bp, n2w, n2b, w1, b1, w2, b2, B, L, h
         # bf16-stored operands: every GEMM input below is written as bf16 by its producer (fp32 copies stay for
         # the weight-gradient GEMMs and the LayerNorm / attention backward kernels)
         f32 = dict(dtype=torch.float32, device=x.device)
-        fused = fused_ln_enabled() and hid <= 1024      # LayerNorm as the prologue of the GEMM that consumes it
         y1 = y2 = a = x.new_empty(0)         # the fp32 twins are not materialised: every consumer reads bf16
-        b16att = bf16_attention_enabled() and dh == 64   # q/k/v stay bf16 from the GEMM epilogue to the attention kernels' LDS-DMA
+        b16att = dh == 64   # q/k/v stay bf16 from the GEMM epilogue to the attention kernels' LDS-DMA
         qkv = torch.empty(M, 3 * hid, dtype=torch.bfloat16 if b16att else torch.float32, device=x.device)
-        if fused:
-            y1b = bf16_like(x) if train else None
-            m1 = torch.empty(M, **f32) if train else None
-            r1 = torch.empty(M, **f32) if train else None
-            ln_gemm_bf16(x, n1w, n1b, weight_bf16(wqkv), C=None if b16att else qkv, Cb=qkv if b16att else None, xn=y1b, mean=m1, rstd=r1)
+        pre = _stashed_ln(x, n1w, n1b)       # norm1(x) may have been formed by the kernel that produced x
+        if pre is not None:
+            y1b, m1, r1 = pre
         else:
-            pre = _stashed_ln(x, n1w, n1b)       # norm1(x) may have been formed by the kernel that produced x
-            if pre is not None:
-                y1b, m1, r1 = pre
-            else:
-                y1b = bf16_like(x)
-                _, m1, r1 = layernorm_fwd(x, n1w, n1b, bf16_out=y1b, want_fp32=False)
-            gemm_bf16(y1b, weight_bf16(wqkv), M, 3 * hid, hid, C=None if b16att else qkv, Cb=qkv if b16att else None)
+            y1b = bf16_like(x)
+            _, m1, r1 = layernorm_fwd(x, n1w, n1b, bf16_out=y1b, want_fp32=False)
+        gemm_bf16(y1b, weight_bf16(wqkv), M, 3 * hid, hid, C=None if b16att else qkv, Cb=qkv if b16att else None)
         attb = bf16_like(x)
         if b16att:
             att = x.new_empty(0)
@@ -1428,19 +1365,13 @@ def _tblock_forward(x, n1w, n1b, wqkv, wp, bp, n2w, n2b, w1, b1, w2, b2, B, L, h
         gemm_bf16(attb, weight_bf16(wp), M, hid, hid, C=x1, bias=bp, res=x, ldr=hid)
         u = torch.empty(M, mlp, **f32) if train else None      # pre-activation, only GELU' in backward reads it
         ab = torch.empty(M, mlp, dtype=torch.bfloat16, device=x.device)
-        if fused:
-            y2b = bf16_like(x) if train else None
-            m2 = torch.empty(M, **f32) if train else None
-            r2 = torch.empty(M, **f32) if train else None
-            ln_gemm_bf16(x1, n2w, n2b, weight_bf16(w1), bias=b1, act=1, Cb=ab, pre=u, xn=y2b, mean=m2, rstd=r2)
-        else:
-            y2b = bf16_like(x)
-            _, m2, r2 = layernorm_fwd(x1, n2w, n2b, bf16_out=y2b, want_fp32=False)
-            gemm_bf16(y2b, weight_bf16(w1), M, mlp, hid, Cb=ab, bias=b1, act=1, pre=u)
+        y2b = bf16_like(x)
+        _, m2, r2 = layernorm_fwd(x1, n2w, n2b, bf16_out=y2b, want_fp32=False)
+        gemm_bf16(y2b, weight_bf16(w1), M, mlp, hid, Cb=ab, bias=b1, act=1, pre=u)
         if not train:
             u = m1 = r1 = m2 = r2 = y1b = y2b = x.new_empty(0)
         x2 = torch.empty(M, hid, **f32)
-        if next_ln is not None and not fused and not emit_twin:      # (a tapped block writes the bf16 twin of x2 from its own epilogue)
+        if next_ln is not None and not emit_twin:      # (a tapped block writes the bf16 twin of x2 from its own epilogue)
             xn = bf16_like(x)
             mn, rn = gemm_bf16_ln_fwd(ab, weight_bf16(w2), M, hid, mlp, x2, next_ln[0], next_ln[1], xn, bias=b2, res=x1, ldr=hid)
             _stash_ln(x2, next_ln[0], next_ln[1], xn, mn, rn)
@@ -1676,7 +1607,7 @@ def _resblock_fwd_fin(x, ldx, dims, cout, w1, w2, w3, prec, to_cat, head=None):
     cin = w1.shape[1]
     # the block on the image (<= 4 fp32 input channels, no input gradient): its 1x1x1 branch is never stored -- the block-end
     # kernels form it from the image (csrc/norm_misc.hip: ImgBranch)
-    img = (img_branch_enabled() and x.dtype == torch.float32 and cin <= 4 and ldx == cin and not x.requires_grad and w3.is_contiguous()
+    img = (x.dtype == torch.float32 and cin <= 4 and ldx == cin and not x.requires_grad and w3.is_contiguous()
            and cout % 8 == 0 and 64 % max(1, cout // 8) == 0)
     f1 = conv3_parts(x, ldx, w1, w3, dims, prec, store3=not img)
     if f1 is None and img:
@@ -1770,7 +1701,7 @@ def _resblock_bwd(dout, x, ldx, dims, cin, cout, w1, w2, w3, saved, prec, need_d
         dw1 = conv3_wgrad(x, ldx, dc1, cout, dims, cin, cout, prec, out=g1, dy3=dc3, out3=o3)
     if img3 is not None:
         rq = [(img3[1], dw3, cout * cin, img3[2])]
-        if st is not None and q1 and reduce_defer_enabled():
+        if st is not None and q1:
             st.defer["reduce"].append(rq[0])           # joins the grouped reduce at the end of the backward pass (armed by conv3_wgrad)
         else:
             _launch_reduces(rq)

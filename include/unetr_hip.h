@@ -35,7 +35,7 @@ extern "C" {
 /* Bumped whenever an exported signature or a descriptor struct changes.  A binding (3dmedicalimagesegmentation_amd/_capi.py, or a
  * C caller) must compare unetr_abi_version() with the UNETR_ABI_VERSION it was written against before its first call: a stale
  * .so would otherwise shift arguments silently (a stream pointer in an int slot). */
-#define UNETR_ABI_VERSION 20
+#define UNETR_ABI_VERSION 21
 int unetr_abi_version(void);
 
 /* ---- generic MFMA GEMM: C[M,N] = epilogue(A[M,K] * B[K,N]) ------------------------------------------
@@ -161,32 +161,13 @@ int unetr_tconv2_wgrad_supported(long M, int Cin, int Cout, long ldx, long lddy)
 
 
 /* ---- the same attention core on bf16-STORED q/k/v (bf16 mode, head dim 64): qkv bf16 [B*L, 3*heads*64] as written by
- * unetr_ln_gemm_bf16, out fp32 and/or bf16 [B*L, heads*64] (either may be NULL), lse [B, heads, L].  Backward: out_bf16 /
+ * unetr_gemm_bf16, out fp32 and/or bf16 [B*L, heads*64] (either may be NULL), lse [B, heads, L].  Backward: out_bf16 /
  * dout_bf16 bf16 [B*L, heads*64], writes dqkv_bf16 (required) and dqkv fp32 (optional), delta [B, heads, L] scratch.
  * Returns "unsupported" (3) for other head dims -- the caller then uses unetr_attention_fwd / _bwd on fp32 q/k/v. */
 int unetr_attention_bf16_fwd(const void* qkv, float* out, void* out_bf16, float* lse, int B, int L, int heads, int dh,
                              float scale, void* stream);
 int unetr_attention_bf16_bwd(const void* qkv, const void* out_bf16, const void* dout_bf16, const float* lse, float* dqkv,
                              void* dqkv_bf16, float* delta, int B, int L, int heads, int dh, float scale, void* stream);
-
-/* ---- LayerNorm fused into the GEMM that consumes it (bf16 mode, small token counts): y = act(LayerNorm(x) W^T + bias).
- * The two calls per transformer block it replaces in MONAI's TransformerBlock.forward (built at unetr.py:78-89):
- * attn.qkv(norm1(x)) and mlp.linear1(norm2(x)) followed by GELU.  x fp32 [M,K] (pitch ldx), gamma / beta [K], W bf16 [N,K]
- * (pitch ldw, K contiguous).  Outputs (any may be NULL except that one of C / Cb is required): C fp32 / Cb bf16 [M,N]
- * after the activation (act: 0 none, 1 exact-erf GELU), pre fp32 [M,N] before it; xn bf16 [M,K] = the normalised rows,
- * mean / rstd [M] (the LayerNorm backward's and the weight gradient's inputs).  K % 64 == 0, K <= 1024, N % 4 == 0. */
-typedef struct {
-    const float* x; long ldx;
-    const float* gamma; const float* beta; float eps;
-    const void* W; long ldw;
-    const float* bias; int act;
-    float* pre; long ldpre;
-    void* Cb; long ldcb;
-    float* C; long ldc;
-    void* xn; float* mean; float* rstd;
-    int M, N, K;
-} unetr_ln_gemm_desc;
-int unetr_ln_gemm_bf16(const unetr_ln_gemm_desc* d, void* stream);
 
 /* The small transposed convs (Cin a multiple of 64, bf16 mode) run as plain unetr_gemm_bf16 calls on torch's own weight
  * matrix [Cin, Cout*8]; these two move between the GEMM-side matrix t / g [M, Cout*8] (column = co*8 + tap) and the

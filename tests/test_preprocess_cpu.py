@@ -107,7 +107,7 @@ def test_public_signatures(pkg):
     assert p["scale_range"].default is None and p["crop_foreground"].default is False
     assert list(inspect.signature(pkg.preprocess.plan).parameters) == ["shape", "affine", "pixdim", "axcodes"]
     assert callable(pkg.VolumeCache.affine)
-    assert "unetr_resample_orient" in pkg._capi.EXPORTED_SYMBOLS and pkg._capi.ABI_VERSION == 20
+    assert "unetr_resample_orient" in pkg._capi.EXPORTED_SYMBOLS and pkg._capi.ABI_VERSION == 21
 
 
 def test_cpu_tensors_have_no_fallback(pkg):

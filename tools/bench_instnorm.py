@@ -33,25 +33,3 @@ for name, (fn, passes) in cases.items():
     e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / 30
     print(f"{name:28s} {ms * 1e3:7.1f} us  {passes * mb / ms / 1e3:6.2f} TB/s")
-
-if "sweep" in sys.argv[1:] or os.environ.get("IN_SWEEP"):
-    # tuning hooks of the backward reduce pass (read at launch time by the C ABI): voxels in flight per thread x grid size
-    def t(fn):
-        fn(); torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            for _ in range(10):
-                fn()
-        g.replay(); torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(3):
-            g.replay()
-        e1.record(); torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / 30 * 1e3
-    for u in (2, 3, 4):
-        for blocks in (512, 768, 1024, 1536, 2048, 4096):
-            os.environ["UNETR_IN_U"], os.environ["UNETR_IN_BLOCKS"] = str(u), str(blocks)
-            a = t(lambda: Fn.instnorm_bwd(dy, C, c1, s1, B, V, C, True))
-            b = t(lambda: Fn.instnorm_bwd(dy, C, c2, s2, B, V, C, True, x2=c3, sb=s3))
-            print(f"U={u} blocks={blocks:5d}: bwd single {a:7.1f} us   bwd dual {b:7.1f} us", flush=True)

@@ -33,7 +33,7 @@ def timeit(fn, reps=20, iters=10):
 
 
 def env(**kw):
-    for k in ("UNETR_GEMM_CFG", "UNETR_GEMM_SPLITS", "UNETR_GEMM_STAGES", "UNETR_LNGEMM_BN"):
+    for k in ("UNETR_GEMM_CFG", "UNETR_GEMM_SPLITS"):
         os.environ.pop(k, None)
     for k, v in kw.items():
         os.environ[k] = str(v)
@@ -63,14 +63,6 @@ for cfg in ("6464", "64128", "6496"):
         lambda: Fn.gemm_bf16(xb, w["w1"], M, MLP, H, Cb=ab, bias=bias3, act=1, pre=u))
     qb2_ = torch.empty(M, 3 * H, device=dev, dtype=torch.bfloat16)
     res[f"gemm_bf16 qkv   N=2304 K=768  cfg {cfg} (bf16 out only)"] = timeit(lambda: Fn.gemm_bf16(xb, w["qkv"], M, 3 * H, H, Cb=qb2_))
-for bn in (64, 128):
-    env(UNETR_LNGEMM_BN=bn)
-    res[f"ln_gemm   qkv   N=2304 K=768  BN {bn} (fp32 out, keeps xn/mean/rstd)"] = timeit(
-        lambda: Fn.ln_gemm_bf16(x, gam, bet, w["qkv"], C=qkv, xn=y1b, mean=m1, rstd=r1))
-    qb_ = torch.empty(M, 3 * H, device=dev, dtype=torch.bfloat16)
-    res[f"ln_gemm   qkv   N=2304 K=768  BN {bn} (bf16 out only)"] = timeit(lambda: Fn.ln_gemm_bf16(x, gam, bet, w["qkv"], Cb=qb_))
-    res[f"ln_gemm   mlp1  N=3072 K=768  BN {bn} (+gelu, bf16 out, pre, keeps)"] = timeit(
-        lambda: Fn.ln_gemm_bf16(x, gam, bet, w["w1"], bias=bias3, act=1, Cb=ab, pre=u, xn=y1b, mean=m1, rstd=r1))
 for cfg in ("6464", "6432", "3264"):
     for sp in (0, 1):
         env(UNETR_GEMM_CFG=cfg, **({"UNETR_GEMM_SPLITS": 1} if sp else {}))
@@ -79,10 +71,6 @@ for cfg in ("6464", "6432", "3264"):
             lambda: Fn.gemm_bf16(xb, w["p"], M, H, H, C=x1, bias=bias1, res=x, ldr=H))
         res[f"gemm_bf16 mlp2  N=768  K=3072 cfg {cfg} {tag} (+bias,res)"] = timeit(
             lambda: Fn.gemm_bf16(hb, w["w2"], M, H, MLP, C=x1, bias=bias1, res=x, ldr=H))
-for st in (2, 4, 6):
-    env(UNETR_GEMM_CFG="6464", UNETR_GEMM_STAGES=st, UNETR_GEMM_SPLITS=1)
-    res[f"gemm_bf16 mlp2  N=768  K=3072 cfg 6464 no split stages {st}"] = timeit(
-        lambda: Fn.gemm_bf16(hb, w["w2"], M, H, MLP, C=x1, bias=bias1, res=x, ldr=H))
 # data gradients (B read as [K,N])
 dyb = torch.randn(M, H, device=dev).bfloat16()
 dub = torch.randn(M, MLP, device=dev).bfloat16()

@@ -1,6 +1,6 @@
 """ViT GEMM shapes at batch 2 with COLD weights: every launch of the timed chain reads a different copy of the weight matrix
 (enough copies to exceed L2 + Infinity Cache), as the real step does -- tools/probe_encoder.py re-reads one warm matrix.
-Rows: ring depth (UNETR_GEMM_STAGES) x tile (UNETR_GEMM_CFG); us per launch inside a hipGraph chain."""
+Rows: tile (UNETR_GEMM_CFG); us per launch inside a hipGraph chain."""
 import importlib
 import os
 import sys
@@ -35,7 +35,7 @@ def timeit(fns, iters=5):
 
 
 def env(**kw):
-    for k in ("UNETR_GEMM_CFG", "UNETR_GEMM_SPLITS", "UNETR_GEMM_STAGES"):
+    for k in ("UNETR_GEMM_CFG", "UNETR_GEMM_SPLITS"):
         os.environ.pop(k, None)
     for k, v in kw.items():
         os.environ[k] = str(v)
@@ -64,20 +64,13 @@ wkey = {"fwd qkv": "qkv", "fwd proj": "p", "fwd mlp1": "w1", "fwd mlp2": "w2", "
 hq = hb[:, :3 * H].contiguous()
 shapes["dgrad dqkv N=768  K=2304"] = lambda w: Fn.gemm_bf16(hq, w, M, H, 3 * H, b_kn=True, C=o768)
 cfgs = os.environ.get("PROBE_CFGS", "0,6464,6432,3264").split(",")
-stages = os.environ.get("PROBE_STAGES", "0,6,8").split(",")
 for name, fn in shapes.items():
     ws = W[wkey[" ".join(name.split()[:2])]]
     for cfg in cfgs:
-        for st in stages:
-            kw = {}
-            if cfg != "0":
-                kw["UNETR_GEMM_CFG"] = cfg
-            if st != "0":
-                kw["UNETR_GEMM_STAGES"] = st
-            env(**kw)
-            try:
-                cold = timeit([lambda w=w: fn(w) for w in ws])
-                warm = timeit([lambda: fn(ws[0])] * 24)
-                print(f"{name}  cfg {cfg:>5s} stages {st:>2s}: cold {cold:6.2f} us   warm {warm:6.2f} us", flush=True)
-            except Exception as e:
-                print(f"{name}  cfg {cfg:>5s} stages {st:>2s}: {type(e).__name__} {str(e)[:60]}", flush=True)
+        env(**({"UNETR_GEMM_CFG": cfg} if cfg != "0" else {}))
+        try:
+            cold = timeit([lambda w=w: fn(w) for w in ws])
+            warm = timeit([lambda: fn(ws[0])] * 24)
+            print(f"{name}  cfg {cfg:>5s}: cold {cold:6.2f} us   warm {warm:6.2f} us", flush=True)
+        except Exception as e:
+            print(f"{name}  cfg {cfg:>5s}: {type(e).__name__} {str(e)[:60]}", flush=True)
