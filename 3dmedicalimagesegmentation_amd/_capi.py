@@ -66,6 +66,10 @@ class SplitProblem(ctypes.Structure):
     _fields_ = [("src", c_void_p), ("dst", c_void_p), ("rows", c_long), ("cols", c_long), ("second", c_int)]
 
 
+class Prefetch(ctypes.Structure):
+    _fields_ = [("ptr", c_void_p * 2), ("bytes", c_size_t * 2)]
+
+
 class ColsumProblem(ctypes.Structure):
     _fields_ = [("x", c_void_p), ("out", c_void_p), ("ld", c_long), ("M", c_int), ("N", c_int), ("x_bf16", c_int)]
 
@@ -83,13 +87,17 @@ _SIGNATURES = {
     "unetr_gemm": [ctypes.POINTER(GemmDesc), P, P, P, P, c_size_t, P],
     "unetr_gemm_bf16": [ctypes.POINTER(GemmBf16Desc), P, P, P, P, P, c_size_t, P],
     "unetr_gemm_bf16_ln_bwd": [ctypes.POINTER(GemmBf16Desc), P, P, P, P, P, P, P, P, P, P, P, P, P, c_size_t, P, c_size_t, P],
+    "unetr_gemm_bf16_ln_bwd_pf": [ctypes.POINTER(GemmBf16Desc), P, P, P, P, P, P, P, P, P, P, P, P, P, c_size_t, P, c_size_t, P, ctypes.POINTER(Prefetch)],
     "unetr_gemm_bf16_ln_fwd": [ctypes.POINTER(GemmBf16Desc), P, P, P, P, P, c_float, P, P, P, P, P, c_size_t, P],
+    "unetr_gemm_bf16_ln_fwd_pf": [ctypes.POINTER(GemmBf16Desc), P, P, P, P, P, c_float, P, P, P, P, P, c_size_t, P, ctypes.POINTER(Prefetch)],
     "unetr_cast_bf16": [P, P, c_long, P],
     "unetr_split_words": [P, P, c_long, P],
     "unetr_split_stack_bf16": [P, P, c_long, c_long, c_int, P],
     "unetr_split_stack_bf16_grouped": [ctypes.POINTER(SplitProblem), c_int, P],
     "unetr_attention_bf16_fwd": [P, P, P, P, c_int, c_int, c_int, c_int, c_float, P],
+    "unetr_attention_bf16_fwd_pf": [P, P, P, P, c_int, c_int, c_int, c_int, c_float, P, ctypes.POINTER(Prefetch)],
     "unetr_attention_bf16_bwd": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P],
+    "unetr_attention_bf16_bwd_pf": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P, ctypes.POINTER(Prefetch)],
     "unetr_gemm_grouped_wgrad": [ctypes.POINTER(GroupedProblem), c_int, c_int, P],
     "unetr_gemm_bf16_grouped_wgrad": [ctypes.POINTER(GroupedProblem), c_int, P],
     "unetr_gemm_bf16_grouped_wgrad_adamw": [ctypes.POINTER(GroupedProblem), c_int, ctypes.POINTER(AdamWArena), ctypes.POINTER(c_int), P],
@@ -109,7 +117,9 @@ _SIGNATURES = {
     "unetr_pixel_unshuffle2_bf16": [P, c_long, P, c_int, c_int, c_int, c_int, c_int, c_int, P],
     "unetr_colsum": [P, c_long, c_int, c_int, P, c_int, P, c_size_t, P],
     "unetr_layernorm_fwd": [P, P, P, P, P, P, P, c_int, c_int, c_float, P],
+    "unetr_layernorm_fwd_pf": [P, P, P, P, P, P, P, c_int, c_int, c_float, P, ctypes.POINTER(Prefetch)],
     "unetr_layernorm_bwd": [P, P, P, P, P, P, P, P, P, P, c_int, c_int, P, c_size_t, P],
+    "unetr_layernorm_bwd_pf": [P, P, P, P, P, P, P, P, P, P, c_int, c_int, P, c_size_t, P, ctypes.POINTER(Prefetch)],
     "unetr_attention_fwd": [P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_int, P],
     "unetr_attention_bwd": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_int, P],
     "unetr_conv_pack_weight": [P, P, c_int, c_int, c_int, c_int, P],

@@ -150,8 +150,11 @@ __device__ __forceinline__ float grp_sum(float v) { v += __shfl_xor(v, 16, 64); 
 template <int NW>
 __global__ void __launch_bounds__(64 * NW)
 attn16_fwd_kernel(const uint16_t* __restrict__ qkv, float* __restrict__ out, uint16_t* __restrict__ outb, float* __restrict__ lse,
-                  int L, int heads, float scale) {
+                  int L, int heads, float scale, PrefetchRider pf) {
     constexpr int NT = 64 * NW;
+    // with a prefetch rider (common.hpp) the grid has one more z plane, dispatched after the work planes: its blocks read the next
+    // GEMMs' weights and return
+    if (pf.nblk && blockIdx.z == gridDim.z - 1) { prefetch_rider_block(pf, blockIdx.y * gridDim.x + blockIdx.x); return; }
     extern __shared__ __attribute__((aligned(1024))) char lds[];
     char* kimg = lds;
     char* vimg = lds + IMG;
@@ -445,7 +448,9 @@ template <int NW>
 __global__ void __launch_bounds__(64 * NW)
 attn16_bwd_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ outb, const uint16_t* __restrict__ doutb,
                   const float* __restrict__ lse, float* __restrict__ delta, float* __restrict__ dqkv, uint16_t* __restrict__ dqkvb,
-                  int L, int heads, float scale, int nqb) {
+                  int L, int heads, float scale, int nqb, PrefetchRider pf) {
+    // (the last z plane of a launch with a prefetch rider: see attn16_fwd_kernel)
+    if (pf.nblk && blockIdx.z == gridDim.z - 1) { prefetch_rider_block(pf, blockIdx.y * gridDim.x + blockIdx.x); return; }
     extern __shared__ __attribute__((aligned(1024))) char lds[];
     const int xb = __builtin_amdgcn_readfirstlane(blockIdx.x);
     if (xb < nqb) attn16_bwd_dq_body<NW>(lds, xb, qkv, outb, doutb, lse, delta, dqkv, dqkvb, L, heads, scale);
@@ -468,26 +473,40 @@ inline int pick_nw_fwd(int B, int L, int heads) {
     return (nw == 4 && (long)cdiv(L, 64) * heads * B > 1024) ? 8 : nw;
 }
 
+// the rider plane of a (query block, head, batch item) grid: gx * heads blocks sharing the ranges evenly
+inline PrefetchRider attn_rider(const unetr_prefetch* pf, int gx, int heads, int B) {
+    return B < 65535 ? prefetch_rider(pf, 0, gx * heads) : prefetch_rider(nullptr, 0);
+}
+
 }  // namespace
 
-extern "C" int unetr_attention_bf16_fwd(const void* qkv, float* out, void* out_bf16, float* lse, int B, int L, int heads, int dh,
-                                        float scale, void* stream) {
+extern "C" int unetr_attention_bf16_fwd_pf(const void* qkv, float* out, void* out_bf16, float* lse, int B, int L, int heads, int dh,
+                                           float scale, void* stream, const unetr_prefetch* pf) {
     if (!qkv || (!out && !out_bf16) || !lse || B <= 0 || L <= 0 || heads <= 0 || B > 65535 || heads > 65535) return UNETR_ERR_ARG;
     if (dh != DH || ((uintptr_t)qkv & 15) || (out && ((uintptr_t)out & 15)) || (out_bf16 && ((uintptr_t)out_bf16 & 7))) return UNETR_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = 2 * IMG;
     const int nw = pick_nw_fwd(B, L, heads);
+    const int gx = cdiv(L, 16 * nw);
+    const PrefetchRider rd = attn_rider(pf, gx, heads, B);
+    const dim3 grid(gx, heads, B + (rd.nblk ? 1 : 0));
     if (nw == 2)
-        launch_dyn(attn16_fwd_kernel<2>, dim3(cdiv(L, 32), heads, B), 128, lds, st, (const uint16_t*)qkv, out, (uint16_t*)out_bf16, lse, L, heads, scale);
+        launch_dyn(attn16_fwd_kernel<2>, grid, 128, lds, st, (const uint16_t*)qkv, out, (uint16_t*)out_bf16, lse, L, heads, scale, rd);
     else if (nw == 4)
-        launch_dyn(attn16_fwd_kernel<4>, dim3(cdiv(L, 64), heads, B), 256, lds, st, (const uint16_t*)qkv, out, (uint16_t*)out_bf16, lse, L, heads, scale);
+        launch_dyn(attn16_fwd_kernel<4>, grid, 256, lds, st, (const uint16_t*)qkv, out, (uint16_t*)out_bf16, lse, L, heads, scale, rd);
     else
-        launch_dyn(attn16_fwd_kernel<8>, dim3(cdiv(L, 128), heads, B), 512, lds, st, (const uint16_t*)qkv, out, (uint16_t*)out_bf16, lse, L, heads, scale);
+        launch_dyn(attn16_fwd_kernel<8>, grid, 512, lds, st, (const uint16_t*)qkv, out, (uint16_t*)out_bf16, lse, L, heads, scale, rd);
     return unetr_check_launch();
 }
 
-extern "C" int unetr_attention_bf16_bwd(const void* qkv, const void* out_bf16, const void* dout_bf16, const float* lse, float* dqkv,
-                                        void* dqkv_bf16, float* delta, int B, int L, int heads, int dh, float scale, void* stream) {
+extern "C" int unetr_attention_bf16_fwd(const void* qkv, float* out, void* out_bf16, float* lse, int B, int L, int heads, int dh,
+                                        float scale, void* stream) {
+    return unetr_attention_bf16_fwd_pf(qkv, out, out_bf16, lse, B, L, heads, dh, scale, stream, nullptr);
+}
+
+extern "C" int unetr_attention_bf16_bwd_pf(const void* qkv, const void* out_bf16, const void* dout_bf16, const float* lse, float* dqkv,
+                                           void* dqkv_bf16, float* delta, int B, int L, int heads, int dh, float scale, void* stream,
+                                           const unetr_prefetch* pf) {
     if (!qkv || !out_bf16 || !dout_bf16 || !lse || !dqkv_bf16 || !delta || B <= 0 || L <= 0 || heads <= 0 || B > 65535 || heads > 65535)
         return UNETR_ERR_ARG;
     if (dh != DH || ((uintptr_t)qkv & 15) || ((uintptr_t)out_bf16 & 15) || ((uintptr_t)dout_bf16 & 15) || ((uintptr_t)dqkv_bf16 & 7) ||
@@ -501,10 +520,17 @@ extern "C" int unetr_attention_bf16_bwd(const void* qkv, const void* out_bf16, c
     const size_t lk = 2 * IMG + 2 * CKEYS * sizeof(float);
     if (pick_nw(B, L, heads) == 2) {
         const int nqb = cdiv(L, 32);
-        launch_dyn(attn16_bwd_kernel<2>, dim3(2 * nqb, heads, B), 128, lk, st, q, o, d, lse, delta, dqkv, gq, L, heads, scale, nqb);
+        const PrefetchRider rd = attn_rider(pf, 2 * nqb, heads, B);
+        launch_dyn(attn16_bwd_kernel<2>, dim3(2 * nqb, heads, B + (rd.nblk ? 1 : 0)), 128, lk, st, q, o, d, lse, delta, dqkv, gq, L, heads, scale, nqb, rd);
     } else {
         const int nqb = cdiv(L, 64);
-        launch_dyn(attn16_bwd_kernel<4>, dim3(2 * nqb, heads, B), 256, lk, st, q, o, d, lse, delta, dqkv, gq, L, heads, scale, nqb);
+        const PrefetchRider rd = attn_rider(pf, 2 * nqb, heads, B);
+        launch_dyn(attn16_bwd_kernel<4>, dim3(2 * nqb, heads, B + (rd.nblk ? 1 : 0)), 256, lk, st, q, o, d, lse, delta, dqkv, gq, L, heads, scale, nqb, rd);
     }
     return unetr_check_launch();
+}
+
+extern "C" int unetr_attention_bf16_bwd(const void* qkv, const void* out_bf16, const void* dout_bf16, const float* lse, float* dqkv,
+                                        void* dqkv_bf16, float* delta, int B, int L, int heads, int dh, float scale, void* stream) {
+    return unetr_attention_bf16_bwd_pf(qkv, out_bf16, dout_bf16, lse, dqkv, dqkv_bf16, delta, B, L, heads, dh, scale, stream, nullptr);
 }

@@ -12,6 +12,7 @@
 #include "../../include/unetr_hip.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -281,15 +282,66 @@ __device__ __forceinline__ u32x4 act_chunk(const typename ActOf<P>::type* p, boo
     const u32x4 w = *(const u32x4*)p;
     return ok ? P::from_raw(w) : (u32x4){0u, 0u, 0u, 0u};
 }
+// ---- prefetch rider: extra workgroups of a small launch that only READ the weight bytes the following GEMM(s) will want, so that
+// those lines sit in the Infinity Cache when the GEMM starts (unetr_prefetch in the header).  The two ranges, trimmed to whole
+// 16-byte units inside [ptr, ptr + bytes), are numbered as one sequence of units: range 0 first, then range 1; rider block r
+// owns units [r * upb, (r + 1) * upb).  nblk == 0: the launch carries no rider.
+struct PrefetchRider { const u32x4* p[2]; long u[2]; int upb, nblk; };
+
+// host side: `block_bytes` per rider block, or -- fixed_blocks > 0 -- exactly that many rider blocks sharing the units evenly
+static inline PrefetchRider prefetch_rider(const unetr_prefetch* pf, long block_bytes, int fixed_blocks = 0) {
+    PrefetchRider r{{nullptr, nullptr}, {0, 0}, 0, 0};
+    if (!pf) return r;
+    for (int i = 0; i < 2; ++i) {
+        if (!pf->ptr[i] || pf->bytes[i] < 16) continue;
+        const uintptr_t lo = ((uintptr_t)pf->ptr[i] + 15) & ~(uintptr_t)15, hi = ((uintptr_t)pf->ptr[i] + pf->bytes[i]) & ~(uintptr_t)15;
+        if (hi <= lo) continue;
+        r.p[i] = (const u32x4*)lo;
+        r.u[i] = (long)((hi - lo) >> 4);
+    }
+    const long total = r.u[0] + r.u[1];
+    if (total == 0) return r;
+    if (fixed_blocks > 0) {
+        r.nblk = fixed_blocks;
+        r.upb = (int)((total + fixed_blocks - 1) / fixed_blocks);
+    } else {
+        r.upb = (int)(block_bytes >> 4);
+        r.nblk = (int)std::min<long>((total + r.upb - 1) / r.upb, 4096);
+        r.upb = (int)((total + r.nblk - 1) / r.nblk);          // (the cap above: fewer, larger shares)
+    }
+    return r;
+}
+
+// device side: rider block `rb` of the launch reads its units with plain 16-byte loads (default cache policy: the lines are to be
+// allocated), PF_FLIGHT per thread before the first wait; the values go nowhere (the empty asm keeps the loads alive).  A unit
+// index past the block's share is clamped to its last unit -- a repeated read, never one outside the ranges.
+constexpr int PF_FLIGHT = 8;
+__device__ __forceinline__ void prefetch_rider_block(const PrefetchRider& r, int rb) {
+    const long total = r.u[0] + r.u[1];
+    const long lo = (long)rb * r.upb, hi = min(lo + r.upb, total);
+    const int nt = blockDim.x;
+    for (long i = lo + threadIdx.x; i < hi; i += (long)nt * PF_FLIGHT) {
+        u32x4 v[PF_FLIGHT];
+#pragma unroll
+        for (int j = 0; j < PF_FLIGHT; ++j) {
+            const long k = min(i + (long)j * nt, hi - 1);
+            const u32x4* q = k < r.u[0] ? r.p[0] + k : r.p[1] + (k - r.u[0]);
+            v[j] = *q;
+        }
+#pragma unroll
+        for (int j = 0; j < PF_FLIGHT; ++j) asm volatile("" ::"v"(v[j]));
+    }
+}
+
 // LayerNorm backward whose dy arrives as split-K partial slabs (norm_misc.hip; used by unetr_gemm_bf16_ln_bwd in gemm_bf16.hip)
 int unetr_layernorm_bwd_partials(const float* dy, int splits, long slab, const float* x, const float* gamma, const float* mean,
                                  const float* rstd, float* dx, void* dx_bf16, const float* dres, float* dgamma,
-                                 float* dbeta, int M, int H, float* ws, size_t ws_bytes, void* stream);
+                                 float* dbeta, int M, int H, float* ws, size_t ws_bytes, void* stream, const unetr_prefetch* pf = nullptr);
 
 // LayerNorm forward whose rows arrive as split-K partial slabs + (bias, residual) epilogue (norm_misc.hip; unetr_gemm_bf16_ln_fwd)
 int unetr_layernorm_fwd_partials(const float* partials, int splits, long slab, const float* bias, const float* res, long ldr, int res_mod,
                                  float* xout, const float* gamma, const float* beta, float* y, void* y_bf16, float* mean, float* rstd,
-                                 int M, int H, float eps, void* stream);
+                                 int M, int H, float eps, void* stream, const unetr_prefetch* pf = nullptr);
 
 // bf16x3 Linear GEMM on fp32-stored operands through the LDS-DMA kernel (gemm_bf16.hip); UNSUPPORTED = take the generic family
 int unetr_gemm_x3_dma(const unetr_gemm_bf16_desc* d, const float* A, const float* B, int b_words, float* C, float* ws, size_t ws_bytes, void* stream,

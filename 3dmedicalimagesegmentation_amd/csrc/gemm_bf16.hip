@@ -1034,33 +1034,47 @@ extern "C" int unetr_gemm_bf16(const unetr_gemm_bf16_desc* d, const void* A, con
 // dx = LayerNorm backward of dy = A . B (a plain product: alpha 1, no bias / activation / residual) in two launches: when the
 // GEMM is cut into K slabs (the batch-2 data gradients with K = 2304 / 3072) the LayerNorm kernel sums the slabs itself, in the
 // order the separate reduce launch would; otherwise the product lands in the scratch matrix C [M, N] first.
-extern "C" int unetr_gemm_bf16_ln_bwd(const unetr_gemm_bf16_desc* d, const void* A, const void* B, float* C,
-                                      const float* x, const float* gamma, const float* mean, const float* rstd,
-                                      float* dx, void* dx_bf16, const float* dres, float* dgamma, float* dbeta,
-                                      float* ln_ws, size_t ln_ws_bytes, float* ws, size_t ws_bytes, void* stream) {
+// (pf: prefetch rider on the LayerNorm launch -- the weights of the GEMM(s) that follow it, common.hpp)
+extern "C" int unetr_gemm_bf16_ln_bwd_pf(const unetr_gemm_bf16_desc* d, const void* A, const void* B, float* C,
+                                         const float* x, const float* gamma, const float* mean, const float* rstd,
+                                         float* dx, void* dx_bf16, const float* dres, float* dgamma, float* dbeta,
+                                         float* ln_ws, size_t ln_ws_bytes, float* ws, size_t ws_bytes, void* stream, const unetr_prefetch* pf) {
     if (!d || !C) return UNETR_ERR_ARG;
     if (d->bias || d->res || d->pre || d->act || d->accumulate || d->alpha != 1.f || d->ldc != d->N) return UNETR_ERR_UNSUPPORTED;
     int splits = 1;
     if (int e = gemm_bf16_impl(d, A, B, C, nullptr, ws, ws_bytes, stream, &splits)) return e;
     const float* dy = splits > 1 ? ws : C;
     return unetr_layernorm_bwd_partials(dy, splits, (long)d->M * d->N, x, gamma, mean, rstd, dx, dx_bf16, dres, dgamma, dbeta,
-                                        d->M, d->N, ln_ws, ln_ws_bytes, stream);
+                                        d->M, d->N, ln_ws, ln_ws_bytes, stream, pf);
+}
+
+extern "C" int unetr_gemm_bf16_ln_bwd(const unetr_gemm_bf16_desc* d, const void* A, const void* B, float* C,
+                                      const float* x, const float* gamma, const float* mean, const float* rstd,
+                                      float* dx, void* dx_bf16, const float* dres, float* dgamma, float* dbeta,
+                                      float* ln_ws, size_t ln_ws_bytes, float* ws, size_t ws_bytes, void* stream) {
+    return unetr_gemm_bf16_ln_bwd_pf(d, A, B, C, x, gamma, mean, rstd, dx, dx_bf16, dres, dgamma, dbeta, ln_ws, ln_ws_bytes, ws, ws_bytes, stream, nullptr);
 }
 
 // C = A . B + bias + res (the residual-stream output of a block's last Linear) AND the LayerNorm of C that the next layer starts
 // with, in two launches: when the GEMM is cut into K slabs the LayerNorm kernel sums the slabs, applies bias and residual, writes
 // C and normalises the row it has just formed; otherwise the GEMM writes C through its own epilogue and the plain LayerNorm runs.
-extern "C" int unetr_gemm_bf16_ln_fwd(const unetr_gemm_bf16_desc* d, const void* A, const void* B, float* C,
-                                      const float* gamma, const float* beta, float eps, float* y, void* y_bf16, float* mean, float* rstd,
-                                      float* ws, size_t ws_bytes, void* stream) {
+extern "C" int unetr_gemm_bf16_ln_fwd_pf(const unetr_gemm_bf16_desc* d, const void* A, const void* B, float* C,
+                                         const float* gamma, const float* beta, float eps, float* y, void* y_bf16, float* mean, float* rstd,
+                                         float* ws, size_t ws_bytes, void* stream, const unetr_prefetch* pf) {
     if (!d || !C) return UNETR_ERR_ARG;
     if (d->pre || d->act || d->accumulate || d->alpha != 1.f || d->ldc != d->N) return UNETR_ERR_UNSUPPORTED;
     int splits = 1;
     if (int e = gemm_bf16_impl(d, A, B, C, nullptr, ws, ws_bytes, stream, &splits)) return e;
     if (splits > 1)
         return unetr_layernorm_fwd_partials(ws, splits, (long)d->M * d->N, d->bias, d->res, d->ldr, d->res_mod > 0 ? d->res_mod : d->M,
-                                            C, gamma, beta, y, y_bf16, mean, rstd, d->M, d->N, eps, stream);
-    return unetr_layernorm_fwd(C, gamma, beta, y, y_bf16, mean, rstd, d->M, d->N, eps, stream);
+                                            C, gamma, beta, y, y_bf16, mean, rstd, d->M, d->N, eps, stream, pf);
+    return unetr_layernorm_fwd_pf(C, gamma, beta, y, y_bf16, mean, rstd, d->M, d->N, eps, stream, pf);
+}
+
+extern "C" int unetr_gemm_bf16_ln_fwd(const unetr_gemm_bf16_desc* d, const void* A, const void* B, float* C,
+                                      const float* gamma, const float* beta, float eps, float* y, void* y_bf16, float* mean, float* rstd,
+                                      float* ws, size_t ws_bytes, void* stream) {
+    return unetr_gemm_bf16_ln_fwd_pf(d, A, B, C, gamma, beta, eps, y, y_bf16, mean, rstd, ws, ws_bytes, stream, nullptr);
 }
 
 // fp32 -> bf16 (round to nearest even), the weight shadow / activation cast

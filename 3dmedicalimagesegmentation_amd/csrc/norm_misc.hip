@@ -18,7 +18,10 @@ template <int LN_MAXV>
 __global__ void __launch_bounds__(256)
 layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
                      float* __restrict__ y, uint16_t* __restrict__ yb, float* __restrict__ mean, float* __restrict__ rstd,
-                     int M, int H, float eps, LnFwdSrc src) {
+                     int M, int H, float eps, LnFwdSrc src, PrefetchRider pf) {
+    // blocks past the row blocks are prefetch riders (common.hpp): they read the next GEMM's weights and touch nothing else
+    const int rider = (int)blockIdx.x - ((int)gridDim.x - pf.nblk);
+    if (rider >= 0) { prefetch_rider_block(pf, rider); return; }
     const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
     const int nv = H >> 2;
@@ -101,7 +104,10 @@ template <int LN_MAXV>
 __global__ void __launch_bounds__(256)
 layernorm_bwd_kernel(const float* __restrict__ dy, int splits, long slab, const float* __restrict__ x, const float* __restrict__ gamma,
                      const float* __restrict__ mean, const float* __restrict__ rstd, float* __restrict__ dx,
-                     uint16_t* __restrict__ dxb, const float* __restrict__ dres, float* __restrict__ part, int M, int H) {
+                     uint16_t* __restrict__ dxb, const float* __restrict__ dres, float* __restrict__ part, int M, int H, PrefetchRider pf) {
+    // blocks past the nblk row blocks are prefetch riders (common.hpp): no LDS, no barrier, no partial row of theirs
+    const int rider = (int)blockIdx.x - ((int)gridDim.x - pf.nblk);
+    if (rider >= 0) { prefetch_rider_block(pf, rider); return; }
     // dy may arrive as `splits` split-K partial slabs of the GEMM that produced it (slab = elements between slabs): they are
     // summed here in slab order from 0.f -- the arithmetic of splitk_reduce_kernel, whose launch this saves
     extern __shared__ __attribute__((aligned(16))) float lds[];  // [4 waves][2][H]
@@ -1712,28 +1718,37 @@ inline int grid_for(long total, int per_block = 256, int cap = 8192) {
 }  // namespace
 
 // ============================================================================================ C ABI
-extern "C" int unetr_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, void* y_bf16,
-                                   float* mean, float* rstd, int M, int H, float eps, void* stream) {
+constexpr long LN_PF_BLOCK_BYTES = 32 * 1024;   // per rider block: one round of PF_FLIGHT 16-byte loads per thread
+
+extern "C" int unetr_layernorm_fwd_pf(const float* x, const float* gamma, const float* beta, float* y, void* y_bf16,
+                                      float* mean, float* rstd, int M, int H, float eps, void* stream, const unetr_prefetch* pf) {
     if (!x || !gamma || !beta || (!y && !y_bf16) || !mean || !rstd || M <= 0) return UNETR_ERR_ARG;
     if ((H & 3) || H > LN_MAXV_MAX * 256) return UNETR_ERR_UNSUPPORTED;
     const LnFwdSrc src{1, 0, nullptr, nullptr, 0, 1, nullptr};
-#define LN_FWD(V_) hipLaunchKernelGGL(layernorm_fwd_kernel<V_>, dim3(cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, \
-                                      (uint16_t*)y_bf16, mean, rstd, M, H, eps, src)
+    const PrefetchRider rd = prefetch_rider(pf, LN_PF_BLOCK_BYTES);
+#define LN_FWD(V_) hipLaunchKernelGGL(layernorm_fwd_kernel<V_>, dim3(cdiv(M, 4) + rd.nblk), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, \
+                                      (uint16_t*)y_bf16, mean, rstd, M, H, eps, src, rd)
     if (H <= 768) LN_FWD(3); else if (H <= 1024) LN_FWD(4); else LN_FWD(8);
 #undef LN_FWD
     return unetr_check_launch();
 }
 
+extern "C" int unetr_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, void* y_bf16,
+                                   float* mean, float* rstd, int M, int H, float eps, void* stream) {
+    return unetr_layernorm_fwd_pf(x, gamma, beta, y, y_bf16, mean, rstd, M, H, eps, stream, nullptr);
+}
+
 // rows = split-K partial slabs + epilogue (see LnFwdSrc); declared in common.hpp for unetr_gemm_bf16_ln_fwd
 int unetr_layernorm_fwd_partials(const float* partials, int splits, long slab, const float* bias, const float* res, long ldr, int res_mod,
                                  float* xout, const float* gamma, const float* beta, float* y, void* y_bf16, float* mean, float* rstd,
-                                 int M, int H, float eps, void* stream) {
+                                 int M, int H, float eps, void* stream, const unetr_prefetch* pf) {
     if (!partials || splits < 2 || !xout || !gamma || !beta || (!y && !y_bf16) || !mean || !rstd || M <= 0) return UNETR_ERR_ARG;
     if ((H & 3) || H > LN_MAXV_MAX * 256 || (res && (ldr & 3))) return UNETR_ERR_UNSUPPORTED;
     const LnFwdSrc src{splits, slab, bias, res, ldr, res_mod > 0 ? res_mod : M, xout};
     const float* x = partials;
-#define LN_FWD(V_) hipLaunchKernelGGL(layernorm_fwd_kernel<V_>, dim3(cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, \
-                                      (uint16_t*)y_bf16, mean, rstd, M, H, eps, src)
+    const PrefetchRider rd = prefetch_rider(pf, LN_PF_BLOCK_BYTES);
+#define LN_FWD(V_) hipLaunchKernelGGL(layernorm_fwd_kernel<V_>, dim3(cdiv(M, 4) + rd.nblk), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, \
+                                      (uint16_t*)y_bf16, mean, rstd, M, H, eps, src, rd)
     if (H <= 768) LN_FWD(3); else if (H <= 1024) LN_FWD(4); else LN_FWD(8);
 #undef LN_FWD
     return unetr_check_launch();
@@ -1742,24 +1757,31 @@ int unetr_layernorm_fwd_partials(const float* partials, int splits, long slab, c
 // dy as `splits` partial slabs (see the kernel); declared in common.hpp for unetr_gemm_bf16_ln_bwd
 int unetr_layernorm_bwd_partials(const float* dy, int splits, long slab, const float* x, const float* gamma, const float* mean,
                                  const float* rstd, float* dx, void* dx_bf16, const float* dres, float* dgamma,
-                                 float* dbeta, int M, int H, float* ws, size_t ws_bytes, void* stream) {
+                                 float* dbeta, int M, int H, float* ws, size_t ws_bytes, void* stream, const unetr_prefetch* pf) {
     if (!dy || !x || !gamma || !mean || !rstd || !dx || ((dgamma == nullptr) != (dbeta == nullptr)) || M <= 0) return UNETR_ERR_ARG;
     if ((H & 3) || H > LN_MAXV_MAX * 256) return UNETR_ERR_UNSUPPORTED;
     int nblk = cdiv(M, LN_RPB);
     if ((size_t)nblk * 2 * H * sizeof(float) > ws_bytes || !ws) return UNETR_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-#define LN_BWD(V_) hipLaunchKernelGGL(layernorm_bwd_kernel<V_>, dim3(nblk), dim3(256), 4 * 2 * H * sizeof(float), st, dy, splits, slab, x, gamma, mean, \
-                                      rstd, dx, (uint16_t*)dx_bf16, dres, ws, M, H)
+    const PrefetchRider rd = prefetch_rider(pf, LN_PF_BLOCK_BYTES);     // rider blocks follow the nblk row blocks; ws stays [nblk][2][H]
+#define LN_BWD(V_) hipLaunchKernelGGL(layernorm_bwd_kernel<V_>, dim3(nblk + rd.nblk), dim3(256), 4 * 2 * H * sizeof(float), st, dy, splits, slab, x, gamma, mean, \
+                                      rstd, dx, (uint16_t*)dx_bf16, dres, ws, M, H, rd)
     if (H <= 768) LN_BWD(3); else if (H <= 1024) LN_BWD(4); else LN_BWD(8);
     // dgamma == dbeta == NULL: the caller reduces the [nblk][2][H] partials left in ws itself (grouped, off the critical path)
     if (dgamma) hipLaunchKernelGGL(ln_finalize_kernel, dim3(cdiv(2 * H, 64)), dim3(256), 0, st, ws, nblk, H, dgamma, dbeta);
     return unetr_check_launch();
 }
 
+extern "C" int unetr_layernorm_bwd_pf(const float* dy, const float* x, const float* gamma, const float* mean,
+                                      const float* rstd, float* dx, void* dx_bf16, const float* dres, float* dgamma,
+                                      float* dbeta, int M, int H, float* ws, size_t ws_bytes, void* stream, const unetr_prefetch* pf) {
+    return unetr_layernorm_bwd_partials(dy, 1, 0, x, gamma, mean, rstd, dx, dx_bf16, dres, dgamma, dbeta, M, H, ws, ws_bytes, stream, pf);
+}
+
 extern "C" int unetr_layernorm_bwd(const float* dy, const float* x, const float* gamma, const float* mean,
                                    const float* rstd, float* dx, void* dx_bf16, const float* dres, float* dgamma,
                                    float* dbeta, int M, int H, float* ws, size_t ws_bytes, void* stream) {
-    return unetr_layernorm_bwd_partials(dy, 1, 0, x, gamma, mean, rstd, dx, dx_bf16, dres, dgamma, dbeta, M, H, ws, ws_bytes, stream);
+    return unetr_layernorm_bwd_pf(dy, x, gamma, mean, rstd, dx, dx_bf16, dres, dgamma, dbeta, M, H, ws, ws_bytes, stream, nullptr);
 }
 
 extern "C" int unetr_colsum(const float* x, long ld, int M, int N, float* out, int accumulate,

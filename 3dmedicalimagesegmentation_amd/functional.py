@@ -397,6 +397,7 @@ def gemm_bf16(A, B, M, N, K, *, b_kn=False, C=None, Cb=None, lda=None, ldb=None,
 # of this package that changes weights behind torch's back (per-parameter AdamW, DDP broadcast) bumps the epoch.
 # Under hipGraph capture a non-maintained shadow is always re-cast, so the cast is part of the captured step.
 _SHADOW = {}
+_SHADOW_AT = {}       # the same entries by the parameter's storage address (_prefetch is handed detached aliases)
 _WEIGHT_EPOCH = [0]
 
 
@@ -507,6 +508,7 @@ def refresh_x3_shadow(flat, written=False):
 def register_weight_shadow(w, shadow):
     """flat-arena mode: `shadow` is the bf16 view the optimizer kernel keeps in step with `w`"""
     _SHADOW[id(w)] = [shadow, w._version, _WEIGHT_EPOCH[0], True, weakref.ref(w), w.data_ptr()]   # caller has just cast it
+    _SHADOW_AT[w.data_ptr()] = _SHADOW[id(w)]
 
 
 def weight_bf16(w):
@@ -514,6 +516,7 @@ def weight_bf16(w):
     if ent is None or ent[4]() is not w or ent[0].shape != w.shape or ent[0].device != w.device:
         ent = [torch.empty(w.shape, dtype=torch.bfloat16, device=w.device), -1, -1, False, weakref.ref(w), 0]
         _SHADOW[id(w)] = ent
+        _SHADOW_AT[w.data_ptr()] = ent
     # (a re-pointed parameter -- `p.data = other` -- keeps its version counter: the storage address is part of the key)
     fresh = ent[1] == w._version and ent[5] == w.data_ptr() and (
         ent[3] or (ent[2] == _WEIGHT_EPOCH[0] and not torch.cuda.is_current_stream_capturing()))
@@ -589,6 +592,30 @@ def shadow_ptr_for_update(w):
         return None
     ent[3] = True
     return ent[0].data_ptr()
+
+
+# Prefetch riders: the launch just before a ViT Linear GEMM (a LayerNorm, the attention core) carries spare workgroups that read
+# the bf16 weights of the GEMM(s) behind it into the Infinity Cache (include/unetr_hip.h: unetr_prefetch).  Results are
+# bit-identical with and without; False launches every host exactly as without riders (tests/test_prefetch_rider_gpu.py), a
+# collection of host names ("attn_fwd", "ln1_fwd", "ln2_fwd", "ln1_bwd", "ln2_bwd", "attn_bwd") keeps only those (per-host A/B).
+PREFETCH_RIDERS = True
+
+
+def _prefetch(host, *weights):
+    """unetr_prefetch over the bf16 shadows of up to two weights for the launch `host`, or None.  Only a shadow that already
+    exists is named (its buffer lives as long as the parameter and is what the GEMM itself reads): no cast is launched from here."""
+    if not PREFETCH_RIDERS or (PREFETCH_RIDERS is not True and host not in PREFETCH_RIDERS):
+        return None
+    pf, n = _capi.Prefetch(), 0
+    for w in weights:
+        # (by storage address: callers hand detached aliases of the next / lower block's parameters)
+        ent = _SHADOW_AT.get(w.data_ptr()) if w is not None else None
+        owner = ent[4]() if ent is not None else None
+        if owner is None or owner.data_ptr() != w.data_ptr() or ent[0].shape != w.shape or ent[0].device != w.device:
+            continue
+        pf.ptr[n], pf.bytes[n] = ent[0].data_ptr(), ent[0].numel() * 2
+        n += 1
+    return pf if n else None
 
 
 def _bf16_path(prec, *kdims):
@@ -700,41 +727,41 @@ def bf16_like(t):
     return torch.empty(t.shape, dtype=torch.bfloat16, device=t.device)
 
 
-def layernorm_fwd(x, w, b, bf16_out=None, want_fp32=True):
+def layernorm_fwd(x, w, b, bf16_out=None, want_fp32=True, pf=None):
     M, H = x.shape
     y = torch.empty_like(x) if want_fp32 else None
     mean = torch.empty(M, dtype=torch.float32, device=x.device)
     rstd = torch.empty(M, dtype=torch.float32, device=x.device)
-    call("unetr_layernorm_fwd", x.data_ptr(), w.data_ptr(), b.data_ptr(), _p(y), _p(bf16_out), mean.data_ptr(),
-         rstd.data_ptr(), M, H, LN_EPS, _stream())
+    call("unetr_layernorm_fwd_pf", x.data_ptr(), w.data_ptr(), b.data_ptr(), _p(y), _p(bf16_out), mean.data_ptr(),
+         rstd.data_ptr(), M, H, LN_EPS, _stream(), pf)
     return y, mean, rstd
 
 
-def layernorm_bwd(dy, x, w, mean, rstd, dres=None, out_w=None, out_b=None, dx_bf16=None):
+def layernorm_bwd(dy, x, w, mean, rstd, dres=None, out_w=None, out_b=None, dx_bf16=None, pf=None):
     M, H = x.shape
     dx = torch.empty_like(x)
     dw = out_w if out_w is not None else torch.empty(H, dtype=torch.float32, device=x.device)
     db = out_b if out_b is not None else torch.empty(H, dtype=torch.float32, device=x.device)
     ws = workspace(x.device)
-    call("unetr_layernorm_bwd", dy.data_ptr(), x.data_ptr(), w.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
-         _p(dx_bf16), dres.data_ptr() if dres is not None else None, dw.data_ptr(), db.data_ptr(), M, H, ws.data_ptr(), ws.numel() * 4, _stream())
+    call("unetr_layernorm_bwd_pf", dy.data_ptr(), x.data_ptr(), w.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
+         _p(dx_bf16), dres.data_ptr() if dres is not None else None, dw.data_ptr(), db.data_ptr(), M, H, ws.data_ptr(), ws.numel() * 4, _stream(), pf)
     return dx, dw, db
 
 
-def layernorm_bwd_params(dy, x, w, b, mean, rstd, dres=None, dx_bf16=None):
+def layernorm_bwd_params(dy, x, w, b, mean, rstd, dres=None, dx_bf16=None, pf=None):
     """LayerNorm backward returning (dx, grad_w, grad_b) as autograd wants them.  In arena mode the dgamma/dbeta
     reduction over row blocks is not needed inside backward: the kernel leaves its partials in a private buffer and the
     two column sums join the grouped launch at the end of the pass (one launch for all 25 LayerNorms)."""
     ow, ob = _gout(w), _gout(b)
     if ow is None or ob is None:
-        dx, dw, db = layernorm_bwd(dy, x, w, mean, rstd, dres=dres, out_w=ow, out_b=ob, dx_bf16=dx_bf16)
+        dx, dw, db = layernorm_bwd(dy, x, w, mean, rstd, dres=dres, out_w=ow, out_b=ob, dx_bf16=dx_bf16, pf=pf)
         return dx, _ret(w, dw), _ret(b, db)
     M, H = x.shape
     nblk = (M + 3) // 4
     part = torch.empty(nblk * 2 * H, dtype=torch.float32, device=x.device)
     dx = torch.empty_like(x)
-    call("unetr_layernorm_bwd", dy.data_ptr(), x.data_ptr(), w.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
-         _p(dx_bf16), _p(dres), None, None, M, H, part.data_ptr(), part.numel() * 4, _stream())
+    call("unetr_layernorm_bwd_pf", dy.data_ptr(), x.data_ptr(), w.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
+         _p(dx_bf16), _p(dres), None, None, M, H, part.data_ptr(), part.numel() * 4, _stream(), pf)
     st = _GRAD_SINK[w.data_ptr()]
     st.defer["colsum"].append((part, ow, nblk, H, 2 * H))
     st.defer["colsum"].append((part[H:], ob, nblk, H, 2 * H))
@@ -747,7 +774,7 @@ def x3_ride_ok(M, N, K):
     return M >= 32 and K % 32 == 0 and N % 4 == 0 and N >= 64 and os.environ.get("UNETR_X3_GEMM_DMA", "1") != "0"
 
 
-def gemm_bf16_ln_fwd(A, B, M, N, K, C, gamma, beta, y_bf16, bias=None, res=None, ldr=0, y=None, b_words=None):
+def gemm_bf16_ln_fwd(A, B, M, N, K, C, gamma, beta, y_bf16, bias=None, res=None, ldr=0, y=None, b_words=None, pf=None):
     """C[M,N] = A[M,K] @ B[N,K]^T + bias + res, and y_bf16 = LayerNorm(C) (gamma, beta) with its (mean, rstd):
     unetr_gemm_bf16_ln_fwd -- the LayerNorm of the NEXT layer rides on the split-K reduction of this GEMM.
     bf16x3 mode: A / B fp32 (B optionally as its word shadow b_words), the normalised rows go to the fp32 tensor ``y``."""
@@ -765,8 +792,8 @@ def gemm_bf16_ln_fwd(A, B, M, N, K, C, gamma, beta, y_bf16, bias=None, res=None,
     mean = torch.empty(M, dtype=torch.float32, device=C.device)
     rstd = torch.empty(M, dtype=torch.float32, device=C.device)
     ws = workspace(C.device)
-    call("unetr_gemm_bf16_ln_fwd", ctypes.byref(d), A.data_ptr(), B.data_ptr(), C.data_ptr(), gamma.data_ptr(), beta.data_ptr(), LN_EPS,
-         _p(y), _p(y_bf16), mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream())
+    call("unetr_gemm_bf16_ln_fwd_pf", ctypes.byref(d), A.data_ptr(), B.data_ptr(), C.data_ptr(), gamma.data_ptr(), beta.data_ptr(), LN_EPS,
+         _p(y), _p(y_bf16), mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream(), pf)
     return mean, rstd
 
 
@@ -793,7 +820,7 @@ def _stashed_ln(x, gamma, beta):
     return st[0], st[1], st[2]
 
 
-def gemm_ln_bwd_params(A, Bw, M, N, K, x, w, b, mean, rstd, dres=None, dx_bf16=None, b_words=None):
+def gemm_ln_bwd_params(A, Bw, M, N, K, x, w, b, mean, rstd, dres=None, dx_bf16=None, b_words=None, pf=None):
     """(dx, grad_w, grad_b) of a LayerNorm whose output gradient is dy = A[M,K] @ Bw[K,N] (the data gradient of the Linear
     layer behind it, bf16-stored operands, Bw read as the [K, N] operand): unetr_gemm_bf16_ln_bwd -- when the GEMM is cut into K
     slabs the LayerNorm kernel sums them itself, so the separate split-K reduce launch disappears (bit-identical)."""
@@ -815,14 +842,14 @@ def gemm_ln_bwd_params(A, Bw, M, N, K, x, w, b, mean, rstd, dres=None, dx_bf16=N
         dw = ow if ow is not None else torch.empty(N, dtype=torch.float32, device=x.device)
         db = ob if ob is not None else torch.empty(N, dtype=torch.float32, device=x.device)
         lnws = torch.empty(nblk * 2 * N, dtype=torch.float32, device=x.device)
-        call("unetr_gemm_bf16_ln_bwd", ctypes.byref(d), A.data_ptr(), Bw.data_ptr(), scratch.data_ptr(), x.data_ptr(), w.data_ptr(),
+        call("unetr_gemm_bf16_ln_bwd_pf", ctypes.byref(d), A.data_ptr(), Bw.data_ptr(), scratch.data_ptr(), x.data_ptr(), w.data_ptr(),
              mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(), _p(dx_bf16), _p(dres), dw.data_ptr(), db.data_ptr(),
-             lnws.data_ptr(), lnws.numel() * 4, ws.data_ptr(), ws.numel() * 4, _stream())
+             lnws.data_ptr(), lnws.numel() * 4, ws.data_ptr(), ws.numel() * 4, _stream(), pf)
         return dx, _ret(w, dw), _ret(b, db)
     part = torch.empty(nblk * 2 * N, dtype=torch.float32, device=x.device)
-    call("unetr_gemm_bf16_ln_bwd", ctypes.byref(d), A.data_ptr(), Bw.data_ptr(), scratch.data_ptr(), x.data_ptr(), w.data_ptr(),
+    call("unetr_gemm_bf16_ln_bwd_pf", ctypes.byref(d), A.data_ptr(), Bw.data_ptr(), scratch.data_ptr(), x.data_ptr(), w.data_ptr(),
          mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(), _p(dx_bf16), _p(dres), None, None,
-         part.data_ptr(), part.numel() * 4, ws.data_ptr(), ws.numel() * 4, _stream())
+         part.data_ptr(), part.numel() * 4, ws.data_ptr(), ws.numel() * 4, _stream(), pf)
     st = _GRAD_SINK[w.data_ptr()]
     st.defer["colsum"].append((part, ow, nblk, N, 2 * N))
     st.defer["colsum"].append((part[N:], ob, nblk, N, 2 * N))
@@ -846,17 +873,17 @@ def attention_bwd(qkv, out, dout, lse, B, L, heads, dh, prec, dqkv_bf16=None):
     return dqkv
 
 
-def attention_bf16_fwd(qkvb, B, L, heads, dh, out_bf16, out=None):
+def attention_bf16_fwd(qkvb, B, L, heads, dh, out_bf16, out=None, pf=None):
     lse = torch.empty(B, heads, L, dtype=torch.float32, device=qkvb.device)
-    call("unetr_attention_bf16_fwd", qkvb.data_ptr(), _p(out), out_bf16.data_ptr(), lse.data_ptr(), B, L, heads, dh, float(dh) ** -0.5, _stream())
+    call("unetr_attention_bf16_fwd_pf", qkvb.data_ptr(), _p(out), out_bf16.data_ptr(), lse.data_ptr(), B, L, heads, dh, float(dh) ** -0.5, _stream(), pf)
     return lse
 
 
-def attention_bf16_bwd(qkvb, outb, doutb, lse, B, L, heads, dh, dqkv=None):
+def attention_bf16_bwd(qkvb, outb, doutb, lse, B, L, heads, dh, dqkv=None, pf=None):
     dqkvb = torch.empty_like(qkvb)
     delta = torch.empty_like(lse)
-    call("unetr_attention_bf16_bwd", qkvb.data_ptr(), outb.data_ptr(), doutb.data_ptr(), lse.data_ptr(), _p(dqkv), dqkvb.data_ptr(),
-         delta.data_ptr(), B, L, heads, dh, float(dh) ** -0.5, _stream())
+    call("unetr_attention_bf16_bwd_pf", qkvb.data_ptr(), outb.data_ptr(), doutb.data_ptr(), lse.data_ptr(), _p(dqkv), dqkvb.data_ptr(),
+         delta.data_ptr(), B, L, heads, dh, float(dh) ** -0.5, _stream(), pf)
     return dqkvb
 
 
@@ -1335,9 +1362,12 @@ class PatchEmbedFn(torch.autograd.Function):
         return None, dw, db, dpos, None, None
 
 
-def _tblock_forward(x, n1w, n1b, wqkv, wp, bp, n2w, n2b, w1, b1, w2, b2, B, L, heads, prec, train, next_ln=None, emit_twin=False):
+def _tblock_forward(x, n1w, n1b, wqkv, wp, bp, n2w, n2b, w1, b1, w2, b2, B, L, heads, prec, train, next_ln=None, emit_twin=False,
+                    next_wqkv=None):
     """kernels of one transformer block; returns (x2, tensors backward needs, bf16 twins or None).  next_ln = (gamma, beta) of
-    the LayerNorm the next layer starts with: computed by the kernel that forms x2 and left on x2 (_stash_ln)"""
+    the LayerNorm the next layer starts with: computed by the kernel that forms x2 and left on x2 (_stash_ln).  next_wqkv: the
+    qkv weight of that next layer, prefetched by the same kernel.  bf16 path: every non-GEMM launch prefetches the weights of
+    the GEMM(s) behind it (_prefetch)"""
     hid = x.shape[1]
     dh = hid // heads
     M, mlp = x.shape[0], w1.shape[0]
@@ -1353,12 +1383,12 @@ def _tblock_forward(x, n1w, n1b, wqkv, wp, bp, n2w, n2b, w1, b1, w2, b2, B, L, h
             y1b, m1, r1 = pre
         else:
             y1b = bf16_like(x)
-            _, m1, r1 = layernorm_fwd(x, n1w, n1b, bf16_out=y1b, want_fp32=False)
+            _, m1, r1 = layernorm_fwd(x, n1w, n1b, bf16_out=y1b, want_fp32=False, pf=_prefetch("ln1_fwd", wqkv))
         gemm_bf16(y1b, weight_bf16(wqkv), M, 3 * hid, hid, C=None if b16att else qkv, Cb=qkv if b16att else None)
         attb = bf16_like(x)
         if b16att:
             att = x.new_empty(0)
-            lse = attention_bf16_fwd(qkv, B, L, heads, dh, attb)
+            lse = attention_bf16_fwd(qkv, B, L, heads, dh, attb, pf=_prefetch("attn_fwd", wp, w1))
         else:
             att, lse = attention_fwd(qkv, B, L, heads, dh, prec, out_bf16=attb)
         x1 = torch.empty(M, hid, **f32)
@@ -1366,14 +1396,15 @@ def _tblock_forward(x, n1w, n1b, wqkv, wp, bp, n2w, n2b, w1, b1, w2, b2, B, L, h
         u = torch.empty(M, mlp, **f32) if train else None      # pre-activation, only GELU' in backward reads it
         ab = torch.empty(M, mlp, dtype=torch.bfloat16, device=x.device)
         y2b = bf16_like(x)
-        _, m2, r2 = layernorm_fwd(x1, n2w, n2b, bf16_out=y2b, want_fp32=False)
+        _, m2, r2 = layernorm_fwd(x1, n2w, n2b, bf16_out=y2b, want_fp32=False, pf=_prefetch("ln2_fwd", w2))
         gemm_bf16(y2b, weight_bf16(w1), M, mlp, hid, Cb=ab, bias=b1, act=1, pre=u)
         if not train:
             u = m1 = r1 = m2 = r2 = y1b = y2b = x.new_empty(0)
         x2 = torch.empty(M, hid, **f32)
         if next_ln is not None and not emit_twin:      # (a tapped block writes the bf16 twin of x2 from its own epilogue)
             xn = bf16_like(x)
-            mn, rn = gemm_bf16_ln_fwd(ab, weight_bf16(w2), M, hid, mlp, x2, next_ln[0], next_ln[1], xn, bias=b2, res=x1, ldr=hid)
+            mn, rn = gemm_bf16_ln_fwd(ab, weight_bf16(w2), M, hid, mlp, x2, next_ln[0], next_ln[1], xn, bias=b2, res=x1, ldr=hid,
+                                      pf=_prefetch("ln1_fwd", next_wqkv))
             _stash_ln(x2, next_ln[0], next_ln[1], xn, mn, rn)
         else:
             # emit_twin: this block's output also feeds a skip-path transposed conv that reads bf16 tokens (its GEMM form):
@@ -1411,9 +1442,11 @@ class TransformerBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, n1w, n1b, wqkv, wp, bp, n2w, n2b, w1, b1, w2, b2, B, L, heads, prec, ckpt=False, next_n1w=None, next_n1b=None,
-                emit_twin=False):
+                emit_twin=False, next_wqkv=None, below_w2=None, below_w1=None):
         """next_n1w / next_n1b: weight and bias of the LayerNorm the NEXT block starts with (not differentiated here: that block
-        owns its backward) -- its forward is formed by this block's last kernel"""
+        owns its backward) -- its forward is formed by this block's last kernel.  next_wqkv, below_w2 / below_w1 (detached, prefetch
+        only): the qkv weight of the next block, read ahead by that kernel, and linear2 / linear1 of the block BELOW, whose
+        backward starts with those two GEMMs right after this block's last backward launch"""
         _require_gpu(x)
         xc = x.contiguous()
         if xc is not x and hasattr(x, "_unetr_ln"):
@@ -1421,7 +1454,8 @@ class TransformerBlockFn(torch.autograd.Function):
         x = xc
         train = any(ctx.needs_input_grad[:12])
         x2, acts, twins = _tblock_forward(x, n1w, n1b, wqkv, wp, bp, n2w, n2b, w1, b1, w2, b2, B, L, heads, prec,
-                                          train and not ckpt, None if next_n1w is None else (next_n1w, next_n1b), bool(emit_twin))
+                                          train and not ckpt, None if next_n1w is None else (next_n1w, next_n1b), bool(emit_twin), next_wqkv)
+        ctx.below = (below_w2, below_w1)
         ctx.ckpt = bool(ckpt) and train
         if ctx.ckpt:
             acts, twins = (), None
@@ -1462,7 +1496,8 @@ class TransformerBlockFn(torch.autograd.Function):
         db1 = colsum_or_defer(dub if fast else du, M, mlp, mlp, b1)
         if fast:
             dx1b = bf16_like(x)
-            dx1, dn2w, dn2b = gemm_ln_bwd_params(dub, weight_bf16(w1), M, hid, mlp, x1, n2w, n2b, m2, r2, dres=dx2, dx_bf16=dx1b)
+            dx1, dn2w, dn2b = gemm_ln_bwd_params(dub, weight_bf16(w1), M, hid, mlp, x1, n2w, n2b, m2, r2, dres=dx2, dx_bf16=dx1b,
+                                                 pf=_prefetch("ln2_bwd", wp))
         else:
             dx1b = None
             if prec == _capi.PREC_BF16X3 and ln_ride_enabled() and x3_ride_ok(M, hid, mlp):
@@ -1485,14 +1520,15 @@ class TransformerBlockFn(torch.autograd.Function):
         dbp = colsum_or_defer(dx1, M, hid, hid, bp)
         if b16att:
             dqkv = None
-            dqkvb = attention_bf16_bwd(qkv, attb, dattb, lse, B, L, heads, dh)
+            dqkvb = attention_bf16_bwd(qkv, attb, dattb, lse, B, L, heads, dh, pf=_prefetch("attn_bwd", wqkv))
         else:
             dqkvb = torch.empty(M, 3 * hid, dtype=torch.bfloat16, device=x.device) if fast else None
             dqkv = attention_bwd(qkv, att, datt, lse, B, L, heads, dh, prec, dqkv_bf16=dqkvb)
         dwqkv = wgrad_or_defer(dqkv, y1, prec, wqkv, dqkvb, y1b)
         if fast:
             dxb = bf16_like(x)
-            dx, dn1w, dn1b = gemm_ln_bwd_params(dqkvb, weight_bf16(wqkv), M, hid, 3 * hid, x, n1w, n1b, m1, r1, dres=dx1, dx_bf16=dxb)
+            dx, dn1w, dn1b = gemm_ln_bwd_params(dqkvb, weight_bf16(wqkv), M, hid, 3 * hid, x, n1w, n1b, m1, r1, dres=dx1, dx_bf16=dxb,
+                                                pf=_prefetch("ln1_bwd", *ctx.below))
         else:
             dxb = None
             if prec == _capi.PREC_BF16X3 and ln_ride_enabled() and x3_ride_ok(M, hid, 3 * hid):
@@ -1502,12 +1538,14 @@ class TransformerBlockFn(torch.autograd.Function):
                 dx, dn1w, dn1b = layernorm_bwd_params(dy1, x, n1w, n1b, m1, r1, dres=dx1, dx_bf16=dxb)
         if fast:
             _attach_twin(dx, dxb)      # the block below picks its bf16 operand up from here (functional._twin)
-        return (dx, dn1w, dn1b, dwqkv, dwp, dbp, dn2w, dn2b, dw1, db1, dw2, db2, None, None, None, None, None, None, None, None)
+        return (dx, dn1w, dn1b, dwqkv, dwp, dbp, dn2w, dn2b, dw1, db1, dw2, db2) + (None,) * 11
 
 
 class LayerNormFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b, twin=False):
+    def forward(ctx, x, w, b, twin=False, below_w2=None, below_w1=None):
+        """below_w2 / below_w1 (detached, prefetch only): linear2 / linear1 of the transformer block whose backward follows this
+        LayerNorm's (TransformerBlockFn.forward)"""
         _require_gpu(x)
         x = x.contiguous()
         yb = bf16_like(x) if twin else None       # (twin: decoder5's transposed conv reads bf16 tokens in its GEMM form)
@@ -1516,16 +1554,17 @@ class LayerNormFn(torch.autograd.Function):
             _attach_twin(y, yb)
         ctx.save_for_backward(x, w, mean, rstd, b)
         ctx.twin = bool(twin)
+        ctx.below = (below_w2, below_w1) if twin else (None, None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w, mean, rstd, b = ctx.saved_tensors
         dxb = bf16_like(x) if ctx.twin else None    # bf16 operand for the last transformer block's backward GEMMs
-        dx, dw, db = layernorm_bwd_params(dy.contiguous(), x, w, b, mean, rstd, dx_bf16=dxb)
+        dx, dw, db = layernorm_bwd_params(dy.contiguous(), x, w, b, mean, rstd, dx_bf16=dxb, pf=_prefetch("ln1_bwd", *ctx.below))
         if dxb is not None:
             _attach_twin(dx, dxb)
-        return dx, dw, db, None
+        return dx, dw, db, None, None, None
 
 
 # ------------------------------------------------------------------------------ conv-side building blocks

@@ -348,7 +348,11 @@ class UNETR(nn.Module):
                 blk.norm2.weight, blk.norm2.bias, blk.mlp.linear1.weight, blk.mlp.linear1.bias, blk.mlp.linear2.weight,
                 blk.mlp.linear2.bias, B, L, self.num_heads, prec, ckpt,
                 None if nxt is None else nxt.weight.detach(), None if nxt is None else nxt.bias.detach(),
-                i in taps)                      # (a tapped block's last GEMM also writes the bf16 tokens the transposed conv reads)
+                i in taps,                      # (a tapped block's last GEMM also writes the bf16 tokens the transposed conv reads)
+                # prefetch riders (bf16 path): the next block's qkv weight, and linear2 / linear1 of the block below
+                self.vit.blocks[i + 1].attn.qkv.weight.detach() if b16 and i + 1 < nblk else None,
+                self.vit.blocks[i - 1].mlp.linear2.weight.detach() if b16 and i > 0 else None,
+                self.vit.blocks[i - 1].mlp.linear1.weight.detach() if b16 and i > 0 else None)
             k = self._pass_of_block(i) - 1      # staged mode: index of the pass that runs block i's backward
             if i in taps:
                 # two consumers: the next block takes alias `xa`, the skip path alias `xb`; TapFn's backward forms the sum of
@@ -361,8 +365,9 @@ class UNETR(nn.Module):
                 if (i + 1) in starts:
                     x = cut(x, k)
                 hidden_states_out.append(x)
-        x = Fn.LayerNormFn.apply(x, self.vit.norm.weight, self.vit.norm.bias,
-                                 Fn._bf16_path(prec, self.hidden_size, self.vit.blocks[0].mlp.linear1.weight.shape[0]))
+        x = Fn.LayerNormFn.apply(x, self.vit.norm.weight, self.vit.norm.bias, b16,
+                                 self.vit.blocks[-1].mlp.linear2.weight.detach() if b16 else None,
+                                 self.vit.blocks[-1].mlp.linear1.weight.detach() if b16 else None)
         x = cut(x, 0)
         # every skip tensor is produced straight into the second half of the decoder's concatenation buffer (to_cat)
         enc1 = Fn.ResBlockFn.apply(Fn.to_channels_last(x_in), *self._res_w(self.encoder1.layer), prec, True)

@@ -169,6 +169,24 @@ int unetr_attention_bf16_fwd(const void* qkv, float* out, void* out_bf16, float*
 int unetr_attention_bf16_bwd(const void* qkv, const void* out_bf16, const void* dout_bf16, const float* lse, float* dqkv,
                              void* dqkv_bf16, float* delta, int B, int L, int heads, int dh, float scale, void* stream);
 
+/* ---- prefetch rider: weight bytes for the NEXT launch(es), read by spare workgroups of a small launch ---------------------------
+ * The ViT Linear GEMMs at a few hundred token rows are one round of workgroups whose first K stages wait on HBM: their weights are
+ * used once per pass and never survive in the Infinity Cache until the next use.  The launch just before such a GEMM (a LayerNorm,
+ * the attention core) leaves most of the chip idle; the *_pf entry points below run the same kernels with extra workgroups, placed
+ * after the work blocks, that only read up to two byte ranges [ptr[i], ptr[i] + bytes[i]) with plain 16-byte loads, so those lines
+ * are cache hits for the following GEMM(s).  A rider writes nothing and takes no part in the work blocks' barriers or
+ * reductions: results are bit-identical and workspaces are sized as without it.  Only whole 16-byte units inside a range are
+ * read (ragged ends are skipped); ptr == NULL or bytes < 16 drops that range; pf == NULL or two empty ranges launch exactly the
+ * grid of the plain entry point.  Ranges must be readable device memory for the duration of the launch.
+ * (These entry points are additions: no existing signature moved, so UNETR_ABI_VERSION stays where it was -- a library built
+ * before them lacks the symbols and is refused at load for that.) */
+typedef struct { const void* ptr[2]; size_t bytes[2]; } unetr_prefetch;
+int unetr_attention_bf16_fwd_pf(const void* qkv, float* out, void* out_bf16, float* lse, int B, int L, int heads, int dh,
+                                float scale, void* stream, const unetr_prefetch* pf);
+int unetr_attention_bf16_bwd_pf(const void* qkv, const void* out_bf16, const void* dout_bf16, const float* lse, float* dqkv,
+                                void* dqkv_bf16, float* delta, int B, int L, int heads, int dh, float scale, void* stream,
+                                const unetr_prefetch* pf);
+
 /* The small transposed convs (Cin a multiple of 64, bf16 mode) run as plain unetr_gemm_bf16 calls on torch's own weight
  * matrix [Cin, Cout*8]; these two move between the GEMM-side matrix t / g [M, Cout*8] (column = co*8 + tap) and the
  * voxel-major tensor y / dy [B, 2D, 2H, 2W, Cout] (pitch ldy): the pixel shuffle that is left of the "transposed conv". */
@@ -189,6 +207,12 @@ int unetr_layernorm_bwd(const float* dy, const float* x, const float* gamma, con
                         const float* rstd, float* dx, void* dx_bf16 /* optional bf16 copy of dx, or NULL */,
                         const float* dres /* optional, added to dx */, float* dgamma, float* dbeta,
                         int M, int H, float* ws, size_t ws_bytes, void* stream);
+/* the same two launches carrying a prefetch rider (unetr_prefetch above; pf may be NULL) */
+int unetr_layernorm_fwd_pf(const float* x, const float* gamma, const float* beta, float* y, void* y_bf16,
+                           float* mean, float* rstd, int M, int H, float eps, void* stream, const unetr_prefetch* pf);
+int unetr_layernorm_bwd_pf(const float* dy, const float* x, const float* gamma, const float* mean,
+                           const float* rstd, float* dx, void* dx_bf16, const float* dres, float* dgamma, float* dbeta,
+                           int M, int H, float* ws, size_t ws_bytes, void* stream, const unetr_prefetch* pf);
 
 /* nn.LayerNorm backward (norm1 / norm2 of MONAI TransformerBlock) applied to dy = A . B, the data gradient of the Linear layer
  * that consumed the LayerNorm output (SABlock.qkv / MLPBlock.linear1): when that GEMM is cut into K slabs the LayerNorm kernel
@@ -207,6 +231,14 @@ int unetr_gemm_bf16_ln_bwd(const unetr_gemm_bf16_desc* d, const void* A, const v
 int unetr_gemm_bf16_ln_fwd(const unetr_gemm_bf16_desc* d, const void* A, const void* B, float* C,
                            const float* gamma, const float* beta, float eps, float* y, void* y_bf16, float* mean, float* rstd,
                            float* ws, size_t ws_bytes, void* stream);
+/* both LayerNorm-riding forms with a prefetch rider on their LayerNorm launch (pf may be NULL) */
+int unetr_gemm_bf16_ln_bwd_pf(const unetr_gemm_bf16_desc* d, const void* A, const void* B, float* C,
+                              const float* x, const float* gamma, const float* mean, const float* rstd,
+                              float* dx, void* dx_bf16, const float* dres, float* dgamma, float* dbeta,
+                              float* ln_ws, size_t ln_ws_bytes, float* ws, size_t ws_bytes, void* stream, const unetr_prefetch* pf);
+int unetr_gemm_bf16_ln_fwd_pf(const unetr_gemm_bf16_desc* d, const void* A, const void* B, float* C,
+                              const float* gamma, const float* beta, float eps, float* y, void* y_bf16, float* mean, float* rstd,
+                              float* ws, size_t ws_bytes, void* stream, const unetr_prefetch* pf);
 
 /* ---- multi-head self-attention core (MONAI SABlock.forward between qkv and out_proj) ----------------
  * qkv: [B*L, 3*Hd] with feature = which*Hd + head*dh + j;  out: [B*L, Hd] ("b h l d -> b l (h d)");

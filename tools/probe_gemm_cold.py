@@ -1,6 +1,9 @@
 """ViT GEMM shapes at batch 2 with COLD weights: every launch of the timed chain reads a different copy of the weight matrix
 (enough copies to exceed L2 + Infinity Cache), as the real step does -- tools/probe_encoder.py re-reads one warm matrix.
-Rows: tile (UNETR_GEMM_CFG); us per launch inside a hipGraph chain."""
+Rows: tile (UNETR_GEMM_CFG); us per launch inside a hipGraph chain.
+"ln+cold" / "ln+rider": the cold chain with a LayerNorm launch (432 x 768, the step's host kernel) in front of every GEMM, without
+and with the prefetch rider for that GEMM's weight copy (unetr_prefetch); us per (LayerNorm, GEMM) pair, so the difference of the
+two is what a rider gains or costs, host and GEMM together.  PROBE_RIDER=0 skips them."""
 import importlib
 import os
 import sys
@@ -64,6 +67,23 @@ wkey = {"fwd qkv": "qkv", "fwd proj": "p", "fwd mlp1": "w1", "fwd mlp2": "w2", "
 hq = hb[:, :3 * H].contiguous()
 shapes["dgrad dqkv N=768  K=2304"] = lambda w: Fn.gemm_bf16(hq, w, M, H, 3 * H, b_kn=True, C=o768)
 cfgs = os.environ.get("PROBE_CFGS", "0,6464,6432,3264").split(",")
+RIDER = os.environ.get("PROBE_RIDER", "1") != "0"
+lnw, lnb, lny = torch.ones(H, device=dev), torch.zeros(H, device=dev), torch.empty(M, H, device=dev, dtype=torch.bfloat16)
+
+
+def ln_host(w, rider):
+    pf = None
+    if rider:
+        pf = pkg._capi.Prefetch()
+        pf.ptr[0], pf.bytes[0] = w.data_ptr(), w.numel() * 2
+    Fn.layernorm_fwd(x, lnw, lnb, bf16_out=lny, want_fp32=False, pf=pf)
+
+
+def pair(fn, w, rider):
+    ln_host(w, rider)
+    fn(w)
+
+
 for name, fn in shapes.items():
     ws = W[wkey[" ".join(name.split()[:2])]]
     for cfg in cfgs:
@@ -71,6 +91,11 @@ for name, fn in shapes.items():
         try:
             cold = timeit([lambda w=w: fn(w) for w in ws])
             warm = timeit([lambda: fn(ws[0])] * 24)
-            print(f"{name}  cfg {cfg:>5s}: cold {cold:6.2f} us   warm {warm:6.2f} us", flush=True)
+            tail = ""
+            if RIDER:
+                plain = timeit([lambda w=w: pair(fn, w, False) for w in ws])       # (per closure = per pair)
+                ride = timeit([lambda w=w: pair(fn, w, True) for w in ws])
+                tail = f"   ln+cold {plain:6.2f} us   ln+rider {ride:6.2f} us   rider gain {plain - ride:5.2f} us"
+            print(f"{name}  cfg {cfg:>5s}: cold {cold:6.2f} us   warm {warm:6.2f} us{tail}", flush=True)
         except Exception as e:
             print(f"{name}  cfg {cfg:>5s}: {type(e).__name__} {str(e)[:60]}", flush=True)
