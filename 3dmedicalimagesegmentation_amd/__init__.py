@@ -7,7 +7,7 @@ The directory name starts with a digit, so import it with
 from .unetr import UNETR, UNETRLogits, default_precision  # noqa: F401
 from .losses import DiceCELoss, ranking_loss  # noqa: F401
 from .optim import AdamW  # noqa: F401
-from .inference import DiceMetric, sliding_window_inference  # noqa: F401
+from .inference import DiceMetric, SlidingWindowInferer, sliding_window_inference  # noqa: F401
 from .metrics import ConfusionMatrixMetric, HausdorffDistanceMetric  # noqa: F401
 from .train_step import TrainStep  # noqa: F401
 from .augment import RandCropAugment, VolumeCache  # noqa: F401
@@ -16,5 +16,5 @@ from .functional import invalidate_weight_shadows  # noqa: F401
 from . import _capi, augment, ddp, functional, inference, metrics, preprocess, train_step  # noqa: F401
 
 __all__ = ["UNETR", "UNETRLogits", "DiceCELoss", "ranking_loss", "AdamW", "default_precision", "sliding_window_inference",
-           "DiceMetric", "ConfusionMatrixMetric", "HausdorffDistanceMetric", "TrainStep", "invalidate_weight_shadows",
+           "SlidingWindowInferer", "DiceMetric", "ConfusionMatrixMetric", "HausdorffDistanceMetric", "TrainStep", "invalidate_weight_shadows",
            "VolumeCache", "RandCropAugment", "resample_orient"]

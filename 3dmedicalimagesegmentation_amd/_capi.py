@@ -81,6 +81,16 @@ class AugDesc(ctypes.Structure):
                 ("shift_lo", c_double), ("shift_hi", c_double), ("seed", ctypes.c_uint64)]
 
 
+class SwVolume(ctypes.Structure):
+    _fields_ = [("in_", c_void_p), ("out", c_void_p), ("count", c_void_p), ("table", c_void_p),
+                ("B", c_int), ("Cin", c_int), ("C", c_int), ("Di", c_int), ("Hi", c_int), ("Wi", c_int),
+                ("D", c_int), ("H", c_int), ("W", c_int), ("pz", c_int), ("py", c_int), ("px", c_int),
+                ("cval", c_float), ("rows", c_int), ("cursor", c_int)]
+
+
+SW_MAX_BATCH = 16                      # = UNETR_SW_MAX_BATCH
+SW_ROW_INTS = 4 + 4 * SW_MAX_BATCH     # = UNETR_SW_ROW_INTS
+
 P = c_void_p
 _SIGNATURES = {
     "unetr_abi_version": [],
@@ -161,6 +171,10 @@ _SIGNATURES = {
     "unetr_sw_accumulate": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
     "unetr_sw_finalize": [P, P, c_int, c_int, c_long, P],
     "unetr_dice_counts": [P, P, c_int, c_int, c_long, c_int, P, P, c_size_t, P],
+    "unetr_sw_advance": [P, P],
+    "unetr_sw_gather_batch": [P, P, c_int, c_int, c_int, c_int, c_int, P],
+    "unetr_sw_accumulate_batch": [P, P, P, c_int, c_int, c_int, c_int, c_int, P],
+    "unetr_sw_finalize_post": [P, P, P, c_int, c_int, c_long, c_int, P],
     "unetr_hausdorff": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, P, P, c_size_t, c_int, P],
     "unetr_aug_prep": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, P, P, P],
     "unetr_aug_crop": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P],

@@ -126,3 +126,238 @@ extern "C" int unetr_dice_counts(const float* pred, const float* y, int B, int C
     hipLaunchKernelGGL(dice_counts_final_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, ws, n, B, C, nchunk, counts);
     return unetr_check_launch();
 }
+
+// ---- batched, table-driven sliding-window kernels (SlidingWindowInferer) ---------------------------------------------------
+// One forward batch = one row of a device-resident window table; the volume (pointers, extents, padding) is described by a
+// device-resident unetr_sw_volume, so none of these launches carries a volume size or a window position in its arguments and a
+// hipGraph of advance -> gather -> forward -> accumulate serves every volume.  All three are HBM-bound streaming passes: four
+// x-neighbours per thread, 16-byte accesses wherever the address is 16-byte aligned, plain vector stores, no atomics.
+namespace {
+
+constexpr int SWROW = UNETR_SW_ROW_INTS;
+
+__device__ __forceinline__ bool sw_al16(const void* p) { return ((size_t)p & 15) == 0; }
+
+template <int NV>
+__device__ __forceinline__ void sw_ld(float (&r)[NV], const float* p) {
+    if (NV == 4 && sw_al16(p)) {
+        const float4 t = *reinterpret_cast<const float4*>(p);
+        r[0] = t.x; r[1 % NV] = t.y; r[2 % NV] = t.z; r[3 % NV] = t.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) r[k] = p[k];
+    }
+}
+
+template <int NV>
+__device__ __forceinline__ void sw_st(float* p, const float (&r)[NV]) {
+    if (NV == 4 && sw_al16(p)) {
+        *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1 % NV], r[2 % NV], r[3 % NV]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) p[k] = r[k];
+    }
+}
+
+__global__ void sw_advance_kernel(unetr_sw_volume* vol) { vol->cursor = vol->cursor + 1; }
+
+// the row in flight, or nullptr-like failure (uniform per launch): loads the row into LDS
+__device__ __forceinline__ bool sw_load_row(const unetr_sw_volume* vol, int* row) {
+    const int cur = vol->cursor;
+    if (cur < 0 || cur >= vol->rows) return false;
+    if (threadIdx.x < SWROW) row[threadIdx.x] = vol->table[(long)cur * SWROW + threadIdx.x];
+    __syncthreads();
+    return true;
+}
+
+// a slot is used only when its window lies inside the padded volume of an existing batch item (a bad table writes nothing)
+__device__ __forceinline__ bool sw_slot_ok(const unetr_sw_volume* vol, const int* row, int i, int rz, int ry, int rx) {
+    const int b = row[4 + 4 * i], z = row[5 + 4 * i], y = row[6 + 4 * i], x = row[7 + 4 * i];
+    return b >= 0 && b < vol->B && z >= 0 && y >= 0 && x >= 0 && z + rz <= vol->D && y + ry <= vol->H && x + rx <= vol->W;
+}
+
+// dst[j, c, z, y, x] = in[b_j, c, z_j + z - pz, y_j + y - py, x_j + x - px], cval outside the stored volume (and in unused slots)
+template <int NV>
+__global__ void __launch_bounds__(256)
+sw_gather_batch_kernel(const unetr_sw_volume* __restrict__ vol, float* __restrict__ dst, int n, int Cin, int rz, int ry, int rx) {
+    __shared__ int row[SWROW];
+    if (vol->Cin != Cin || !sw_load_row(vol, row)) return;
+    const int j = blockIdx.y;
+    const int xq = rx / NV;
+    const long rv = (long)rz * ry * rx, quads = (long)Cin * rz * ry * xq;
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= quads) return;
+    const int x = (int)(q % xq) * NV, y = (int)((q / xq) % ry), z = (int)((q / ((long)xq * ry)) % rz), c = (int)(q / ((long)xq * ry * rz));
+    const float cval = vol->cval;
+    float r[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) r[k] = cval;
+    if (j < row[0] && sw_slot_ok(vol, row, j, rz, ry, rx)) {
+        const int Di = vol->Di, Hi = vol->Hi, Wi = vol->Wi;
+        const int Z = row[5 + 4 * j] + z - vol->pz, Y = row[6 + 4 * j] + y - vol->py, X = row[7 + 4 * j] + x - vol->px;
+        if (Z >= 0 && Z < Di && Y >= 0 && Y < Hi) {
+            const float* src = vol->in + (((long)row[4 + 4 * j] * Cin + c) * Di + Z) * (long)Hi * Wi + (long)Y * Wi;
+            if (X >= 0 && X + NV <= Wi) {
+                sw_ld<NV>(r, src + X);
+            } else {
+#pragma unroll
+                for (int k = 0; k < NV; ++k)
+                    if (X + k >= 0 && X + k < Wi) r[k] = src[X + k];
+            }
+        }
+    }
+    sw_st<NV>(dst + ((long)j * Cin + c) * rv + ((long)z * ry + y) * rx + x, r);
+}
+
+// NV x-neighbours at (Z, Y, X..) of one batch item, covered by exactly the windows in `mask`: add those windows in slot order.
+// The per-window update is the one sw_accumulate_kernel performs (out = fma(w, seg, out); count = count + w), so a voxel
+// receives the same fp32 operations in the same order as from one unetr_sw_accumulate launch per window.
+template <int NV>
+__device__ __forceinline__ void sw_blend(const int* row, unsigned mask, int Z, int Y, int X, const float* __restrict__ seg,
+                                         const float* __restrict__ imp, float* __restrict__ out, float* __restrict__ count,
+                                         int C, int ry, int rx, long rv, int H, int W, long V) {
+    const long o = ((long)Z * H + Y) * W + X;
+    float cnt[NV], w[NV], s[NV], acc[NV];
+    sw_ld<NV>(cnt, count + o);
+    for (unsigned m = mask; m; m &= m - 1) {
+        const int i = __ffs(m) - 1;
+        const long li = ((long)(Z - row[5 + 4 * i]) * ry + (Y - row[6 + 4 * i])) * rx + (X - row[7 + 4 * i]);
+        if (imp) sw_ld<NV>(w, imp + li);
+#pragma unroll
+        for (int k = 0; k < NV; ++k) cnt[k] += imp ? w[k] : 1.f;
+    }
+    sw_st<NV>(count + o, cnt);
+    for (int c = 0; c < C; ++c) {
+        float* po = out + (long)c * V + o;
+        sw_ld<NV>(acc, po);
+        for (unsigned m = mask; m; m &= m - 1) {
+            const int i = __ffs(m) - 1;
+            const long li = ((long)(Z - row[5 + 4 * i]) * ry + (Y - row[6 + 4 * i])) * rx + (X - row[7 + 4 * i]);
+            if (imp) sw_ld<NV>(w, imp + li);
+            sw_ld<NV>(s, seg + ((long)i * C + c) * rv + li);
+#pragma unroll
+            for (int k = 0; k < NV; ++k) acc[k] = fmaf(imp ? w[k] : 1.f, s[k], acc[k]);
+        }
+        sw_st<NV>(po, acc);
+    }
+}
+
+// grid (tiles of window voxels, slot j).  The windows of one row overlap, so every output voxel has ONE owner: the thread of the
+// first active slot that covers it.  The owner adds slot j, j+1, ... in order; every other thread leaves the voxel alone.
+template <int NV>
+__global__ void __launch_bounds__(256)
+sw_accumulate_batch_kernel(const unetr_sw_volume* __restrict__ vol, const float* __restrict__ seg, const float* __restrict__ imp,
+                           int n, int C, int rz, int ry, int rx) {
+    __shared__ int row[SWROW];
+    if (vol->C != C || !sw_load_row(vol, row)) return;
+    const int j = blockIdx.y, nact = min(row[0], n);
+    if (j >= nact || !sw_slot_ok(vol, row, j, rz, ry, rx)) return;
+    const int xq = rx / NV;
+    const long rv = (long)rz * ry * rx, quads = (long)rz * ry * xq;
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= quads) return;
+    const int b = row[4 + 4 * j];
+    const int Z = row[5 + 4 * j] + (int)(q / ((long)xq * ry)), Y = row[6 + 4 * j] + (int)((q / xq) % ry), X = row[7 + 4 * j] + (int)(q % xq) * NV;
+    unsigned mk[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) mk[k] = 0u;
+    for (int i = 0; i < nact; ++i) {
+        const int zi = row[5 + 4 * i], yi = row[6 + 4 * i], xi = row[7 + 4 * i];
+        if (row[4 + 4 * i] != b || Z < zi || Z >= zi + rz || Y < yi || Y >= yi + ry || !sw_slot_ok(vol, row, i, rz, ry, rx)) continue;
+#pragma unroll
+        for (int k = 0; k < NV; ++k)
+            if (X + k >= xi && X + k < xi + rx) mk[k] |= 1u << i;
+    }
+    const int H = vol->H, W = vol->W;
+    const long V = (long)vol->D * H * W;
+    float* out = vol->out + (long)b * C * V;
+    float* count = vol->count + (long)b * V;
+    bool same = true;
+#pragma unroll
+    for (int k = 1; k < NV; ++k) same = same && mk[k] == mk[0];
+    if (NV > 1 && same) {
+        if (__ffs(mk[0]) - 1 == j) sw_blend<NV>(row, mk[0], Z, Y, X, seg, imp, out, count, C, ry, rx, rv, H, W, V);
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+        if (__ffs(mk[k]) - 1 == j) sw_blend<1>(row, mk[k], Z, Y, X + k, seg, imp, out, count, C, ry, rx, rv, H, W, V);
+}
+
+// v = out / count, then per voxel: post 0 stores v; 1 stores one_hot(argmax_c v) over out; 2 stores argmax_c v (as float) into
+// dst [B, V]; 3 stores (v >= 0) -- sigmoid(v) >= 0.5 -- over out.  argmax takes the first maximal channel (torch.argmax).
+template <int NV>
+__global__ void __launch_bounds__(256)
+sw_finalize_post_kernel(float* __restrict__ out, const float* __restrict__ count, float* __restrict__ dst, int C, long V, int post) {
+    const long v = ((long)blockIdx.x * 256 + threadIdx.x) * NV;
+    if (v >= V) return;
+    const int b = blockIdx.y;
+    float cn[NV], a[NV], mx[NV];
+    int am[NV];
+    sw_ld<NV>(cn, count + (long)b * V + v);
+    float* ob = out + (long)b * C * V + v;
+    for (int c = 0; c < C; ++c) {
+        sw_ld<NV>(a, ob + (long)c * V);
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            a[k] = a[k] / cn[k];
+            if (c == 0 || a[k] > mx[k]) { mx[k] = a[k]; am[k] = c; }
+            if (post == 3) a[k] = a[k] >= 0.f ? 1.f : 0.f;
+        }
+        if (post == 0 || post == 3) sw_st<NV>(ob + (long)c * V, a);
+    }
+    if (post == 1) {
+        for (int c = 0; c < C; ++c) {
+#pragma unroll
+            for (int k = 0; k < NV; ++k) a[k] = am[k] == c ? 1.f : 0.f;
+            sw_st<NV>(ob + (long)c * V, a);
+        }
+    } else if (post == 2) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) a[k] = (float)am[k];
+        sw_st<NV>(dst + (long)b * V + v, a);
+    }
+}
+
+}  // namespace
+
+extern "C" int unetr_sw_advance(unetr_sw_volume* vol, void* stream) {
+    if (!vol) return UNETR_ERR_ARG;
+    hipLaunchKernelGGL(sw_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, vol);
+    return unetr_check_launch();
+}
+
+extern "C" int unetr_sw_gather_batch(const unetr_sw_volume* vol, float* dst, int n, int Cin, int rz, int ry, int rx, void* stream) {
+    if (!vol || !dst || Cin <= 0 || rz <= 0 || ry <= 0 || rx <= 0) return UNETR_ERR_ARG;
+    if (n < 1 || n > UNETR_SW_MAX_BATCH) return UNETR_ERR_UNSUPPORTED;
+    const bool v4 = rx % 4 == 0 && ((size_t)dst & 15) == 0;
+    const long quads = (long)Cin * rz * ry * (rx / (v4 ? 4 : 1));
+    const dim3 grid(cdiv(quads, 256), n);
+    if (v4) hipLaunchKernelGGL(sw_gather_batch_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, vol, dst, n, Cin, rz, ry, rx);
+    else hipLaunchKernelGGL(sw_gather_batch_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, vol, dst, n, Cin, rz, ry, rx);
+    return unetr_check_launch();
+}
+
+extern "C" int unetr_sw_accumulate_batch(const unetr_sw_volume* vol, const float* seg, const float* importance, int n, int C,
+                                         int rz, int ry, int rx, void* stream) {
+    if (!vol || !seg || C <= 0 || rz <= 0 || ry <= 0 || rx <= 0) return UNETR_ERR_ARG;
+    if (n < 1 || n > UNETR_SW_MAX_BATCH) return UNETR_ERR_UNSUPPORTED;
+    const bool v4 = rx % 4 == 0 && ((size_t)seg & 15) == 0 && ((size_t)importance & 15) == 0;
+    const long quads = (long)rz * ry * (rx / (v4 ? 4 : 1));
+    const dim3 grid(cdiv(quads, 256), n);
+    hipStream_t st = (hipStream_t)stream;
+    if (v4) hipLaunchKernelGGL(sw_accumulate_batch_kernel<4>, grid, dim3(256), 0, st, vol, seg, importance, n, C, rz, ry, rx);
+    else hipLaunchKernelGGL(sw_accumulate_batch_kernel<1>, grid, dim3(256), 0, st, vol, seg, importance, n, C, rz, ry, rx);
+    return unetr_check_launch();
+}
+
+extern "C" int unetr_sw_finalize_post(float* out, const float* count, float* dst, int B, int C, long V, int post, void* stream) {
+    if (!out || !count || B <= 0 || B > 65535 || C <= 0 || V <= 0 || post < 0 || post > 3 || (post == 2 && !dst)) return UNETR_ERR_ARG;
+    if ((post == 1 || post == 2) && C > DMAXC) return UNETR_ERR_UNSUPPORTED;
+    const bool v4 = V % 4 == 0 && ((size_t)out & 15) == 0 && ((size_t)count & 15) == 0 && ((size_t)dst & 15) == 0;
+    const dim3 grid(cdiv(cdiv(V, v4 ? 4 : 1), 256), B);
+    hipStream_t st = (hipStream_t)stream;
+    if (v4) hipLaunchKernelGGL(sw_finalize_post_kernel<4>, grid, dim3(256), 0, st, out, count, dst, C, V, post);
+    else hipLaunchKernelGGL(sw_finalize_post_kernel<1>, grid, dim3(256), 0, st, out, count, dst, C, V, post);
+    return unetr_check_launch();
+}

@@ -423,7 +423,17 @@ def invalidate_weight_shadows():
     copies are optimizer-maintained (this package's AdamW has stepped): such a write changes neither the version counter
     nor the storage address, so nothing else can notice it.  Everything torch can see is handled automatically: in-place
     ops on the parameter, torch optimizers, ``load_state_dict``, re-pointed ``.data``, and -- for copies no optimizer of
-    this package maintains -- any change at all between two forward passes (``begin_forward``)."""
+    this package maintains -- any change at all between two forward passes (``begin_forward``).
+
+    Captured inference graphs (inference.SlidingWindowInferer) follow the same contract.  A forward captured under no_grad
+    reads derived copies in two ways: a copy that no optimizer of this package maintained at capture time is re-derived INSIDE
+    the graph (weight_bf16 / conv_pack_get never trust an epoch under capture), so every replay is current; a copy that was
+    optimizer-maintained at capture time -- and the bf16x3 word shadow -- is read as it is.  Before the first replay of every
+    call the inferer therefore starts a new weight epoch and walks the as-is copies through these same getters eagerly: nothing
+    happens to a copy that is still maintained and in step, a stale one (version counter, address, or this function) is
+    re-derived into the same buffer, which the graph then reads.  If a parameter, a derived buffer or the scratch workspace has
+    moved since capture, the graph is captured again.  A live TrainStep on the same model needs nothing extra: its optimizer
+    kernels rewrite the buffers the inference graph reads."""
     _WEIGHT_EPOCH[0] += 1
     for ent in _SHADOW.values():
         ent[1] = -1

@@ -8,13 +8,29 @@
 The window forward is the HIP hot path (run under torch.no_grad); blending and the Dice sums are the HIP kernels of
 csrc/inference.hip.  Window geometry (scan interval, dense patch starts, padding of small volumes) is host integer logic
 restated from MONAI 0.6.0 (monai/inferers/utils.py, monai/data/utils.py::dense_patch_slices).  No CPU fallback.
+
+``SlidingWindowInferer`` (monai.inferers.SlidingWindowInferer's constructor + ``use_graph``, ``__call__(inputs, network,
+post=None)``) is the same computation without per-window host work: the windows of a call are planned once into a device-resident
+table (rows of ``sw_batch_size`` windows), and each row is advance -> gather -> forward -> accumulate over that table
+(unetr_sw_gather_batch / unetr_sw_accumulate_batch: one launch each per row).  For this package's UNETR the row is captured
+into one hipGraph per (model, precision, roi, batch size, input channels) and replayed for every row of every volume: volume
+sizes live in a device-side descriptor, not in kernel arguments.  ``post`` fuses AsDiscrete / Activations into the finalize pass.
+Both routes forward the same window batches in the same order and blend with the same fp32 operations as the per-window
+function, so their results are bit-identical to it.
+
+``mode="gaussian"``: MONAI is not installed where this was written, so the Gaussian importance map is RESTATED from memory of
+MONAI 0.6.0 (monai/data/utils.py::compute_importance_map + monai/networks/layers/simplelayers.py::GaussianFilter /
+convutils.gaussian_1d(approx="erf")) -- recalled, not pinned against the library; tests/inference_ref.py holds the same map
+by real separable filtering.
 """
 import math
+import weakref
 from typing import Callable, Sequence, Union
 
 import torch
 import torch.nn.functional as F
 
+from . import _capi
 from . import functional as Fn
 from ._capi import call
 
@@ -49,6 +65,58 @@ def _dense_patch_starts(image_size, patch_size, scan_interval):
     return [(z, y, x) for z in starts[0] for y in starts[1] for x in starts[2]]
 
 
+def _check_mode(mode):
+    if mode not in ("constant", "gaussian"):
+        raise ValueError(f"{mode!r} is not a valid BlendMode")          # what monai.utils.BlendMode(mode) raises
+
+
+def _gaussian_1d(sigma):
+    """monai.networks.layers.convutils.gaussian_1d(sigma, truncated=4.0, approx="erf", normalize=False), fp32"""
+    tail = int(max(float(sigma) * 4.0, 0.5) + 0.5)
+    x = torch.arange(-tail, tail + 1, dtype=torch.float32)
+    t = 0.70710678 / abs(float(sigma))
+    return (0.5 * ((t * (x + 0.5)).erf() - (t * (x - 0.5)).erf())).clamp(min=0), tail
+
+
+def importance_map(roi_size, mode="constant", sigma_scale=0.125):
+    """monai.data.utils.compute_importance_map (0.6.0) as a CPU fp32 tensor [rz, ry, rx].  "gaussian": a unit impulse at roi // 2
+    filtered along z, y, x by the erf-approximated Gaussian of sigma = roi * sigma_scale (zero padding), divided by its maximum,
+    clamped from below to its smallest non-zero entry.  Filtering an impulse with a separable kernel has a closed form -- the 1-D
+    kernels read at offsets i - roi // 2 (zero beyond the tail), multiplied in filtering order (kz * ky) * kx -- which is what is
+    evaluated here, with torch CPU fp32 ops."""
+    _check_mode(mode)
+    roi = [int(r) for r in roi_size]
+    if mode == "constant":
+        return torch.ones(roi, dtype=torch.float32)
+    sig = list(sigma_scale) if isinstance(sigma_scale, (tuple, list)) else [sigma_scale] * len(roi)
+    if len(sig) != len(roi):
+        raise ValueError(f"sigma_scale: sequence must have length {len(roi)}, got {len(sig)}.")      # ensure_tuple_rep
+    prof = []
+    for r, sc in zip(roi, sig):
+        k, tail = _gaussian_1d(r * sc)
+        off = torch.arange(r) - r // 2
+        inside = off.abs() <= tail
+        prof.append(torch.where(inside, k[(off + tail).clamp(0, 2 * tail)], torch.zeros((), dtype=torch.float32)))
+    m = (prof[0][:, None, None] * prof[1][None, :, None]) * prof[2][None, None, :]
+    m = m / m.max()
+    return m.clamp(min=m[m != 0].min())
+
+
+_IMP = {}
+
+
+def _device_importance_map(roi, mode, sigma_scale, device):
+    """the importance map on `device` (computed on the host once per (roi, sigma_scale, device)); None for the constant mode"""
+    _check_mode(mode)
+    if mode == "constant":
+        return None
+    key = (tuple(roi), tuple(sigma_scale) if isinstance(sigma_scale, (tuple, list)) else float(sigma_scale), str(device))
+    imp = _IMP.get(key)
+    if imp is None:
+        imp = _IMP[key] = importance_map(roi, mode, sigma_scale).to(device).contiguous()
+    return imp
+
+
 @torch.no_grad()
 def sliding_window_inference(inputs: torch.Tensor, roi_size: Union[Sequence[int], int], sw_batch_size: int,
                              predictor: Callable[..., torch.Tensor], overlap: float = 0.25, mode: str = "constant",
@@ -59,9 +127,7 @@ def sliding_window_inference(inputs: torch.Tensor, roi_size: Union[Sequence[int]
         raise ValueError("3-D volumes [B,C,D,H,W] expected")
     if overlap < 0 or overlap >= 1:
         raise AssertionError("overlap must be >= 0 and < 1.")
-    if mode != "constant":
-        # the reference never passes mode (default "constant"); MONAI's Gaussian importance map is not restated here
-        raise NotImplementedError(f"blending mode {mode!r}: only mode='constant' (the reference's default) is implemented")
+    _check_mode(mode)
     B = inputs.shape[0]
     image_size_ = list(inputs.shape[2:])
     roi = [roi_size] * 3 if isinstance(roi_size, int) else list(roi_size)
@@ -79,7 +145,7 @@ def sliding_window_inference(inputs: torch.Tensor, roi_size: Union[Sequence[int]
     starts = _dense_patch_starts(image_size, roi, interval)
     num_win = len(starts)
     total = num_win * B
-    imp = None                                  # constant importance map (all ones)
+    imp = _device_importance_map(roi, mode, sigma_scale, inputs.device)      # None: constant importance map (all ones)
     D, H, W = image_size
     V = D * H * W
     out = count = None
@@ -169,3 +235,324 @@ class DiceMetric:
 
     def reset(self):
         self._buf = []
+
+
+# ---- SlidingWindowInferer: table-driven rows, captured forward, fused post-processing ------------------------------------------
+_POST = {None: 0, "onehot": 1, "argmax": 2, "sigmoid": 3}
+
+
+def plan_window_table(batch, image_size, roi, overlap, n):
+    """The windows of one call as rows of ``n`` slots, in the order sliding_window_inference visits them (batch item major, then
+    _dense_patch_starts).  Returns (int32 CPU tensor [rows, SW_ROW_INTS] in the layout of include/unetr_hip.h: [active, 0, 0, 0,
+    (b, z, y, x) per slot], list of active counts per row); only the last row may hold fewer than ``n`` windows."""
+    if not 1 <= n <= _capi.SW_MAX_BATCH:
+        raise ValueError(f"sw_batch_size must be in [1, {_capi.SW_MAX_BATCH}], got {n}")
+    starts = _dense_patch_starts(image_size, roi, _scan_interval(image_size, roi, overlap))
+    num_win = len(starts)
+    total = num_win * batch
+    rows = (total + n - 1) // n
+    table = torch.zeros(rows, _capi.SW_ROW_INTS, dtype=torch.int32)
+    flat = [(idx // num_win,) + tuple(starts[idx % num_win]) for idx in range(total)]
+    counts = []
+    for r in range(rows):
+        slots = flat[r * n:(r + 1) * n]
+        counts.append(len(slots))
+        table[r, 0] = len(slots)
+        table[r, 4:4 + 4 * len(slots)] = torch.tensor(slots, dtype=torch.int32).flatten()
+    return table, counts
+
+
+class _CapturedRow:
+    __slots__ = ("graph", "static_in", "seg", "as_is", "derived", "signature", "model")
+
+
+class SlidingWindowInferer:
+    """monai.inferers.SlidingWindowInferer (0.6.0) plus ``use_graph`` and the ``post`` argument of ``__call__``:
+
+        inferer = SlidingWindowInferer(roi_size, sw_batch_size, overlap, mode, sigma_scale, padding_mode, cval, use_graph=True)
+        out = inferer(inputs, network, post=None)
+
+    post=None: the blended logits [B, C, D, H, W] (what sliding_window_inference returns, bit for bit); "onehot":
+    AsDiscrete(argmax=True, to_onehot=True, n_classes=C) of them; "argmax": the class ids as float [B, 1, D, H, W]; "sigmoid":
+    Activations(sigmoid=True) + AsDiscrete(threshold_values=True), i.e. 1.0 where the logit is >= 0.  All three come out of the
+    finalize kernel in the pass that divides by the weight sum.  ``network`` is any callable (a tuple result means its last
+    element).  For this package's UNETR / UNETRLogits with use_graph=True, one row of windows -- advance the device cursor,
+    gather, forward, accumulate -- is ONE hipGraph per (model, precision, roi, batch size, input channels), replayed for every row
+    of every volume size; a call is then a table upload, a descriptor upload, ``rows`` replays and one finalize launch, with no
+    host synchronisation.  A last row with fewer windows runs through a second graph of exactly that batch size, so every route
+    forwards the batch compositions the function forwards.  Anything else runs the same kernels eagerly.
+    ``stats``: captures / recaptures / replays / eager_rows, counted over the inferer's life.
+
+    Weight freshness of a captured forward: see functional.invalidate_weight_shadows (rule for captured inference graphs)."""
+
+    def __init__(self, roi_size, sw_batch_size: int = 1, overlap: float = 0.25, mode: str = "constant", sigma_scale=0.125,
+                 padding_mode: str = "constant", cval: float = 0.0, use_graph: bool = True):
+        _check_mode(mode)
+        if overlap < 0 or overlap >= 1:
+            raise AssertionError("overlap must be >= 0 and < 1.")
+        if not 1 <= int(sw_batch_size) <= _capi.SW_MAX_BATCH:
+            raise ValueError(f"sw_batch_size must be in [1, {_capi.SW_MAX_BATCH}], got {sw_batch_size}")
+        self.roi_size = roi_size
+        self.sw_batch_size = int(sw_batch_size)
+        self.overlap, self.mode, self.sigma_scale = overlap, mode, sigma_scale
+        self.padding_mode, self.cval = padding_mode, float(cval)
+        self.use_graph = bool(use_graph)
+        self.stats = dict(captures=0, recaptures=0, replays=0, eager_rows=0)
+        self._desc = {}        # device index -> uint8 tensor holding the unetr_sw_volume every launch of this inferer reads
+        self._graphs = {}      # (id(model), precision, roi, batch size, Cin, device index) -> _CapturedRow
+        self._inputs = {}      # eager route: (batch size, Cin, roi, device index) -> forward input buffer
+        self._plans = {}
+        self._keep = None      # table / staging of the call in flight
+
+    # ------------------------------------------------------------------------------------------------ host side
+    def _plan(self, B, image_size, roi):
+        key = (B, tuple(image_size), tuple(roi))
+        plan = self._plans.get(key)
+        if plan is None:
+            if len(self._plans) > 64:
+                self._plans.clear()
+            plan = self._plans[key] = plan_window_table(B, image_size, roi, self.overlap, self.sw_batch_size)
+        return plan
+
+    def _desc_of(self, device):
+        d = self._desc.get(device.index)
+        if d is None:
+            import ctypes
+            d = self._desc[device.index] = torch.zeros(ctypes.sizeof(_capi.SwVolume), dtype=torch.uint8, device=device)
+        return d
+
+    def _upload_desc(self, desc, vol):
+        host = torch.frombuffer(bytearray(bytes(vol)), dtype=torch.uint8).pin_memory()
+        desc.copy_(host, non_blocking=True)          # (the pinned block is not reused before the copy has run: caching host allocator)
+
+    # ------------------------------------------------------------------------------------------------ one row
+    @staticmethod
+    def _gather(desc, static_in, roi):
+        s = Fn._stream()
+        call("unetr_sw_advance", desc.data_ptr(), s)
+        call("unetr_sw_gather_batch", desc.data_ptr(), static_in.data_ptr(), static_in.shape[0], static_in.shape[1], *roi, s)
+
+    @staticmethod
+    def _forward(network, static_in, args, kwargs):
+        seg = network(static_in, *args, **kwargs)
+        if isinstance(seg, (tuple, list)):
+            seg = seg[-1]
+        seg = seg.contiguous().float()
+        if seg.dim() != 5 or seg.shape[0] != static_in.shape[0] or tuple(seg.shape[2:]) != tuple(static_in.shape[2:]):
+            raise ValueError(f"network returned {tuple(seg.shape)} for windows {tuple(static_in.shape)}")
+        return seg
+
+    @staticmethod
+    def _accumulate(desc, seg, imp, roi):
+        call("unetr_sw_accumulate_batch", desc.data_ptr(), seg.data_ptr(), imp.data_ptr() if imp is not None else None,
+             seg.shape[0], seg.shape[1], *roi, Fn._stream())
+
+    # ------------------------------------------------------------------------------------------------ capture
+    @staticmethod
+    def _derived_entries(model):
+        """(kind, parameter, table entry, getter arguments) of every derived weight copy registered for the model's parameters"""
+        params = {id(p): p for p in model.parameters()}
+        out = []
+        for pid, p in params.items():
+            ent = Fn._SHADOW.get(pid)
+            if ent is not None and ent[4]() is p:
+                out.append(("bf16", p, ent, ()))
+            ent = Fn._SHADOW_X3.get(pid)
+            if ent is not None and ent[2]() is p:
+                out.append(("x3", p, ent, ()))
+        for key, ent in Fn._PACKS.items():
+            p = params.get(key[0])
+            if p is not None and ent[4]() is p:
+                out.append(("pack", p, ent, (key[1], key[2])))
+        return out
+
+    @staticmethod
+    def _signature(model, device, derived):
+        """every address a captured forward may have baked in: the parameters, the scratch workspace, and the buffers of the
+        derived copies that existed when it was captured (`derived`: (kind, weak parameter, getter arguments), looked up again)"""
+        sig = [p.data_ptr() for p in model.parameters()]
+        sig.append(Fn.workspace(device).data_ptr())
+        for kind, ref, extra in derived:
+            p = ref()
+            ent = None
+            if p is not None:
+                ent = (Fn._SHADOW.get(id(p)) if kind == "bf16" else Fn._SHADOW_X3.get(id(p)) if kind == "x3"
+                       else Fn._PACKS.get((id(p),) + tuple(extra)))
+            sig.append(ent[0].data_ptr() if ent is not None else 0)
+        return tuple(sig)
+
+    @classmethod
+    def _as_is(cls, model):
+        """the derived copies a capture starting now would READ AS THEY ARE (optimizer-maintained, or the word shadow in step with
+        its parameter) instead of re-deriving them inside the graph"""
+        out = []
+        for kind, p, ent, extra in cls._derived_entries(model):
+            if kind == "x3":
+                if ent[1] == p._version and ent[3] == p.data_ptr():
+                    out.append((kind, weakref.ref(p), extra))
+            elif ent[3] and ent[1] == p._version and ent[5] == p.data_ptr():
+                out.append((kind, weakref.ref(p), extra))
+        return out
+
+    def _capture(self, model, key, m, Cin, roi, desc, imp):
+        from .train_step import side_stream
+        device = desc.device
+        cur = torch.cuda.current_stream(device)
+        side = side_stream(device)
+        ent = _CapturedRow()
+        ent.model = weakref.ref(model)
+        ent.static_in = torch.zeros(m, Cin, *roi, dtype=torch.float32, device=device)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side), torch.no_grad():
+            Fn.workspace(device)                       # exists before capture, outside the graph's private pool
+            self._forward(model, ent.static_in, (), {})  # eager warm-up: derived weight copies and buffers come to exist
+        cur.wait_stream(side)
+        torch.cuda.synchronize(device)
+        ent.as_is = self._as_is(model)
+        ent.graph = torch.cuda.CUDAGraph()
+        # (thread-local capture mode: a live process group's watchdog thread polls events, see TrainStep._capture)
+        with torch.cuda.graph(ent.graph, stream=side, capture_error_mode="thread_local"), torch.no_grad():
+            self._gather(desc, ent.static_in, roi)
+            ent.seg = self._forward(model, ent.static_in, (), {})
+            self._accumulate(desc, ent.seg, imp, roi)
+        cur.wait_stream(side)
+        ent.derived = [(kind, weakref.ref(p), extra) for kind, p, _, extra in self._derived_entries(model)]
+        ent.signature = self._signature(model, device, ent.derived)
+        self._graphs[key] = ent
+        self.stats["captures"] += 1
+        return ent
+
+    def _refresh(self, model, ents):
+        """Before the first replay of a call: the copies the graphs read as they are go through their getters eagerly in a new
+        weight epoch -- nothing happens to a copy that is still optimizer-maintained and in step; a stale one is re-derived into
+        the buffer the graph reads.  False when an address a graph baked in has moved (the caller captures again)."""
+        Fn.begin_forward(None)
+        seen = set()
+        for ent in ents:
+            for kind, ref, extra in ent.as_is:
+                p = ref()
+                if p is None:
+                    return False
+                if (kind, id(p), extra) in seen:
+                    continue
+                seen.add((kind, id(p), extra))
+                if kind == "bf16":
+                    Fn.weight_bf16(p)
+                elif kind == "x3":
+                    Fn.weight_x3(p)
+                else:
+                    Fn.conv_pack_get(p, *extra)
+        device = ents[0].static_in.device
+        return all(ent.signature == self._signature(model, device, ent.derived) for ent in ents)
+
+    def _rows_captured(self, model, sizes, Cin, roi, desc, imp):
+        """the graphs for the batch sizes of this call, captured or re-captured as needed, fresh for replay"""
+        keys = {m: (id(model), model.precision, tuple(roi), m, Cin, desc.device.index, None if imp is None else imp.data_ptr())
+                for m in sizes}
+        for m, key in keys.items():
+            ent = self._graphs.get(key)
+            if ent is not None and ent.model() is not model:
+                del self._graphs[key]
+                ent = None
+            if ent is None:
+                self._capture(model, key, m, Cin, roi, desc, imp)
+        if not self._refresh(model, [self._graphs[k] for k in keys.values()]):
+            for m, key in keys.items():
+                del self._graphs[key]
+                self._capture(model, key, m, Cin, roi, desc, imp)
+                self.stats["recaptures"] += 1
+            if not self._refresh(model, [self._graphs[k] for k in keys.values()]):
+                raise RuntimeError("SlidingWindowInferer: weight buffers moved again right after a re-capture")
+        return {m: self._graphs[k] for m, k in keys.items()}
+
+    # ------------------------------------------------------------------------------------------------ call
+    @torch.no_grad()
+    def __call__(self, inputs: torch.Tensor, network: Callable[..., torch.Tensor], post=None, *args, **kwargs) -> torch.Tensor:
+        from .unetr import UNETR
+        Fn._require_gpu(inputs)
+        if inputs.dim() != 5:
+            raise ValueError("3-D volumes [B,C,D,H,W] expected")
+        if post not in _POST:
+            raise ValueError(f"post must be one of {list(_POST)}, got {post!r}")
+        device = inputs.device
+        B, Cin = inputs.shape[0], inputs.shape[1]
+        image_size_ = list(inputs.shape[2:])
+        roi_size = self.roi_size
+        roi = [roi_size] * 3 if isinstance(roi_size, int) else list(roi_size)
+        roi = [int(r) if r and r > 0 else i for r, i in zip(roi, image_size_)]           # fall_back_tuple
+        image_size = [max(i, r) for i, r in zip(image_size_, roi)]
+        pad = []
+        for k in range(4, 1, -1):
+            diff = max(roi[k - 2] - inputs.shape[k], 0)
+            half = diff // 2
+            pad.extend([half, diff - half])
+        if any(pad) and self.padding_mode != "constant":
+            inputs = F.pad(inputs, pad=pad, mode=self.padding_mode)       # the gather then reads a volume that needs no padding
+            in_size, offs = image_size, (0, 0, 0)
+        else:
+            in_size, offs = image_size_, (pad[4], pad[2], pad[0])         # constant padding happens inside the gather
+        inputs = inputs.contiguous().float()
+        table_cpu, counts = self._plan(B, image_size, roi)
+        n = self.sw_batch_size
+        imp = _device_importance_map(roi, self.mode, self.sigma_scale, device)
+        desc = self._desc_of(device)
+        D, H, W = image_size
+        V = D * H * W
+        captured = self.use_graph and isinstance(network, UNETR) and not args and not kwargs
+        graphs = None
+        if captured:
+            graphs = self._rows_captured(network, sorted(set(counts)), Cin, roi, desc, imp)
+        C = network.out_channels if isinstance(network, UNETR) else None
+        table = table_cpu.pin_memory().to(device, non_blocking=True)
+        vol = _capi.SwVolume()
+        vol.in_, vol.table = inputs.data_ptr(), table.data_ptr()
+        vol.B, vol.Cin = B, Cin
+        vol.Di, vol.Hi, vol.Wi = in_size
+        vol.D, vol.H, vol.W = D, H, W
+        vol.pz, vol.py, vol.px = offs
+        vol.cval, vol.rows, vol.cursor = self.cval, len(counts), -1
+        out = count = None
+
+        def allocate(C):
+            nonlocal out, count
+            out = torch.zeros(B, C, D, H, W, dtype=torch.float32, device=device)
+            count = torch.zeros(B, D, H, W, dtype=torch.float32, device=device)
+            vol.out, vol.count, vol.C = out.data_ptr(), count.data_ptr(), C
+            self._upload_desc(desc, vol)
+
+        if C is not None:
+            allocate(C)
+        else:
+            vol.out = vol.count = None
+            vol.C = 0
+            self._upload_desc(desc, vol)
+        self._keep = (table, inputs)
+        if captured:
+            for m in counts:
+                graphs[m].graph.replay()
+            self.stats["replays"] += len(counts)
+        else:
+            for r, m in enumerate(counts):
+                key = (m, Cin, tuple(roi), device.index)
+                static_in = self._inputs.get(key)
+                if static_in is None:
+                    static_in = self._inputs[key] = torch.empty(m, Cin, *roi, dtype=torch.float32, device=device)
+                self._gather(desc, static_in, roi)
+                seg = self._forward(network, static_in, args, kwargs)
+                if out is None:
+                    vol.cursor = r                    # (the cursor has been advanced to this row already)
+                    allocate(seg.shape[1])
+                elif seg.shape[1] != out.shape[1]:
+                    raise ValueError(f"network returned {seg.shape[1]} channels, {out.shape[1]} expected")
+                self._accumulate(desc, seg, imp, roi)
+            self.stats["eager_rows"] += len(counts)
+        C = out.shape[1]
+        dst = torch.empty(B, 1, D, H, W, dtype=torch.float32, device=device) if post == "argmax" else None
+        call("unetr_sw_finalize_post", out.data_ptr(), count.data_ptr(), dst.data_ptr() if dst is not None else None, B, C, V,
+             _POST[post], Fn._stream())
+        res = dst if dst is not None else out
+        sl = [slice(None), slice(None)]
+        for sp in range(3):                       # undo the padding of volumes smaller than the window
+            lo = pad[(2 - sp) * 2]
+            sl.append(slice(lo, lo + image_size_[sp]))
+        return res[tuple(sl)]

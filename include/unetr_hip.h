@@ -420,6 +420,41 @@ int unetr_sw_accumulate(const float* seg, const float* importance, float* out, f
 int unetr_sw_finalize(float* out, const float* count, int B, int C, long V, void* stream);
 int unetr_dice_counts(const float* pred, const float* y, int B, int C, long V, int from_logits, double* counts,
                       float* ws, size_t ws_bytes, void* stream);
+/* Batched, table-driven form of the same blending (SlidingWindowInferer): one forward batch of up to UNETR_SW_MAX_BATCH windows
+ * is one ROW of a device-resident window table, and the volume is described by a device-resident unetr_sw_volume, so no launch
+ * carries a volume size or a window position in its arguments -- a hipGraph of advance -> gather -> forward -> accumulate serves
+ * every volume.  A table row is UNETR_SW_ROW_INTS ints: [active, 0, 0, 0, then (b, z, y, x) per slot]; z, y, x are window
+ * corners in the PADDED volume [D, H, W] (a volume smaller than the window is padded: input voxel = padded voxel - (pz, py, px)).
+ * Every kernel reads row `cursor`; a cursor outside [0, rows), a slot whose window does not lie inside the padded volume of an
+ * existing batch item, and a channel count that differs from the descriptor's make the launch (or that slot) a no-op.
+ *   unetr_sw_advance          cursor += 1 (device-side, like AdamW's step counters: the row is chosen inside the graph)
+ *   unetr_sw_gather_batch     dst [n, Cin, rz, ry, rx] = the windows of the row; voxels outside the stored input [B, Cin, Di, Hi, Wi]
+ *                             -- and all of an inactive slot -- read cval (F.pad(mode="constant") fused in)
+ *   unetr_sw_accumulate_batch out / count += the active windows of the row, seg [n, C, rz, ry, rx], in ONE launch.  Windows of a
+ *                             row overlap: each output voxel is owned by the thread of the first active slot that covers it, which
+ *                             adds the covering slots in slot order with the fp32 operations of unetr_sw_accumulate -- the result
+ *                             is bit-identical to one unetr_sw_accumulate launch per window in slot order.  No atomics.
+ *   unetr_sw_finalize_post    v = out / count (out [B, C, V], count [B, V]) and, in the same pass, post = 0: out = v;
+ *                             1: out = one_hot(argmax_c v); 2: dst [B, V] = argmax_c v as float (out is left as sums);
+ *                             3: out = (v >= 0), i.e. sigmoid(v) >= 0.5.  argmax takes the first maximal channel; post 1 / 2
+ *                             need C <= 16.
+ * (Additions: no existing signature moved, UNETR_ABI_VERSION stays.) */
+#define UNETR_SW_MAX_BATCH 16
+#define UNETR_SW_ROW_INTS (4 + 4 * UNETR_SW_MAX_BATCH)
+typedef struct {
+    const float* in; float* out; float* count; const int* table;
+    int B, Cin, C;
+    int Di, Hi, Wi;       /* stored input extents */
+    int D, H, W;          /* padded extents (out, count, window corners) */
+    int pz, py, px;       /* low-side padding */
+    float cval;
+    int rows, cursor;
+} unetr_sw_volume;
+int unetr_sw_advance(unetr_sw_volume* vol, void* stream);
+int unetr_sw_gather_batch(const unetr_sw_volume* vol, float* dst, int n, int Cin, int rz, int ry, int rx, void* stream);
+int unetr_sw_accumulate_batch(const unetr_sw_volume* vol, const float* seg, const float* importance, int n, int C,
+                              int rz, int ry, int rx, void* stream);
+int unetr_sw_finalize_post(float* out, const float* count, float* dst, int B, int C, long V, int post, void* stream);
 /* unetr_hausdorff: monai.metrics.HausdorffDistanceMetric (MONAI 0.6.0, distance_metric="euclidean", :495-496) per item and
  * class: out[b][c - c0] (float64, [B][C-c0]) for the classes c0 <= c < C (c0 = 1: include_background=False).  pred / y as in
  * unetr_dice_counts (from_logits fuses argmax + one-hot; otherwise a voxel is in a mask where its value == 1).  use_percentile = 0
