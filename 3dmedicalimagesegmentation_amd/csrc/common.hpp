@@ -352,3 +352,11 @@ int unetr_instnorm_stats_finalize2(const float* part, const float* part_b, int n
 
 // run CALL with `AT` bound to the activation storage type selected by the run-time flag act16
 #define ACT_DISPATCH(act16, ...) do { if (act16) { typedef uint16_t AT; __VA_ARGS__; } else { typedef float AT; __VA_ARGS__; } } while (0)
+// run CALL with `P` bound to the precision class selected by the run-time value prec; any other value: return UNETR_ERR_ARG
+#define PREC_DISPATCH(prec, ...)                                          \
+    do {                                                                  \
+        if ((prec) == UNETR_PREC_BF16) { typedef PrecBF16 P; __VA_ARGS__; }          \
+        else if ((prec) == UNETR_PREC_F32) { typedef PrecF32 P; __VA_ARGS__; }       \
+        else if ((prec) == UNETR_PREC_BF16X3) { typedef PrecBF16x3 P; __VA_ARGS__; } \
+        else return UNETR_ERR_ARG;                                        \
+    } while (0)

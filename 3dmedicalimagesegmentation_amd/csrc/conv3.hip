@@ -1,9 +1,13 @@
-// 3x3x3 convolution (pad 1, stride 1, no bias) on channels-last feature maps for gfx950, three kernels:
+// 3x3x3 convolution (pad 1, stride 1, no bias) on channels-last feature maps for gfx950:
 //
-//   conv3_fwd_kernel    y[v, co] = sum_{tap, ci} x[v + off(tap), ci] * w[co, ci, tap]
-//                       (also the data gradient: same kernel on dy with flipped / transposed packed weights)
-//   conv3_wgrad_kernel  dw[co, ci, tap] = sum_v dy[v, co] * x[v + off(tap), ci]
-//   pack / reduce helpers
+//   conv3_fwd_kernel        y[v, co] = sum_{tap, ci} x[v + off(tap), ci] * w[co, ci, tap], one tile per workgroup
+//                           (also the data gradient: same kernel on dy with flipped / transposed packed weights)
+//   conv3_fwd_pipe_kernel   the same, persistent and software-pipelined, with the fused InstanceNorm sums / 1x1x1 branch (FUSE)
+//   conv3_c1_fwd_kernel     the single-channel image in front of encoder1 (bf16 and bf16x3 modes)
+//   conv3_wgrad_kernel      dw[co, ci, tap] = sum_v dy[v, co] * x[v + off(tap), ci]
+//   conv3_wgrad_x3_kernel   the same in bf16x3 mode on (hi, lo) bf16 images
+//   conv3_c1_wgrad_kernel   the weight gradient of the single-channel image conv (bf16 mode)
+//   conv3_wgrad_reduce_kernel, the pack kernels (conv3_pack_kernel, _pair_, _1x1_, _grouped_), tr16_probe_kernel (a test's probe)
 //
 // Forward: a workgroup owns a 4x4x16 (z,y,x) output tile.  The 6x6x18 input halo of one channel slab
 // (one MFMA k-block: 32 bf16 / 16 f32 channels) is staged ONCE in LDS (fp32 in HBM -> MFMA operand type),
@@ -546,6 +550,17 @@ __device__ __forceinline__ void stats_zero_rows(float* __restrict__ part, int nb
         for (int bb = 0; bb < nb; ++bb) part[(((long)bb * srows) + blockIdx.x) * 2 * Cout + which * Cout + n0 + ch] = 0.f;
     }
 }
+// The flush of the walk over batch items, at `b != cur_b` and after the last tile: the running sums of batch item cur_b go to this
+// workgroup's row of it, then the same for the 1x1x1 branch's set (N3 = 0: the kernel keeps none).  Not called while cur_b < 0 (no
+// batch item yet); that test stays with the callers: folded in here it cost one pipelined instantiation an accumulator register.
+template <int NTB, int N3>
+__device__ __forceinline__ void flush_stats(int cur_b, bool with3, f32x4 (&rs1)[NTB], f32x4 (&rs2)[NTB], f32x4 (&rt1)[N3 ? N3 : 1], f32x4 (&rt2)[N3 ? N3 : 1],
+                                            float* __restrict__ part, float* __restrict__ part3, int Cout, int n0, int r, int g, int wv, float* sred) {
+    const long srows = (long)gridDim.x;           // partial rows per batch item: one per workgroup
+    const long row = (((long)cur_b * srows) + blockIdx.x) * 2 * Cout;
+    stats_flush<NTB>(rs1, rs2, part + row, Cout, n0, r, g, wv, sred);
+    if constexpr (N3 > 0) { if (with3) stats_flush<NTB>(rt1, rt2, part3 + row, Cout, n0, r, g, wv, sred); }
+}
 
 // FUSE >= 1: besides y = conv3x3x3(x) the kernel emits part = InstanceNorm partial sums of y (the separate statistics
 //   pass over y disappears; the partial buffer must be zero-filled before the launch);
@@ -710,10 +725,7 @@ conv3_fwd_pipe_kernel(const void* __restrict__ x, long ldx, const char* __restri
             }
         if constexpr (STATS) {
             if (b != cur_b) {
-                if (cur_b >= 0) {
-                    stats_flush<NTB>(rs1, rs2, part + (((long)cur_b * srows) + blockIdx.x) * 2 * Cout, Cout, nt0 * 16, r, g, wv, sred);
-                    if constexpr (any3) stats_flush<NTB>(rt1, rt2, part3 + (((long)cur_b * srows) + blockIdx.x) * 2 * Cout, Cout, nt0 * 16, r, g, wv, sred);
-                }
+                if (cur_b >= 0) flush_stats<NTB, any3 ? NTB : 0>(cur_b, true, rs1, rs2, rt1, rt2, part, part3, Cout, nt0 * 16, r, g, wv, sred);
                 cur_b = b;
                 if constexpr (BST) {
                     const float* sa = (const float*)wp3 + ((long)b * Cout + nt0 * 16 + 4 * g) * 2;
@@ -1050,178 +1062,63 @@ conv3_fwd_pipe_kernel(const void* __restrict__ x, long ldx, const char* __restri
         }
         tx = ntx_; ty = nty_; tz = ntz_; b = nb_;
     }
-    if constexpr (STATS) {
-        if (cur_b >= 0) {
-            stats_flush<NTB>(rs1, rs2, part + (((long)cur_b * srows) + blockIdx.x) * 2 * Cout, Cout, nt0 * 16, r, g, wv, sred);
-            if constexpr (any3) stats_flush<NTB>(rt1, rt2, part3 + (((long)cur_b * srows) + blockIdx.x) * 2 * Cout, Cout, nt0 * 16, r, g, wv, sred);
-        }
-    }
+    if constexpr (STATS) { if (cur_b >= 0) flush_stats<NTB, any3 ? NTB : 0>(cur_b, true, rs1, rs2, rt1, rt2, part, part3, Cout, nt0 * 16, r, g, wv, sred); }
 }
 
 // ---- ONE input channel, 16 output channels (the image in front of encoder1: UnetrBasicBlock(in_channels, feature_size),
-// unetr.py:90-98), bf16 mode.  The generic pair-mode kernel treats the image as 16 zero-padded channels: 14 K=32 MFMAs per 16
-// voxels of which 27 of 448 products are not zero, and a window staged with scalar loads (60 us at 96^3 for 113 MB of output).
+// unetr.py:90-98), bf16 and bf16x3 modes.  The generic pair-mode kernel treats the image as 16 zero-padded channels: 14 K=32 MFMAs per
+// 16 voxels of which 27 of 448 products are not zero, and a window staged with scalar loads (60 us at 96^3 for 113 MB of output).
 // Here the contraction index IS the tap: [16 voxels, 27 taps (K = 32)] x [32, 16 channels] = one MFMA per 16 voxels.  A window of
 // 6 x 6 x 18 bf16 image values (1.3 KB) is staged per tile; lane (voxel r, tap group g) gathers its eight taps with ds_read_u16;
 // the 1x1x1 branch (UnetResBlock.conv3 on the same input) is x[v] * w3[co] on the VALU -- the exact product of the two bf16
 // values, as the MFMA formed it.  Weights are read from the pair-mode packs (element [tap >> 1][co][(tap & 1) * 16] of wp, element
 // [co][16] of wp3).  Same tile walk, output layout and InstanceNorm partial rows as conv3_fwd_pipe_kernel<..., PAIR, FUSE 2>.
+// P = PrecBF16x3 (fp32 feature maps, split weights): the window travels as two bf16 arrays (hi, lo), the 27-tap contraction is three
+// MFMAs (w_hi x_hi + w_hi x_lo + w_lo x_hi), the 1x1x1 branch an fp32 product of the recombined halves.  The generic slab kernel
+// spent 112 us on this layer (one real channel in a 16-channel slab, 27 MFMA pairs per row).
+template <class P>
 __global__ void __launch_bounds__(256, 4)
-conv3_c1_fwd_kernel(const float* __restrict__ x, const uint16_t* __restrict__ wp, uint16_t* __restrict__ y, long ldy,
+conv3_c1_fwd_kernel(const float* __restrict__ x, const typename ElemOf<P>::type* __restrict__ wp, typename ActOf<P>::type* __restrict__ y, long ldy,
                     int D, int H, int W, int ntx, int nty, int ntz, int ntiles, float* __restrict__ part,
-                    const uint16_t* __restrict__ wp3, uint16_t* __restrict__ y3, float* __restrict__ part3) {
+                    const typename ElemOf<P>::type* __restrict__ wp3, typename ActOf<P>::type* __restrict__ y3, float* __restrict__ part3) {
+    typedef typename ActOf<P>::type YT;
+    constexpr bool X3 = std::is_same<P, PrecBF16x3>::value;
     constexpr int Cout = 16, NPT = (NHALO + 255) / 256;
-    __shared__ uint16_t win[NHALO + 8];
+    __shared__ uint16_t win[NHALO + 8], winl[X3 ? NHALO + 8 : 1];          // the window's bf16 values; x3: its hi and lo halves
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), r = lane & 15, g = lane >> 4;
     const bool has3 = wp3 != nullptr;
+    auto bf2f = [](uint32_t h) { return __builtin_bit_cast(float, h << 16); };
     // weight fragment (first MFMA operand: rows = channels): lane (co = r, g) holds taps 8g .. 8g+7 of channel r
-    u32x4 wfrag;
-    {
-        uint16_t wv8[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int tap = 8 * g + j;
-            wv8[j] = tap < 27 ? wp[((long)(tap >> 1) * Cout + r) * 32 + (tap & 1) * 16] : (uint16_t)0;
-        }
-#pragma unroll
-        for (int d = 0; d < 4; ++d) wfrag[d] = (uint32_t)wv8[2 * d] | ((uint32_t)wv8[2 * d + 1] << 16);
-    }
-    float w3f[4] = {0.f, 0.f, 0.f, 0.f};
-    if (has3) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w3f[e] = __builtin_bit_cast(float, (uint32_t)wp3[(long)(4 * g + e) * 32 + 16] << 16);
-    }
-    // window offsets (elements) of this lane's eight taps relative to voxel (plane wv, row 0, column r); taps 27..31 (zero weights)
-    // read the centre tap: any finite value
-    int toff[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int tap = 8 * g + j < 27 ? 8 * g + j : 13;
-        toff[j] = ((tap / 9) * HY + (tap % 9) / 3) * HX + tap % 3;
-    }
-    const int base0 = (wv * HY) * HX + r;
-    const int cen = (HY + 1) * HX + 1;                    // centre tap
-    // InstanceNorm partial sums (see stats_add / stats_flush)
-    f32x4 rs1[1] = {{0.f, 0.f, 0.f, 0.f}}, rs2[1] = {{0.f, 0.f, 0.f, 0.f}}, rt1[1] = {{0.f, 0.f, 0.f, 0.f}}, rt2[1] = {{0.f, 0.f, 0.f, 0.f}};
-    int cur_b = -1;
-    const long srows = (long)gridDim.x;
-    __shared__ float sred[128];
-    {
-        const int nb = ntiles / (ntx * nty * ntz);
-        stats_zero_rows<1>(part, nb, srows, Cout, 0);
-        if (has3) stats_zero_rows<1>(part3, nb, srows, Cout, 0);
-    }
-    const long item = (long)D * H * W;
-    // this thread's window pieces of tile (b_, z_, y_, x_): image values, 0 outside the volume
-    float nxt[NPT];
-    auto wload = [&](int b_, int z_, int y_, int x_) {
-#pragma unroll
-        for (int j = 0; j < NPT; ++j) {
-            const int id = threadIdx.x + j * 256;
-            const int hz = id / (HY * HX), rem = id - hz * (HY * HX), hy = rem / HX, hx = rem - hy * HX;
-            const int gz = z_ - 1 + hz, gy = y_ - 1 + hy, gx = x_ - 1 + hx;
-            const bool ok = id < NHALO && (unsigned)gz < (unsigned)D && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
-            float t = 0.f;
-            if (ok) t = x[b_ * item + ((long)gz * H + gy) * W + gx];
-            nxt[j] = t;
-        }
-    };
-    TileTable tt;
-    int kt = 0, tx = 0, ty = 0, tz = 0, b = 0;
-    if ((int)blockIdx.x < ntiles) {
-        tt.get(0, ntiles, ntx, nty, ntz, tx, ty, tz, b);
-        wload(b, tz * TZ, ty * TY, tx * TX);
-    }
-    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x, ++kt) {
-        int ax = tx, ay = ty, az = tz, ab = b;
-        const int x0 = tx * TX, y0 = ty * TY, z0 = tz * TZ;
-        if (b != cur_b) {
-            if (cur_b >= 0) {
-                stats_flush<1>(rs1, rs2, part + (((long)cur_b * srows) + blockIdx.x) * 2 * Cout, Cout, 0, r, g, wv, sred);
-                if (has3) stats_flush<1>(rt1, rt2, part3 + (((long)cur_b * srows) + blockIdx.x) * 2 * Cout, Cout, 0, r, g, wv, sred);
-            }
-            cur_b = b;
-        }
-        __syncthreads();                                     // every wave is done with the previous window
-#pragma unroll
-        for (int j = 0; j < NPT; ++j) {
-            const int id = threadIdx.x + j * 256;
-            if (id < NHALO) win[id] = f2bf(nxt[j]);
-        }
-        __syncthreads();
-        if (tile + (int)gridDim.x < ntiles) {                // the next tile's window is in flight during this tile's work
-            tt.get(kt + 1, ntiles, ntx, nty, ntz, ax, ay, az, ab);
-            wload(ab, az * TZ, ay * TY, ax * TX);
-        }
-        const int zo = z0 + wv, xo = x0 + r;
-        f32x4 acc[4][1], acc3[4][1];
-        bool okv[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint16_t* wb = win + base0 + i * HX;
-            uint16_t a8[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a8[j] = wb[toff[j]];
-            u32x4 af;
-#pragma unroll
-            for (int d = 0; d < 4; ++d) af[d] = (uint32_t)a8[2 * d] | ((uint32_t)a8[2 * d + 1] << 16);
-            acc[i][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            PrecBF16::mma(acc[i][0], wfrag, af);
-            const float xc = __builtin_bit_cast(float, (uint32_t)wb[cen] << 16);
-            acc3[i][0] = (f32x4){xc * w3f[0], xc * w3f[1], xc * w3f[2], xc * w3f[3]};
-            okv[i] = zo < D && y0 + i < H && xo < W;
-        }
-        const long tb = (((long)b * D + zo) * H + y0) * W + xo;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (okv[i]) {
-                Io<uint16_t>::st4(y + (tb + (long)i * W) * ldy + 4 * g, acc[i][0]);
-                if (has3 && y3) Io<uint16_t>::st4(y3 + (tb + (long)i * W) * ldy + 4 * g, acc3[i][0]);      // (y3 == nullptr: statistics only)
-            }
-        }
-        stats_add<1>(acc, okv, rs1, rs2);
-        if (has3) stats_add<1>(acc3, okv, rt1, rt2);
-        tx = ax; ty = ay; tz = az; b = ab;
-    }
-    if (cur_b >= 0) {
-        stats_flush<1>(rs1, rs2, part + (((long)cur_b * srows) + blockIdx.x) * 2 * Cout, Cout, 0, r, g, wv, sred);
-        if (has3) stats_flush<1>(rt1, rt2, part3 + (((long)cur_b * srows) + blockIdx.x) * 2 * Cout, Cout, 0, r, g, wv, sred);
-    }
-}
-
-// the same kernel for the bf16x3 mode (fp32 feature maps, split weights): the window travels as two bf16 arrays (hi, lo), the 27-tap
-// contraction is three MFMAs (w_hi x_hi + w_hi x_lo + w_lo x_hi), the 1x1x1 branch an fp32 product of the recombined halves.  The
-// generic slab kernel spent 112 us on this layer (one real channel in a 16-channel slab, 27 MFMA pairs per row).
-__global__ void __launch_bounds__(256, 4)
-conv3_c1_fwd_x3_kernel(const float* __restrict__ x, const uint32_t* __restrict__ wp, float* __restrict__ y, long ldy,
-                    int D, int H, int W, int ntx, int nty, int ntz, int ntiles, float* __restrict__ part,
-                    const uint32_t* __restrict__ wp3, float* __restrict__ y3, float* __restrict__ part3) {
-    constexpr int Cout = 16, NPT = (NHALO + 255) / 256;
-    __shared__ uint16_t win[NHALO + 8], winl[NHALO + 8];          // the window's hi and lo bf16 halves
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), r = lane & 15, g = lane >> 4;
-    const bool has3 = wp3 != nullptr;
-    // weight fragment (first MFMA operand: rows = channels): lane (co = r, g) holds taps 8g .. 8g+7 of channel r
-    // (packed weights of this mode: one word [hi | lo << 16] per element, [tap][co][16 k] with the single input channel at k = 0)
+    // (packed weights of the x3 mode: one word [hi | lo << 16] per element, [tap][co][16 k] with the single input channel at k = 0)
     u32x4 wfrag, wfragl;
     {
-        uint32_t wv8[8];
+        typename ElemOf<P>::type wv8[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int tap = 8 * g + j;
-            wv8[j] = tap < 27 ? wp[((long)tap * Cout + r) * 16] : 0u;
+            if constexpr (X3) wv8[j] = tap < 27 ? wp[((long)tap * Cout + r) * 16] : 0u;
+            else wv8[j] = tap < 27 ? wp[((long)(tap >> 1) * Cout + r) * 32 + (tap & 1) * 16] : (uint16_t)0;
         }
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
-            wfrag[d] = (wv8[2 * d] & 0xffffu) | (wv8[2 * d + 1] << 16);
-            wfragl[d] = (wv8[2 * d] >> 16) | (wv8[2 * d + 1] & 0xffff0000u);
+            if constexpr (X3) {
+                wfrag[d] = (wv8[2 * d] & 0xffffu) | (wv8[2 * d + 1] << 16);
+                wfragl[d] = (wv8[2 * d] >> 16) | (wv8[2 * d + 1] & 0xffff0000u);
+            } else {
+                wfrag[d] = (uint32_t)wv8[2 * d] | ((uint32_t)wv8[2 * d + 1] << 16);
+            }
         }
     }
     float w3f[4] = {0.f, 0.f, 0.f, 0.f};
     if (has3) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const uint32_t t = wp3[(long)(4 * g + e) * 16];
-            w3f[e] = __builtin_bit_cast(float, t << 16) + __builtin_bit_cast(float, t & 0xffff0000u);
+            if constexpr (X3) {
+                const uint32_t t = wp3[(long)(4 * g + e) * 16];
+                w3f[e] = bf2f(t) + __builtin_bit_cast(float, t & 0xffff0000u);
+            } else {
+                w3f[e] = bf2f(wp3[(long)(4 * g + e) * 32 + 16]);
+            }
         }
     }
     // window offsets (elements) of this lane's eight taps relative to voxel (plane wv, row 0, column r); taps 27..31 (zero weights)
@@ -1237,12 +1134,11 @@ conv3_c1_fwd_x3_kernel(const float* __restrict__ x, const uint32_t* __restrict__
     // InstanceNorm partial sums (see stats_add / stats_flush)
     f32x4 rs1[1] = {{0.f, 0.f, 0.f, 0.f}}, rs2[1] = {{0.f, 0.f, 0.f, 0.f}}, rt1[1] = {{0.f, 0.f, 0.f, 0.f}}, rt2[1] = {{0.f, 0.f, 0.f, 0.f}};
     int cur_b = -1;
-    const long srows = (long)gridDim.x;
     __shared__ float sred[128];
     {
         const int nb = ntiles / (ntx * nty * ntz);
-        stats_zero_rows<1>(part, nb, srows, Cout, 0);
-        if (has3) stats_zero_rows<1>(part3, nb, srows, Cout, 0);
+        stats_zero_rows<1>(part, nb, (long)gridDim.x, Cout, 0);
+        if (has3) stats_zero_rows<1>(part3, nb, (long)gridDim.x, Cout, 0);
     }
     const long item = (long)D * H * W;
     // this thread's window pieces of tile (b_, z_, y_, x_): image values, 0 outside the volume
@@ -1269,17 +1165,17 @@ conv3_c1_fwd_x3_kernel(const float* __restrict__ x, const uint32_t* __restrict__
         int ax = tx, ay = ty, az = tz, ab = b;
         const int x0 = tx * TX, y0 = ty * TY, z0 = tz * TZ;
         if (b != cur_b) {
-            if (cur_b >= 0) {
-                stats_flush<1>(rs1, rs2, part + (((long)cur_b * srows) + blockIdx.x) * 2 * Cout, Cout, 0, r, g, wv, sred);
-                if (has3) stats_flush<1>(rt1, rt2, part3 + (((long)cur_b * srows) + blockIdx.x) * 2 * Cout, Cout, 0, r, g, wv, sred);
-            }
+            if (cur_b >= 0) flush_stats<1, 1>(cur_b, has3, rs1, rs2, rt1, rt2, part, part3, Cout, 0, r, g, wv, sred);
             cur_b = b;
         }
         __syncthreads();                                     // every wave is done with the previous window
 #pragma unroll
         for (int j = 0; j < NPT; ++j) {
             const int id = threadIdx.x + j * 256;
-            if (id < NHALO) { const uint32_t t = PrecBF16x3::split(nxt[j]); win[id] = (uint16_t)t; winl[id] = (uint16_t)(t >> 16); }
+            if (id < NHALO) {
+                if constexpr (X3) { const uint32_t t = PrecBF16x3::split(nxt[j]); win[id] = (uint16_t)t; winl[id] = (uint16_t)(t >> 16); }
+                else win[id] = f2bf(nxt[j]);
+            }
         }
         __syncthreads();
         if (tile + (int)gridDim.x < ntiles) {                // the next tile's window is in flight during this tile's work
@@ -1292,21 +1188,27 @@ conv3_c1_fwd_x3_kernel(const float* __restrict__ x, const uint32_t* __restrict__
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const uint16_t* wb = win + base0 + i * HX;
-            const uint16_t* wbl = winl + base0 + i * HX;
+            const uint16_t* wbl = X3 ? winl + base0 + i * HX : winl;      // (bf16 mode: no lo window)
             uint16_t a8[8], l8[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { a8[j] = wb[toff[j]]; l8[j] = wbl[toff[j]]; }
+            for (int j = 0; j < 8; ++j) {
+                a8[j] = wb[toff[j]];
+                if constexpr (X3) l8[j] = wbl[toff[j]];
+            }
             u32x4 af, afl;
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
                 af[d] = (uint32_t)a8[2 * d] | ((uint32_t)a8[2 * d + 1] << 16);
-                afl[d] = (uint32_t)l8[2 * d] | ((uint32_t)l8[2 * d + 1] << 16);
+                if constexpr (X3) afl[d] = (uint32_t)l8[2 * d] | ((uint32_t)l8[2 * d + 1] << 16);
             }
             acc[i][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            PrecBF16::mma(acc[i][0], wfrag, af);            // w_hi x_hi + w_hi x_lo + w_lo x_hi
-            PrecBF16::mma(acc[i][0], wfrag, afl);
-            PrecBF16::mma(acc[i][0], wfragl, af);
-            const float xc = __builtin_bit_cast(float, (uint32_t)wb[cen] << 16) + __builtin_bit_cast(float, (uint32_t)wbl[cen] << 16);
+            PrecBF16::mma(acc[i][0], wfrag, af);
+            if constexpr (X3) {                             // w_hi x_hi + w_hi x_lo + w_lo x_hi
+                PrecBF16::mma(acc[i][0], wfrag, afl);
+                PrecBF16::mma(acc[i][0], wfragl, af);
+            }
+            float xc = bf2f(wb[cen]);
+            if constexpr (X3) xc += bf2f(wbl[cen]);
             acc3[i][0] = (f32x4){xc * w3f[0], xc * w3f[1], xc * w3f[2], xc * w3f[3]};
             okv[i] = zo < D && y0 + i < H && xo < W;
         }
@@ -1314,18 +1216,15 @@ conv3_c1_fwd_x3_kernel(const float* __restrict__ x, const uint32_t* __restrict__
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             if (okv[i]) {
-                Io<float>::st4(y + (tb + (long)i * W) * ldy + 4 * g, acc[i][0]);
-                if (has3 && y3) Io<float>::st4(y3 + (tb + (long)i * W) * ldy + 4 * g, acc3[i][0]);      // (y3 == nullptr: statistics only)
+                Io<YT>::st4(y + (tb + (long)i * W) * ldy + 4 * g, acc[i][0]);
+                if (has3 && y3) Io<YT>::st4(y3 + (tb + (long)i * W) * ldy + 4 * g, acc3[i][0]);      // (y3 == nullptr: statistics only)
             }
         }
         stats_add<1>(acc, okv, rs1, rs2);
         if (has3) stats_add<1>(acc3, okv, rt1, rt2);
         tx = ax; ty = ay; tz = az; b = ab;
     }
-    if (cur_b >= 0) {
-        stats_flush<1>(rs1, rs2, part + (((long)cur_b * srows) + blockIdx.x) * 2 * Cout, Cout, 0, r, g, wv, sred);
-        if (has3) stats_flush<1>(rt1, rt2, part3 + (((long)cur_b * srows) + blockIdx.x) * 2 * Cout, Cout, 0, r, g, wv, sred);
-    }
+    if (cur_b >= 0) flush_stats<1, 1>(cur_b, has3, rs1, rs2, rt1, rt2, part, part3, Cout, 0, r, g, wv, sred);
 }
 
 // 1x1x1 weights w3[Cout][Cin] in the B-fragment layout the fused kernel reads at the centre tap:
@@ -1361,6 +1260,124 @@ template <class P, bool HAS3 = false> struct WgCfg {
     static constexpr int UPW = (NUX + 3) / 4;                 // units per wave
 };
 
+// One MFMA operand fragment (k = 32 voxels) out of a channel-contiguous bf16 image: two ds_read_b64_tr_b16, one per voxel row of the
+// lane, repacked to the 16-byte operand.
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ u32x4 tr2(const char* img, int o0, int o1) {
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(img + o0));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(img + o1));
+    const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(u32x4, v);
+}
+
+// Addresses of the transposing reads on LAY 2 images (window pitch PX, dy tile pitch PY), everything that does not depend on the
+// k-block, formed once per thread.  uoff: per-unit byte offset of the shifted window's (dz, dy) row (wave-uniform).  The column part
+// of the address is per lane AND per tap column dx (the LAY 2 permutation is not a shift): the three candidates of this lane's two
+// voxel rows are formed once (they do not depend on the k-block: v & 15 is (8g + q) & 15 for every kb).  Unit ui of wave wv handles
+// tap wv + 4 ui, i.e. tap column dx = (wv + ui) % 3: the three column offsets are rotated ONCE by the wave's phase, so unit ui simply
+// takes entry ui % 3 (a compile-time index), and every per-lane address part -- lane row (g >> 1), 8-byte piece p, permuted column
+// -- is summed here, outside the loops.  xc0/1: the centre tap (the 1x1x1 units); ylane0/1: the lane's two rows of a dy tile.
+template <int UPW> struct TrLanes { int uoff[UPW], xs0[3] = {0, 0, 0}, xs1[3] = {0, 0, 0}, xc0 = 0, xc1 = 0, ylane0 = 0, ylane1 = 0; };
+template <int PX, int PY, bool FLIP = true, int UPW>
+__device__ __forceinline__ void tr_lanes(TrLanes<UPW>& L, int wv, int c, int g) {
+#pragma unroll
+    for (int ui = 0; ui < UPW; ++ui) {
+        const int u = wv + 4 * ui;
+        const int tap = u >= 27 ? 13 : u;
+        const int dz = tap / 9, rem = tap - dz * 9, dyy = rem / 3, dx = rem - dyy * 3;
+        L.uoff[ui] = ((dz * HY + dyy) * HX + (FLIP ? 0 : dx)) * PX;
+    }
+    if constexpr (FLIP) {      // (plain layouts: the tap column is a shift of dx voxels, and there are no transposing reads)
+        const int q = c >> 2, p = c & 3;
+        const int xl = (8 * g + q) & 15;
+        const int lane_zy = (g >> 1) * HX * PX + 8 * p;             // the k-block's second voxel row for lane groups 2, 3
+        int t0[3], t1[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { t0[d] = lay_flip(xl + d) * PX + lane_zy; t1[d] = lay_flip(xl + 4 + d) * PX + lane_zy; }
+        const int w3 = wv % 3;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int d = (w3 + j) % 3;                 // wave-uniform
+            L.xs0[j] = d == 0 ? t0[0] : (d == 1 ? t0[1] : t0[2]);
+            L.xs1[j] = d == 0 ? t1[0] : (d == 1 ? t1[1] : t1[2]);
+        }
+        L.xc0 = t0[1]; L.xc1 = t1[1];
+        L.ylane0 = lay_flip(8 * g + q) * PY + 8 * p;
+        L.ylane1 = lay_flip(8 * g + q + 4) * PY + 8 * p;
+    }
+}
+
+// partial sums of a wave's units: part[blockIdx.x][co][ci][tap]; the 1x1x1 unit (u = 27) goes to part3[blockIdx.x][co][ci]
+template <int nunits, int UPW>
+__device__ __forceinline__ void wgrad_store_part(const f32x4 (&acc)[UPW], float* __restrict__ part, float* __restrict__ part3,
+                                                 int wv, int c, int g, int ci0, int co0, int Cin, int Cout) {
+#pragma unroll
+    for (int ui = 0; ui < UPW; ++ui) {
+        const int u = wv + 4 * ui;
+        if (u < nunits) {
+            const int ci = ci0 + c;
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                const int co = co0 + 4 * g + rr;
+                if (ci < Cin && co < Cout) {
+                    if (u < 27) part[(((long)blockIdx.x * Cout + co) * Cin + ci) * 27 + u] = acc[ui][rr];
+                    else part3[((long)blockIdx.x * Cout + co) * Cin + ci] = acc[ui][rr];
+                }
+            }
+        }
+    }
+}
+
+// The NKB x UPW (k-block, unit) steps of one tile as ONE straight line, software-pipelined: every per-lane address part is k-block
+// independent (TrLanes), per read one add of a wave-uniform (k-block, unit) offset; the x fragments of the next DPT steps and the dy
+// fragment of the next k-block are in flight while a step's MFMAs run (as a guarded loop every MFMA waited for its own two reads:
+// lgkmcnt(0) 56 times per tile).  A wave's unit beyond the last one (wave 3 without the 1x1x1 units) reads the centre tap and
+// accumulates into a register that is never written out.  NI = bf16 images per operand: 1 (bf16 mode: one MFMA per step) or 2
+// (bf16x3: [0] = hi, [1] = lo halves, three MFMAs per step: dy_hi x_hi + dy_hi x_lo + dy_lo x_hi).  32-byte voxels in all images.
+template <bool HAS3, int NI, int DPT, int UPW>
+__device__ __forceinline__ void wgrad_pipe_line(f32x4 (&acc)[UPW], const TrLanes<UPW>& L, int wv, const char* const (&ximg)[NI],
+                                                const char* const (&yimg)[NI], const char* const (&y3img)[NI]) {
+    constexpr int PX = 32, PY = 32, NKB = NVOX / 32, NST = NKB * UPW;
+    auto aread = [&](int kb, const char* const (&img)[NI], u32x4 (&af)[NI]) __attribute__((always_inline)) {
+        const int ykb = kb * 32 * PY;
+#pragma unroll
+        for (int n = 0; n < NI; ++n) af[n] = tr2(img[n], ykb + L.ylane0, ykb + L.ylane1);
+    };
+    auto bread = [&](int st, u32x4 (&bf)[NI]) __attribute__((always_inline)) {
+        const int kb = st / UPW, ui = st % UPW;
+        const bool ext1 = HAS3 && ui == UPW - 1 && wv + 4 * ui >= 27;     // wave-uniform
+        const int uo = ((kb >> 1) * HY + (kb & 1) * 2) * HX * PX + L.uoff[ui];    // window row of the k-block's first voxel row
+        const int o0 = uo + (ext1 ? L.xc0 : L.xs0[ui % 3]), o1 = uo + (ext1 ? L.xc1 : L.xs1[ui % 3]);
+#pragma unroll
+        for (int n = 0; n < NI; ++n) bf[n] = tr2(ximg[n], o0, o1);
+    };
+    u32x4 rb[DPT][NI];
+    u32x4 af[2][NI], af3[NI];                     // dy fragment: this k-block's and the next one's; dy3: fetched two steps before its unit
+#pragma unroll
+    for (int n = 0; n < NI; ++n) af3[n] = (u32x4){0u, 0u, 0u, 0u};
+    aread(0, yimg, af[0]);
+#pragma unroll
+    for (int st = 0; st < DPT; ++st) bread(st, rb[st]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int st = 0; st < NST; ++st) {
+        const int kb = st / UPW, ui = st % UPW;
+        if (ui == 0 && kb + 1 < NKB) aread(kb + 1, yimg, af[(kb + 1) & 1]);
+        if constexpr (HAS3) { if (ui == UPW - 3) aread(kb, y3img, af3); }
+        const bool ext1 = HAS3 && ui == UPW - 1 && wv + 4 * ui >= 27;
+        u32x4 a[NI], b[NI];
+#pragma unroll
+        for (int n = 0; n < NI; ++n) { a[n] = ext1 ? af3[n] : af[kb & 1][n]; b[n] = rb[st % DPT][n]; }
+        PrecBF16::mma(acc[ui], a[0], b[0]);
+        if constexpr (NI == 2) {
+            PrecBF16::mma(acc[ui], a[0], b[1]);
+            PrecBF16::mma(acc[ui], a[1], b[0]);
+        }
+        if (st + DPT < NST) bread(st + DPT, rb[st % DPT]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 // XMX: storage of x (see stage_halo); dy / dy3 are feature-map gradients: ActOf<P> (bf16 in bf16 mode -- VECY is then moot:
 // a 16-channel dy row is two 16-byte pieces)
 // resident weight-gradient workgroups per CU: with the software-pipelined unit loop and the staging plans two
@@ -1386,40 +1403,9 @@ conv3_wgrad_kernel(const void* __restrict__ x, long ldx, const typename ActOf<P>
     constexpr int nunits = C::NUX;
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), c = lane & 15, g = lane >> 4;
     const int ci0 = blockIdx.y * 16, co0 = blockIdx.z * 16;
-    // per-unit LDS byte offsets of the shifted window (wave-uniform)
-    // FLIP layout: the column part of the address is per lane AND per tap column dx (the LAY 2 permutation is not a shift):
-    // the three candidates of this lane's two voxel rows are formed once (they do not depend on the k-block: v & 15 is
-    // (8g + q) & 15 for every kb), the per-unit choice is a wave-uniform select
-    int uoff[WG_UPW];
-#pragma unroll
-    for (int ui = 0; ui < WG_UPW; ++ui) {
-        int u = wv + 4 * ui;
-        int tap = u >= WG_UNITS ? 13 : u;
-        int dz = tap / 9, rem = tap - dz * 9, dyy = rem / 3, dx = rem - dyy * 3;
-        uoff[ui] = ((dz * HY + dyy) * HX + (C::FLIP ? 0 : dx)) * C::PX;
-    }
-    // unit ui of wave wv handles tap wv + 4 ui, i.e. tap column dx = (wv + ui) % 3: the three column offsets are rotated
-    // ONCE by the wave's phase, so unit ui simply takes entry ui % 3 (a compile-time index), and every per-lane address part
-    // of the transposing reads -- lane row (g >> 1), 8-byte piece p, permuted column -- is summed here, outside the loops
-    int xs0[3] = {0, 0, 0}, xs1[3] = {0, 0, 0}, xc0 = 0, xc1 = 0, ylane0 = 0, ylane1 = 0;
-    if constexpr (C::FLIP) {
-        const int q = c >> 2, p = c & 3;
-        const int xl = (8 * g + q) & 15;
-        const int lane_zy = (g >> 1) * HX * C::PX + 8 * p;             // the k-block's second voxel row for lane groups 2, 3
-        int t0[3], t1[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { t0[d] = lay_flip(xl + d) * C::PX + lane_zy; t1[d] = lay_flip(xl + 4 + d) * C::PX + lane_zy; }
-        const int w3 = wv % 3;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int d = (w3 + j) % 3;                 // wave-uniform
-            xs0[j] = d == 0 ? t0[0] : (d == 1 ? t0[1] : t0[2]);
-            xs1[j] = d == 0 ? t1[0] : (d == 1 ? t1[1] : t1[2]);
-        }
-        xc0 = t0[1]; xc1 = t1[1];                        // centre tap (the 1x1x1 units)
-        ylane0 = lay_flip(8 * g + q) * C::PY + 8 * p;
-        ylane1 = lay_flip(8 * g + q + 4) * C::PY + 8 * p;
-    }
+    // per-unit LDS byte offsets of the shifted window (wave-uniform) and, in the FLIP layout, the per-lane parts of the transposing reads
+    TrLanes<WG_UPW> tl;
+    tr_lanes<C::PX, C::PY, C::FLIP>(tl, wv, c, g);
     f32x4 acc[WG_UPW];
 #pragma unroll
     for (int ui = 0; ui < WG_UPW; ++ui) acc[ui] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1542,73 +1528,26 @@ conv3_wgrad_kernel(const void* __restrict__ x, long ldx, const typename ActOf<P>
         if (nt < ntiles) tile_load(ab, az * TZ, ay * TY, ax * TX);
 
         if constexpr (CH == 8 && XMX == 2) {
-            // bf16, conflict-free layout: every per-lane address part is k-block independent (formed once before
-            // the loop: ylane0/1, xs0/1[3]); per read one add of a wave-uniform (k-block, unit) offset.  The NKB x UPW (k-block,
-            // unit) steps run as ONE straight line, software-pipelined: the x fragments of the next DPT steps and the dy fragment
-            // of the next k-block are in flight while a step's MFMA runs (as a guarded loop every MFMA waited for its own two
-            // reads: lgkmcnt(0) 56 times per tile).  A wave's unit beyond the last one (wave 3 without the 1x1x1 units) reads the
-            // centre tap and accumulates into a register that is never written out.
-            typedef short s16x8 __attribute__((ext_vector_type(8)));
-            constexpr int NST = C::NKB * WG_UPW, DPT = HAS3 ? 3 : 5;      // (fp32-stored x, the image: the guarded loop below -- its prefetch registers leave no room)
-            auto aread = [&](int kb, const char* img, u32x4& af) {
-                const int ykb = kb * 32 * C::PY;
-                s16x4 alo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(img + ykb + ylane0));
-                s16x4 ahi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(img + ykb + ylane1));
-                s16x8 a8 = {alo[0], alo[1], alo[2], alo[3], ahi[0], ahi[1], ahi[2], ahi[3]};
-                af = __builtin_bit_cast(u32x4, a8);
-            };
-            auto bread = [&](int st, s16x4& lo, s16x4& hi) {
-                const int kb = st / WG_UPW, ui = st % WG_UPW;
-                const bool ext1 = HAS3 && ui == WG_UPW - 1 && wv + 4 * ui >= WG_UNITS;     // wave-uniform
-                const int uo = ((kb >> 1) * HY + (kb & 1) * 2) * HX * C::PX + uoff[ui];    // window row of the k-block's first voxel row
-                lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(ximg + uo + (ext1 ? xc0 : xs0[ui % 3])));
-                hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(ximg + uo + (ext1 ? xc1 : xs1[ui % 3])));
-            };
-            s16x4 rlo[DPT], rhi[DPT];
-            u32x4 af[2], af3 = {0u, 0u, 0u, 0u};          // dy fragment: this k-block's and the next one's; dy3: fetched two steps before its unit
-            aread(0, yimg, af[0]);
-#pragma unroll
-            for (int st = 0; st < DPT; ++st) bread(st, rlo[st], rhi[st]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int st = 0; st < NST; ++st) {
-                const int kb = st / WG_UPW, ui = st % WG_UPW;
-                if (ui == 0 && kb + 1 < C::NKB) aread(kb + 1, yimg, af[(kb + 1) & 1]);
-                if constexpr (HAS3) { if (ui == WG_UPW - 3) aread(kb, y3img, af3); }
-                const s16x4 blo = rlo[st % DPT], bhi = rhi[st % DPT];
-                s16x8 b8 = {blo[0], blo[1], blo[2], blo[3], bhi[0], bhi[1], bhi[2], bhi[3]};
-                const bool ext1 = HAS3 && ui == WG_UPW - 1 && wv + 4 * ui >= WG_UNITS;
-                P::mma(acc[ui], ext1 ? af3 : af[kb & 1], __builtin_bit_cast(u32x4, b8));
-                if (st + DPT < NST) bread(st + DPT, rlo[st % DPT], rhi[st % DPT]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            // bf16, conflict-free layout: the software-pipelined line (fp32-stored x, the image: the guarded loop below -- its
+            // prefetch registers leave no room)
+            static_assert(C::PX == 32 && C::PY == 32 && C::NKB == NVOX / 32, "wgrad_pipe_line reads 32-byte voxels");
+            wgrad_pipe_line<HAS3, 1, HAS3 ? 3 : 5>(acc, tl, wv, {ximg}, {yimg}, {y3img});
         } else
         for (int kb = 0; kb < C::NKB; ++kb) {
             if constexpr (CH == 8) {
                 // bf16 on the fp32-stored image, conflict-free layout: the same addressing as a guarded loop
-                typedef short s16x8 __attribute__((ext_vector_type(8)));
                 const int ykb = kb * 32 * C::PY;
-                s16x4 alo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(yimg + ykb + ylane0));
-                s16x4 ahi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(yimg + ykb + ylane1));
-                s16x8 a8 = {alo[0], alo[1], alo[2], alo[3], ahi[0], ahi[1], ahi[2], ahi[3]};
-                const u32x4 afrag = __builtin_bit_cast(u32x4, a8);
+                const u32x4 afrag = tr2(yimg, ykb + tl.ylane0, ykb + tl.ylane1);
                 u32x4 afrag3 = afrag;
-                if constexpr (HAS3) {
-                    s16x4 clo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(y3img + ykb + ylane0));
-                    s16x4 chi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(y3img + ykb + ylane1));
-                    s16x8 c8 = {clo[0], clo[1], clo[2], clo[3], chi[0], chi[1], chi[2], chi[3]};
-                    afrag3 = __builtin_bit_cast(u32x4, c8);
-                }
+                if constexpr (HAS3) afrag3 = tr2(y3img, ykb + tl.ylane0, ykb + tl.ylane1);
                 const int xkb = ((kb >> 1) * HY + (kb & 1) * 2) * HX * C::PX;       // window row of the k-block's first voxel row
 #pragma unroll
                 for (int ui = 0; ui < WG_UPW; ++ui) {
                     if (wv + 4 * ui < nunits) {
                         const bool ext1 = HAS3 && ui == WG_UPW - 1 && wv + 4 * ui >= WG_UNITS;     // wave-uniform
-                        const int uo = xkb + uoff[ui];
-                        s16x4 blo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(ximg + uo + (ext1 ? xc0 : xs0[ui % 3])));
-                        s16x4 bhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(ximg + uo + (ext1 ? xc1 : xs1[ui % 3])));
-                        s16x8 b8 = {blo[0], blo[1], blo[2], blo[3], bhi[0], bhi[1], bhi[2], bhi[3]};
-                        P::mma(acc[ui], ext1 ? afrag3 : afrag, __builtin_bit_cast(u32x4, b8));
+                        const int uo = xkb + tl.uoff[ui];
+                        const u32x4 bfrag = tr2(ximg, uo + (ext1 ? tl.xc0 : tl.xs0[ui % 3]), uo + (ext1 ? tl.xc1 : tl.xs1[ui % 3]));
+                        P::mma(acc[ui], ext1 ? afrag3 : afrag, bfrag);
                     }
                 }
             } else {
@@ -1629,7 +1568,7 @@ conv3_wgrad_kernel(const void* __restrict__ x, long ldx, const typename ActOf<P>
                         const bool ext = (ui == WG_UPW - 1 && wv + 4 * ui >= WG_UNITS);
                         u32x4 bv;
 #pragma unroll
-                        for (int tt = 0; tt < 4; ++tt) bv[tt] = *(const uint32_t*)(ximg + hb[tt] + uoff[ui]);
+                        for (int tt = 0; tt < 4; ++tt) bv[tt] = *(const uint32_t*)(ximg + hb[tt] + tl.uoff[ui]);
                         P::mma(acc[ui], ext ? av3 : av, bv);
                     }
                 }
@@ -1637,22 +1576,7 @@ conv3_wgrad_kernel(const void* __restrict__ x, long ldx, const typename ActOf<P>
         }
         tx = ax; ty = ay; tz = az; b = ab;
     }
-    // partial sums: part[blockIdx.x][co][ci][tap]
-#pragma unroll
-    for (int ui = 0; ui < WG_UPW; ++ui) {
-        int u = wv + 4 * ui;
-        if (u < nunits) {
-            int ci = ci0 + c;
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                int co = co0 + 4 * g + rr;
-                if (ci < Cin && co < Cout) {
-                    if (u < WG_UNITS) part[(((long)blockIdx.x * Cout + co) * Cin + ci) * 27 + u] = acc[ui][rr];
-                    else part3[((long)blockIdx.x * Cout + co) * Cin + ci] = acc[ui][rr];
-                }
-            }
-        }
-    }
+    wgrad_store_part<nunits>(acc, part, part3, wv, c, g, ci0, co0, Cin, Cout);
 }
 
 // ---- bf16x3 weight gradient on (hi, lo) bf16 images ---------------------------------------------------------------------------
@@ -1672,7 +1596,7 @@ conv3_wgrad_x3_kernel(const float* __restrict__ x, long ldx, const float* __rest
                       const float* __restrict__ dy3, long lddy3, float* __restrict__ part3,
                       int D, int H, int W, int Cin, int Cout, int ntx, int nty, int ntz, int ntiles) {
     constexpr int PX = 32, PY = 32, XB = NHALO * PX, YB = NVOX * PY;
-    constexpr int NKB = NVOX / 32, NU = 27, NUX = NU + (HAS3 ? 1 : 0), UPW = (NUX + 3) / 4;
+    constexpr int NU = 27, NUX = NU + (HAS3 ? 1 : 0), UPW = (NUX + 3) / 4;
     __shared__ __attribute__((aligned(16))) char lds[2 * XB + (HAS3 ? 4 : 2) * YB];
     char* const xhi = lds;
     char* const xlo = lds + XB;
@@ -1682,34 +1606,8 @@ conv3_wgrad_x3_kernel(const float* __restrict__ x, long ldx, const float* __rest
     char* const y3lo = y3hi + YB;
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), c = lane & 15, g = lane >> 4;
     const int ci0 = blockIdx.y * 16, co0 = blockIdx.z * 16;
-    // per-unit window offsets (wave-uniform) and the per-lane parts of the transposing reads: as in conv3_wgrad_kernel's FLIP path
-    int uoff[UPW];
-#pragma unroll
-    for (int ui = 0; ui < UPW; ++ui) {
-        const int u = wv + 4 * ui;
-        const int tap = u >= NU ? 13 : u;
-        const int dz = tap / 9, rem = tap - dz * 9, dyy = rem / 3;
-        uoff[ui] = ((dz * HY + dyy) * HX) * PX;
-    }
-    int xs0[3], xs1[3], xc0, xc1, ylane0, ylane1;
-    {
-        const int q = c >> 2, p = c & 3;
-        const int xl = (8 * g + q) & 15;
-        const int lane_zy = (g >> 1) * HX * PX + 8 * p;
-        int t0[3], t1[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { t0[d] = lay_flip(xl + d) * PX + lane_zy; t1[d] = lay_flip(xl + 4 + d) * PX + lane_zy; }
-        const int w3 = wv % 3;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int d = (w3 + j) % 3;
-            xs0[j] = d == 0 ? t0[0] : (d == 1 ? t0[1] : t0[2]);
-            xs1[j] = d == 0 ? t1[0] : (d == 1 ? t1[1] : t1[2]);
-        }
-        xc0 = t0[1]; xc1 = t1[1];
-        ylane0 = lay_flip(8 * g + q) * PY + 8 * p;
-        ylane1 = lay_flip(8 * g + q + 4) * PY + 8 * p;
-    }
+    TrLanes<UPW> tl;
+    tr_lanes<PX, PY>(tl, wv, c, g);
     f32x4 acc[UPW];
 #pragma unroll
     for (int ui = 0; ui < UPW; ++ui) acc[ui] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1787,67 +1685,10 @@ conv3_wgrad_x3_kernel(const float* __restrict__ x, long ldx, const float* __rest
             }
         }
         __syncthreads();
-        // the NKB x UPW (k-block, unit) steps as one software-pipelined straight line (see conv3_wgrad_kernel's fast path)
-        typedef short s16x8 __attribute__((ext_vector_type(8)));
-        constexpr int NST = NKB * UPW, DPT = 3;
-        auto tr2 = [&](const char* img, int o0, int o1) __attribute__((always_inline)) {
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(img + o0));
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(img + o1));
-            const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            return __builtin_bit_cast(u32x4, v);
-        };
-        auto bread = [&](int st, u32x4& bh, u32x4& bl) __attribute__((always_inline)) {
-            const int kb = st / UPW, ui = st % UPW;
-            const bool ext1 = HAS3 && ui == UPW - 1 && wv + 4 * ui >= NU;     // wave-uniform
-            const int uo = ((kb >> 1) * HY + (kb & 1) * 2) * HX * PX + uoff[ui];
-            const int o0 = uo + (ext1 ? xc0 : xs0[ui % 3]), o1 = uo + (ext1 ? xc1 : xs1[ui % 3]);
-            bh = tr2(xhi, o0, o1);
-            bl = tr2(xlo, o0, o1);
-        };
-        u32x4 rbh[DPT], rbl[DPT];
-        u32x4 ah[2], al[2], a3h = {0u, 0u, 0u, 0u}, a3l = {0u, 0u, 0u, 0u};
-        ah[0] = tr2(yhi, ylane0, ylane1);
-        al[0] = tr2(ylo, ylane0, ylane1);
-#pragma unroll
-        for (int st = 0; st < DPT; ++st) bread(st, rbh[st], rbl[st]);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int st = 0; st < NST; ++st) {
-            const int kb = st / UPW, ui = st % UPW;
-            if (ui == 0 && kb + 1 < NKB) {
-                const int ykb = (kb + 1) * 32 * PY;
-                ah[(kb + 1) & 1] = tr2(yhi, ykb + ylane0, ykb + ylane1);
-                al[(kb + 1) & 1] = tr2(ylo, ykb + ylane0, ykb + ylane1);
-            }
-            if constexpr (HAS3) {
-                if (ui == UPW - 3) { const int ykb = kb * 32 * PY; a3h = tr2(y3hi, ykb + ylane0, ykb + ylane1); a3l = tr2(y3lo, ykb + ylane0, ykb + ylane1); }
-            }
-            const u32x4 bh = rbh[st % DPT], bl = rbl[st % DPT];
-            const bool ext1 = HAS3 && ui == UPW - 1 && wv + 4 * ui >= NU;
-            const u32x4 fh = ext1 ? a3h : ah[kb & 1], fl = ext1 ? a3l : al[kb & 1];
-            PrecBF16::mma(acc[ui], fh, bh);
-            PrecBF16::mma(acc[ui], fh, bl);
-            PrecBF16::mma(acc[ui], fl, bh);
-            if (st + DPT < NST) bread(st + DPT, rbh[st % DPT], rbl[st % DPT]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        static_assert(PX == 32 && PY == 32, "wgrad_pipe_line reads 32-byte voxels");
+        wgrad_pipe_line<HAS3, 2, 3>(acc, tl, wv, {xhi, xlo}, {yhi, ylo}, {y3hi, y3lo});
     }
-    // partial sums: part[blockIdx.x][co][ci][tap]
-#pragma unroll
-    for (int ui = 0; ui < UPW; ++ui) {
-        const int u = wv + 4 * ui;
-        if (u < NUX) {
-            const int ci = ci0 + c;
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int co = co0 + 4 * g + rr;
-                if (ci < Cin && co < Cout) {
-                    if (u < NU) part[(((long)blockIdx.x * Cout + co) * Cin + ci) * 27 + u] = acc[ui][rr];
-                    else part3[((long)blockIdx.x * Cout + co) * Cin + ci] = acc[ui][rr];
-                }
-            }
-        }
-    }
+    wgrad_store_part<NUX>(acc, part, part3, wv, c, g, ci0, co0, Cin, Cout);
 }
 
 // Weight gradient of the same single-input-channel conv (+ its 1x1x1 branch): dw[co][tap] = sum_v dy[v, co] x[v + off(tap)],
@@ -1865,11 +1706,10 @@ conv3_c1_wgrad_kernel(const float* __restrict__ x, const uint16_t* __restrict__ 
     uint16_t* win = (uint16_t*)lds;
     char* yimg = lds + WINB;
     char* y3img = yimg + NVOX * PY;
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), c = lane & 15, g = lane >> 4;
     const bool has3 = dy3 != nullptr;
-    const int q = c >> 2, p = c & 3;
-    const int ylane0 = lay_flip(8 * g + q) * PY + 8 * p, ylane1 = lay_flip(8 * g + q + 4) * PY + 8 * p;
+    TrLanes<1> tl;                                            // (ylane0/1: the dy tiles are read as in conv3_wgrad_kernel)
+    tr_lanes<PY, PY>(tl, wv, c, g);
     // window element offset of this lane's column (tap 16 tt + c; taps >= 27 alias the centre) + its voxel row / half row
     int toff[2];
 #pragma unroll
@@ -1931,16 +1771,9 @@ conv3_c1_wgrad_kernel(const float* __restrict__ x, const uint16_t* __restrict__ 
         for (int h = 0; h < 2; ++h) {
             const int kb = wv + 4 * h;                            // this wave's k-block: voxels 32 kb .. 32 kb + 31
             const int ykb = kb * 32 * PY;
-            s16x4 alo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(yimg + ykb + ylane0));
-            s16x4 ahi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(yimg + ykb + ylane1));
-            const s16x8 a8 = {alo[0], alo[1], alo[2], alo[3], ahi[0], ahi[1], ahi[2], ahi[3]};
+            const u32x4 af = tr2(yimg, ykb + tl.ylane0, ykb + tl.ylane1);
             u32x4 af3 = {0u, 0u, 0u, 0u};
-            if (has3) {
-                s16x4 clo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(y3img + ykb + ylane0));
-                s16x4 chi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(y3img + ykb + ylane1));
-                const s16x8 c8 = {clo[0], clo[1], clo[2], clo[3], chi[0], chi[1], chi[2], chi[3]};
-                af3 = __builtin_bit_cast(u32x4, c8);
-            }
+            if (has3) af3 = tr2(y3img, ykb + tl.ylane0, ykb + tl.ylane1);
             const uint16_t* wb = win + ((kb >> 1) * HY + (kb & 1) * 2) * HX;      // window row of the k-block's first voxel row
             u32x4 bf[2];
 #pragma unroll
@@ -1951,8 +1784,8 @@ conv3_c1_wgrad_kernel(const float* __restrict__ x, const uint16_t* __restrict__ 
 #pragma unroll
                 for (int d = 0; d < 4; ++d) bf[t2][d] = (uint32_t)b8[2 * d] | ((uint32_t)b8[2 * d + 1] << 16);
             }
-            PrecBF16::mma(acc[0], __builtin_bit_cast(u32x4, a8), bf[0]);
-            PrecBF16::mma(acc[1], __builtin_bit_cast(u32x4, a8), bf[1]);
+            PrecBF16::mma(acc[0], af, bf[0]);
+            PrecBF16::mma(acc[1], af, bf[1]);
             if (has3) PrecBF16::mma(acc3, af3, bf[1]);
         }
         tx = ax; ty = ay; tz = az; b = ab;
@@ -2030,6 +1863,12 @@ __global__ void tr16_probe_kernel(const uint16_t* __restrict__ in, uint16_t* __r
 
 // the pair layout is used for bf16 with <= 16 contraction channels (K = Cin forward, Cout for the data gradient)
 template <class P> inline bool use_pair(int K) { return P::CH == 8 && K <= 16; }
+
+// UNETR_TEST_MAX_WG (test hook, long tile walks): an upper bound on the workgroups of a persistent grid
+inline long test_max_wg(long G) {
+    if (const char* e = getenv("UNETR_TEST_MAX_WG")) { if (atoi(e) > 0) G = std::min<long>(G, atoi(e)); }
+    return G;
+}
 
 // ---- all weight re-packs of a step in ONE launch (run by the optimizer right after the update) ---------------------------
 // kind 0 / 1: 3x3x3 forward / data-gradient layout (pair layout when the contraction has <= 16 channels in bf16),
@@ -2157,35 +1996,26 @@ int fwd_t(const void* x, long ldx, const void* wp, void* yv, long ldy, int accum
     }
     if (B16 && fz && fz->k3 > 0 && ((fz->ldy3 & 7) || ((uintptr_t)fz->y3 & 15) || (fz->k3 & 7))) return UNETR_ERR_UNSUPPORTED;
     if ((long)D * H * W * ldx >= (1L << 31)) return UNETR_ERR_UNSUPPORTED;      // 32-bit in-item offsets (halo_load)
-    // persistent grid: at most cap resident workgroups (UNETR_TEST_MAX_WG: test hook, long tile walks).  A workgroup that walks several
+    // persistent grid: at most cap resident workgroups.  A workgroup that walks several
     // tiles must see them in non-decreasing batch order (the fused statistics are flushed when the batch item changes): tile_coords
     // guarantees that for grids that are multiples of the 8 XCDs
     auto grid_x = [&](long cap) {
-        if (const char* e = getenv("UNETR_TEST_MAX_WG")) { if (atoi(e) > 0) cap = std::min<long>(cap, atoi(e)); }
+        cap = test_max_wg(cap);
         if (cap < spatial) cap = std::max<long>(8, cap / 8 * 8);
         return (unsigned)std::min<long>(spatial, cap);
     };
-    if constexpr (B16) {
+    if constexpr (B16 || std::is_same<P, PrecBF16x3>::value) {
         // the single-channel image -> 16 channels with fused statistics (and the 1x1x1 branch): the dedicated one-MFMA kernel
-        if (x_f32 && Cin == 1 && Cout == 16 && ldx == 1 && fz && fz->k3 == 0 && !accumulate && use_pair<P>(Cin) &&
-            ntx < 256 && nty < 256 && ntz < 256 && B < 256 && (ldy & 3) == 0 && ((uintptr_t)y & 7) == 0 && (long)D * H * W < (1L << 31) &&
-            (!fz->y3 || (((uintptr_t)fz->y3 & 7) == 0 && fz->ldy3 == ldy)) && !getenv("UNETR_CONV_C1_OFF")) {
+        // (bf16x3: the same form on split operands); four channels per store
+        constexpr uintptr_t al = 4 * sizeof(YT) - 1;
+        if ((x_f32 || !B16) && Cin == 1 && Cout == 16 && ldx == 1 && fz && fz->k3 == 0 && !accumulate &&
+            ntx < 256 && nty < 256 && ntz < 256 && B < 256 && (ldy & 3) == 0 && ((uintptr_t)y & al) == 0 && (long)D * H * W < (1L << 31) &&
+            (!fz->y3 || (((uintptr_t)fz->y3 & al) == 0 && fz->ldy3 == ldy)) && !getenv("UNETR_CONV_C1_OFF")) {
+            typedef typename ElemOf<P>::type WT;
             const unsigned gx = grid_x(1024);
             fz->rows = (int)gx;
-            hipLaunchKernelGGL(conv3_c1_fwd_kernel, dim3(gx), dim3(256), 0, st, (const float*)x, (const uint16_t*)wp, (uint16_t*)y, ldy, D, H, W,
-                               ntx, nty, ntz, (int)spatial, fz->part, (const uint16_t*)fz->wp3, (uint16_t*)fz->y3, fz->part3);
-            return unetr_check_launch();
-        }
-    }
-    if constexpr (std::is_same<P, PrecBF16x3>::value) {
-        // bf16x3: the same single-channel form on split operands
-        if (Cin == 1 && Cout == 16 && ldx == 1 && fz && fz->k3 == 0 && !accumulate && ntx < 256 && nty < 256 && ntz < 256 &&
-            B < 256 && (ldy & 3) == 0 && ((uintptr_t)y & 15) == 0 && (long)D * H * W < (1L << 31) &&
-            (!fz->y3 || (((uintptr_t)fz->y3 & 15) == 0 && fz->ldy3 == ldy)) && !getenv("UNETR_CONV_C1_OFF")) {
-            const unsigned gx = grid_x(1024);
-            fz->rows = (int)gx;
-            hipLaunchKernelGGL(conv3_c1_fwd_x3_kernel, dim3(gx), dim3(256), 0, st, (const float*)x, (const uint32_t*)wp, (float*)y, ldy, D, H, W,
-                               ntx, nty, ntz, (int)spatial, fz->part, (const uint32_t*)fz->wp3, (float*)fz->y3, fz->part3);
+            hipLaunchKernelGGL(conv3_c1_fwd_kernel<P>, dim3(gx), dim3(256), 0, st, (const float*)x, (const WT*)wp, y, ldy, D, H, W,
+                               ntx, nty, ntz, (int)spatial, fz->part, (const WT*)fz->wp3, (YT*)fz->y3, fz->part3);
             return unetr_check_launch();
         }
     }
@@ -2303,17 +2133,13 @@ int wgrad_t(const void* x, long ldx, const void* dyv, long lddy, float* dw, cons
                                (const float*)ws3, n3, dw3);
         return unetr_check_launch();
     };
-    auto max_wg = [](long G) {          // test hook: long tile walks
-        if (const char* e = getenv("UNETR_TEST_MAX_WG")) { if (atoi(e) > 0) G = std::min<long>(G, atoi(e)); }
-        return G;
-    };
     const int nci = cdiv(Cin, 16), nco = cdiv(Cout, 16);
     const long n = 27L * Cin * Cout, n3 = dy3 ? (long)Cin * Cout : 0;
     if constexpr (B16) {
         // the single-channel image (encoder1's first conv + its 1x1x1 branch): the dedicated tap-column kernel
         if (x_f32 && Cin == 1 && Cout == 16 && ldx == 1 && ((uintptr_t)dy & 15) == 0 && (lddy & 7) == 0 &&
             (!dy3 || (((uintptr_t)dy3 & 15) == 0 && (lddy3 & 7) == 0)) && (long)D * H * W < (1L << 31) && !getenv("UNETR_CONV_C1_OFF"))
-            return finish(max_wg(std::min<long>(1024, ntiles)), n, n3, false, [&](long G, float* ws3) {
+            return finish(test_max_wg(std::min<long>(1024, ntiles)), n, n3, false, [&](long G, float* ws3) {
                 hipLaunchKernelGGL(conv3_c1_wgrad_kernel, dim3((unsigned)G), dim3(256), 0, st, (const float*)x, (const uint16_t*)dy, lddy,
                                    (const uint16_t*)dy3, lddy3, ws, ws3, D, H, W, ntx, nty, ntz, (int)ntiles);
                 return UNETR_OK;
@@ -2327,7 +2153,7 @@ int wgrad_t(const void* x, long ldx, const void* dyv, long lddy, float* dw, cons
         const bool xq16 = ((uintptr_t)x & 15) == 0 && (ldx & 3) == 0 && (Cin & 3) == 0;
         const bool xs = Cin < 4;                 // the image: scalar window loads
         if (yq16 && (xq16 || xs) && !(e && atoi(e) == 0))
-            return finish(max_wg(std::min<long>(ntiles, std::max<long>(1, 512 / ((long)nci * nco)))), n, n3, true, [&](long G, float* ws3) {
+            return finish(test_max_wg(std::min<long>(ntiles, std::max<long>(1, 512 / ((long)nci * nco)))), n, n3, true, [&](long G, float* ws3) {
                 if (nci > 65535 || nco > 65535) return UNETR_ERR_ARG;
 #define X3W_GO(H3_, XS_) hipLaunchKernelGGL((conv3_wgrad_x3_kernel<H3_, XS_>), dim3((unsigned)G, nci, nco), dim3(256), 0, st, (const float*)x, ldx, (const float*)dy, lddy, ws, \
                                             (const float*)dy3, lddy3, ws3, D, H, W, Cin, Cout, ntx, nty, ntz, (int)ntiles)
@@ -2339,7 +2165,7 @@ int wgrad_t(const void* x, long ldx, const void* dyv, long lddy, float* dw, cons
     }
     // persistent workgroups: all of them resident at once
     const long G0 = std::min(std::max<long>(1, ((dy3 && !B16) ? 512 : 256 * WG_LB) / ((long)nci * nco)), ntiles);
-    return finish(max_wg(G0), n, n3, true, [&](long G, float* ws3) {
+    return finish(test_max_wg(G0), n, n3, true, [&](long G, float* ws3) {
         const int vecy3 = (dy3 && ((uintptr_t)dy3 & 15) == 0 && (lddy3 & 3) == 0 && (Cout & 3) == 0) ? 1 : 0;
         if (nci > 65535 || nco > 65535) return UNETR_ERR_ARG;
         int vecx = (((uintptr_t)x & 15) == 0 && (ldx & 3) == 0 && (Cin & 3) == 0) ? 1 : 0;      // XMX
@@ -2381,20 +2207,14 @@ extern "C" size_t unetr_conv3_packed_bytes(int Cin, int Cout, int mode, int prec
 
 extern "C" int unetr_conv3_pack_weight(const float* w, void* wpack, int Cin, int Cout, int mode, int prec, void* stream) {
     if (!w || !wpack || Cin <= 0 || Cout <= 0) return UNETR_ERR_ARG;
-    if (prec == UNETR_PREC_BF16) return pack_t<PrecBF16>(w, wpack, Cin, Cout, mode, (hipStream_t)stream);
-    if (prec == UNETR_PREC_F32) return pack_t<PrecF32>(w, wpack, Cin, Cout, mode, (hipStream_t)stream);
-    if (prec == UNETR_PREC_BF16X3) return pack_t<PrecBF16x3>(w, wpack, Cin, Cout, mode, (hipStream_t)stream);
-    return UNETR_ERR_ARG;
+    PREC_DISPATCH(prec, return pack_t<P>(w, wpack, Cin, Cout, mode, (hipStream_t)stream));
 }
 
 extern "C" int unetr_conv3_fwd(const void* x, long ldx, const void* wpack, void* y, long ldy, int accumulate,
                                int B, int D, int H, int W, int Cin, int Cout, int prec, void* stream) {
     if (!x || !wpack || !y || B <= 0) return UNETR_ERR_ARG;
     if (Cout % 16) return UNETR_ERR_UNSUPPORTED;
-    if (prec == UNETR_PREC_BF16) return fwd_t<PrecBF16>(x, ldx, wpack, y, ldy, accumulate, B, D, H, W, Cin, Cout, (hipStream_t)stream);
-    if (prec == UNETR_PREC_F32) return fwd_t<PrecF32>(x, ldx, wpack, y, ldy, accumulate, B, D, H, W, Cin, Cout, (hipStream_t)stream);
-    if (prec == UNETR_PREC_BF16X3) return fwd_t<PrecBF16x3>(x, ldx, wpack, y, ldy, accumulate, B, D, H, W, Cin, Cout, (hipStream_t)stream);
-    return UNETR_ERR_ARG;
+    PREC_DISPATCH(prec, return fwd_t<P>(x, ldx, wpack, y, ldy, accumulate, B, D, H, W, Cin, Cout, (hipStream_t)stream));
 }
 
 // Forward of the first half of MONAI's UnetResBlock in one launch (unetr.py:90-98 and the decoder blocks :135-174):
@@ -2412,10 +2232,7 @@ extern "C" int unetr_conv3_fwd_fused(const void* x, long ldx, const void* wpack,
     if (!ws || per * (w3pack ? 2 : 1) * sizeof(float) > ws_bytes) return UNETR_ERR_WORKSPACE;
     FuseArgs fz{ws, w3pack, y3, ldy3, w3pack ? ws + per : nullptr, 0, 0};
     int rc;
-    if (prec == UNETR_PREC_BF16) rc = fwd_t<PrecBF16>(x, ldx, wpack, y, ldy, 0, B, D, H, W, Cin, Cout, st, &fz, x_f32);
-    else if (prec == UNETR_PREC_F32) rc = fwd_t<PrecF32>(x, ldx, wpack, y, ldy, 0, B, D, H, W, Cin, Cout, st, &fz);
-    else if (prec == UNETR_PREC_BF16X3) rc = fwd_t<PrecBF16x3>(x, ldx, wpack, y, ldy, 0, B, D, H, W, Cin, Cout, st, &fz);
-    else return UNETR_ERR_ARG;
+    PREC_DISPATCH(prec, rc = fwd_t<P>(x, ldx, wpack, y, ldy, 0, B, D, H, W, Cin, Cout, st, &fz, x_f32));      // (x_f32 matters in bf16 mode only)
     if (rc) return rc;
     const long V = (long)D * H * W;
     if (w3pack) rc = unetr_instnorm_stats_finalize2(ws, ws + per, fz.rows, B, V, Cout, eps, stats, stats3, stream);      // one launch for both sets
@@ -2437,10 +2254,7 @@ extern "C" int unetr_conv3_fwd_parts(const void* x, long ldx, const void* wpack,
     hipStream_t st = (hipStream_t)stream;
     FuseArgs fz{part, w3pack, y3, ldy3, part3, 0, 0};
     int rc;
-    if (prec == UNETR_PREC_BF16) rc = fwd_t<PrecBF16>(x, ldx, wpack, y, ldy, 0, B, D, H, W, Cin, Cout, st, &fz, x_f32);
-    else if (prec == UNETR_PREC_F32) rc = fwd_t<PrecF32>(x, ldx, wpack, y, ldy, 0, B, D, H, W, Cin, Cout, st, &fz);
-    else if (prec == UNETR_PREC_BF16X3) rc = fwd_t<PrecBF16x3>(x, ldx, wpack, y, ldy, 0, B, D, H, W, Cin, Cout, st, &fz);
-    else return UNETR_ERR_ARG;
+    PREC_DISPATCH(prec, rc = fwd_t<P>(x, ldx, wpack, y, ldy, 0, B, D, H, W, Cin, Cout, st, &fz, x_f32));      // (x_f32 matters in bf16 mode only)
     if (rc) return rc;
     if (fz.rows <= 0 || fz.rows > UNETR_CONV3_MAX_ROWS) return UNETR_ERR_WORKSPACE;
     *rows_out = fz.rows;
@@ -2462,10 +2276,7 @@ extern "C" int unetr_conv3_dgrad_stats(const void* dy, long lddy, const void* wp
     FuseArgs fz{part, stats, const_cast<void*>(xn), ldxn, nullptr, 0, 0, 1};
     int rc;
     // the data gradient is the forward kernel with contraction over the conv's Cout channels and Cin outputs
-    if (prec == UNETR_PREC_BF16) rc = fwd_t<PrecBF16>(dy, lddy, wpack_dgrad, dx, lddx, 0, B, D, H, W, Cout, Cin, st, &fz);
-    else if (prec == UNETR_PREC_F32) rc = fwd_t<PrecF32>(dy, lddy, wpack_dgrad, dx, lddx, 0, B, D, H, W, Cout, Cin, st, &fz);
-    else if (prec == UNETR_PREC_BF16X3) rc = fwd_t<PrecBF16x3>(dy, lddy, wpack_dgrad, dx, lddx, 0, B, D, H, W, Cout, Cin, st, &fz);
-    else return UNETR_ERR_ARG;
+    PREC_DISPATCH(prec, rc = fwd_t<P>(dy, lddy, wpack_dgrad, dx, lddx, 0, B, D, H, W, Cout, Cin, st, &fz));
     if (rc) return rc;
     if (fz.rows <= 0 || fz.rows > UNETR_CONV3_MAX_ROWS) return UNETR_ERR_WORKSPACE;
     *rows_out = fz.rows;
@@ -2506,26 +2317,19 @@ extern "C" int unetr_conv3_pack_grouped(const unetr_pack_problem* probs, int n, 
             a.p[i] = PkProblem{q.w, q.out, q.Cin, q.Cout, q.kind, pair, blocks, total, staged};
             blocks += staged ? ((K + SL - 1) / SL) * cdiv(N, 8) : cdiv(total, 2048);
         }
-        if (prec == UNETR_PREC_BF16) hipLaunchKernelGGL((conv3_pack_grouped_kernel<uint16_t>), dim3(blocks), dim3(256), 0, st, a, SL);
-        else if (prec == UNETR_PREC_BF16X3) hipLaunchKernelGGL((conv3_pack_grouped_kernel<uint32_t>), dim3(blocks), dim3(256), 0, st, a, SL);
-        else hipLaunchKernelGGL((conv3_pack_grouped_kernel<float>), dim3(blocks), dim3(256), 0, st, a, SL);
+        PREC_DISPATCH(prec, hipLaunchKernelGGL((conv3_pack_grouped_kernel<typename ElemOf<P>::type>), dim3(blocks), dim3(256), 0, st, a, SL));
     }
     return unetr_check_launch();
 }
 
 static int pack_1x1(const float* w3, void* w3pack, int K, int N, int prec, int allow_pair, int transposed, hipStream_t st) {
     // rows n < N, contraction index k < K
-    if (prec == UNETR_PREC_BF16) {
-        const int pair = (allow_pair && use_pair<PrecBF16>(K)) ? 1 : 0;
-        hipLaunchKernelGGL((conv3_pack_1x1_kernel<uint16_t>), dim3(cdiv((long)((K + 31) / 32) * N * 32, 256)), dim3(256), 0, st, w3,
-                           (uint16_t*)w3pack, K, N, pair, 32, transposed);
-    } else if (prec == UNETR_PREC_BF16X3) {
-        hipLaunchKernelGGL((conv3_pack_1x1_kernel<uint32_t>), dim3(cdiv((long)((K + 15) / 16) * N * 16, 256)), dim3(256), 0, st, w3,
-                           (uint32_t*)w3pack, K, N, 0, 16, transposed);
-    } else if (prec == UNETR_PREC_F32) {
-        hipLaunchKernelGGL((conv3_pack_1x1_kernel<float>), dim3(cdiv((long)((K + 15) / 16) * N * 16, 256)), dim3(256), 0, st, w3,
-                           (float*)w3pack, K, N, 0, 16, transposed);
-    } else return UNETR_ERR_ARG;
+    PREC_DISPATCH(prec, {
+        typedef typename ElemOf<P>::type T;
+        const int SL = 4 * P::CH, pair = (allow_pair && use_pair<P>(K)) ? 1 : 0;      // (pair layout: bf16 only)
+        hipLaunchKernelGGL((conv3_pack_1x1_kernel<T>), dim3(cdiv((long)((K + SL - 1) / SL) * N * SL, 256)), dim3(256), 0, st, w3,
+                           (T*)w3pack, K, N, pair, SL, transposed);
+    });
     return unetr_check_launch();
 }
 
@@ -2552,10 +2356,7 @@ extern "C" int unetr_conv3_dgrad_fused(const void* dc1, long ld1, const void* wp
     }
     FuseArgs fz{nullptr, w3t, const_cast<void*>(dc3), ld3, nullptr, 0, Cout};
     // the data gradient is the same kernel with contraction over the block's Cout channels and Cin outputs
-    if (prec == UNETR_PREC_BF16) return fwd_t<PrecBF16>(dc1, ld1, wpack_dgrad, dx, lddx, 0, B, D, H, W, Cout, Cin, st, &fz);
-    if (prec == UNETR_PREC_F32) return fwd_t<PrecF32>(dc1, ld1, wpack_dgrad, dx, lddx, 0, B, D, H, W, Cout, Cin, st, &fz);
-    if (prec == UNETR_PREC_BF16X3) return fwd_t<PrecBF16x3>(dc1, ld1, wpack_dgrad, dx, lddx, 0, B, D, H, W, Cout, Cin, st, &fz);
-    return UNETR_ERR_ARG;
+    PREC_DISPATCH(prec, return fwd_t<P>(dc1, ld1, wpack_dgrad, dx, lddx, 0, B, D, H, W, Cout, Cin, st, &fz));
 }
 
 extern "C" int unetr_conv3_wgrad(const void* x, long ldx, const void* dy, long ldy, float* dw,
@@ -2563,22 +2364,18 @@ extern "C" int unetr_conv3_wgrad(const void* x, long ldx, const void* dy, long l
                                  int B, int D, int H, int W, int Cin, int Cout, int prec, int x_f32,
                                  float* ws, size_t ws_bytes, void* stream) {
     if (!x || !dy || !dw || B <= 0 || ((dy3 != nullptr) != (dw3 != nullptr))) return UNETR_ERR_ARG;
-    if (prec == UNETR_PREC_BF16) return wgrad_t<PrecBF16>(x, ldx, dy, ldy, dw, dy3, ldy3, dw3, B, D, H, W, Cin, Cout, ws, ws_bytes, (hipStream_t)stream, x_f32);
-    if (prec == UNETR_PREC_F32) return wgrad_t<PrecF32>(x, ldx, dy, ldy, dw, dy3, ldy3, dw3, B, D, H, W, Cin, Cout, ws, ws_bytes, (hipStream_t)stream);
-    if (prec == UNETR_PREC_BF16X3) return wgrad_t<PrecBF16x3>(x, ldx, dy, ldy, dw, dy3, ldy3, dw3, B, D, H, W, Cin, Cout, ws, ws_bytes, (hipStream_t)stream);
-    return UNETR_ERR_ARG;
+    PREC_DISPATCH(prec, return wgrad_t<P>(x, ldx, dy, ldy, dw, dy3, ldy3, dw3, B, D, H, W, Cin, Cout, ws, ws_bytes, (hipStream_t)stream, x_f32));
 }
 
 // number of partial rows unetr_conv3_wgrad_parts writes for this shape (< 0: the shape is not supported)
 extern "C" long unetr_conv3_wgrad_rows(int B, int D, int H, int W, int Cin, int Cout, int prec, int x_f32, int has3) {
     long rows = -1;
     const void* dummy = (const void*)(uintptr_t)256;           // (aligned, never dereferenced: rows_only returns before any launch)
-    int rc = UNETR_ERR_ARG;
     const long ldx = x_f32 && Cin == 1 ? 1 : (Cin + 7) / 8 * 8;
-    if (prec == UNETR_PREC_BF16) rc = wgrad_t<PrecBF16>(dummy, ldx, dummy, Cout, nullptr, has3 ? dummy : nullptr, Cout, nullptr, B, D, H, W, Cin, Cout, nullptr, 0, nullptr, x_f32, true, &rows);
-    else if (prec == UNETR_PREC_F32) rc = wgrad_t<PrecF32>(dummy, ldx, dummy, Cout, nullptr, has3 ? dummy : nullptr, Cout, nullptr, B, D, H, W, Cin, Cout, nullptr, 0, nullptr, 0, true, &rows);
-    else if (prec == UNETR_PREC_BF16X3) rc = wgrad_t<PrecBF16x3>(dummy, ldx, dummy, Cout, nullptr, has3 ? dummy : nullptr, Cout, nullptr, B, D, H, W, Cin, Cout, nullptr, 0, nullptr, 0, true, &rows);
-    return rc == UNETR_OK ? rows : -1;
+    auto run = [&]() -> int {                                  // (x_f32 matters in bf16 mode only)
+        PREC_DISPATCH(prec, return wgrad_t<P>(dummy, ldx, dummy, Cout, nullptr, has3 ? dummy : nullptr, Cout, nullptr, B, D, H, W, Cin, Cout, nullptr, 0, nullptr, x_f32, true, &rows));
+    };
+    return run() == UNETR_OK ? rows : -1;
 }
 
 // unetr_conv3_wgrad without its reduce launch: the per-workgroup partial sums stay in `part` -- [rows][27 Cin Cout] followed, when dy3
@@ -2589,10 +2386,7 @@ extern "C" int unetr_conv3_wgrad_parts(const void* x, long ldx, const void* dy, 
     if (!x || !dy || !part || !rows_out || B <= 0) return UNETR_ERR_ARG;
     float* dummy3 = dy3 ? part : nullptr;                        // (dw / dw3 are not written in this form)
     hipStream_t st = (hipStream_t)stream;
-    if (prec == UNETR_PREC_BF16) return wgrad_t<PrecBF16>(x, ldx, dy, ldy, part, dy3, ldy3, dummy3, B, D, H, W, Cin, Cout, part, part_bytes, st, x_f32, true, nullptr, rows_out);
-    if (prec == UNETR_PREC_F32) return wgrad_t<PrecF32>(x, ldx, dy, ldy, part, dy3, ldy3, dummy3, B, D, H, W, Cin, Cout, part, part_bytes, st, 0, true, nullptr, rows_out);
-    if (prec == UNETR_PREC_BF16X3) return wgrad_t<PrecBF16x3>(x, ldx, dy, ldy, part, dy3, ldy3, dummy3, B, D, H, W, Cin, Cout, part, part_bytes, st, 0, true, nullptr, rows_out);
-    return UNETR_ERR_ARG;
+    PREC_DISPATCH(prec, return wgrad_t<P>(x, ldx, dy, ldy, part, dy3, ldy3, dummy3, B, D, H, W, Cin, Cout, part, part_bytes, st, x_f32, true, nullptr, rows_out));
 }
 
 extern "C" int unetr_debug_tr16(const void* in, void* out, void* stream) {

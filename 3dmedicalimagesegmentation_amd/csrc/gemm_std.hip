@@ -67,14 +67,7 @@ extern "C" int unetr_gemm_grouped_wgrad(const unetr_grouped_problem* probs, int 
             g.tile0 = tiles; g.mtiles = cdiv(q.N, BM);
             tiles += g.mtiles * cdiv(q.K, BN);
         }
-        if (prec == UNETR_PREC_BF16)
-            hipLaunchKernelGGL((gemm_grouped_wgrad_kernel<PrecBF16, 4, 4, 2, 2>), dim3(tiles), dim3(256), 0, st, ga);
-        else if (prec == UNETR_PREC_F32)
-            hipLaunchKernelGGL((gemm_grouped_wgrad_kernel<PrecF32, 4, 4, 2, 2>), dim3(tiles), dim3(256), 0, st, ga);
-        else if (prec == UNETR_PREC_BF16X3)
-            hipLaunchKernelGGL((gemm_grouped_wgrad_kernel<PrecBF16x3, 4, 4, 2, 2>), dim3(tiles), dim3(256), 0, st, ga);
-        else
-            return UNETR_ERR_ARG;
+        PREC_DISPATCH(prec, hipLaunchKernelGGL((gemm_grouped_wgrad_kernel<P, 4, 4, 2, 2>), dim3(tiles), dim3(256), 0, st, ga));
     }
     return unetr_check_launch();
 }

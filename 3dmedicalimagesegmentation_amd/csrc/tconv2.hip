@@ -27,11 +27,6 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 #define LDS_AS3 __attribute__((address_space(3)))
 
-template <class P> struct Elem;
-template <> struct Elem<PrecF32> { typedef float type; };
-template <> struct Elem<PrecBF16> { typedef uint16_t type; };
-template <> struct Elem<PrecBF16x3> { typedef float type; };
-
 constexpr int TV = 64;   // input voxels per tile
 
 // output-voxel index (in units of output voxels) of tap (0,0,0) of input voxel m
@@ -45,9 +40,9 @@ __device__ __forceinline__ int out_base(int m, int D, int H, int W) {
 // over voxel tiles g, g+G, ...   RT = Cin/16 row tiles, CTW = column tiles per wave (NC = 64*CTW).
 template <class P, int RT, int CTW>
 __global__ void __launch_bounds__(256)
-tconv2_wgrad_kernel(const typename Elem<P>::type* __restrict__ x, long ldx, const typename Elem<P>::type* __restrict__ dy, long lddy,
+tconv2_wgrad_kernel(const typename ActOf<P>::type* __restrict__ x, long ldx, const typename ActOf<P>::type* __restrict__ dy, long lddy,
                     float* __restrict__ part, int M, int D, int H, int W, int Cin, int Cout, int ntiles) {
-    typedef typename Elem<P>::type T;
+    typedef typename ActOf<P>::type T;
     constexpr int ES = sizeof(T), CH = P::CH, NC = 64 * CTW;
     constexpr int PXI = RT * 16 * ES + 16, PYI = NC * ES + 16;          // image pitches (bytes), padded
     __shared__ __attribute__((aligned(16))) char lds[TV * PXI + TV * PYI + TV * 4];
@@ -204,9 +199,9 @@ tconv2_reduce_kernel(const float* __restrict__ part, int G, long n, float* __res
 // KB = k-blocks of 4 chunks (64 bytes) per row; NT = 16-column tiles (= 8*Cout/16).  Each wave: 16 voxels x all columns.
 template <class P, int KB, int NT>
 __global__ void __launch_bounds__(256)
-tconv2_fwd_kernel(const typename Elem<P>::type* __restrict__ x, long ldx, const float* __restrict__ w, typename Elem<P>::type* __restrict__ y, long ldy,
+tconv2_fwd_kernel(const typename ActOf<P>::type* __restrict__ x, long ldx, const float* __restrict__ w, typename ActOf<P>::type* __restrict__ y, long ldy,
                   int M, int D, int H, int W, int Cin, int Cout, int ntiles) {
-    typedef typename Elem<P>::type T;
+    typedef typename ActOf<P>::type T;
     constexpr int CH = P::CH, RB = KB * 64;              // bytes per operand row
     constexpr int PA = RB + 16;                          // padded pitches
     __shared__ __attribute__((aligned(16))) char lds[NT * 16 * PA + TV * PA + TV * 4];
@@ -301,9 +296,9 @@ tconv2_fwd_kernel(const typename Elem<P>::type* __restrict__ x, long ldx, const 
 // row-major in k (plain b128 fragment reads); wd[ci][k] is resident in LDS.  NT = Cin/16 column tiles per wave.
 template <class P, int NT>
 __global__ void __launch_bounds__(256)
-tconv2_dgrad_kernel(const typename Elem<P>::type* __restrict__ dy, long lddy, const float* __restrict__ w, typename Elem<P>::type* __restrict__ dx, long ldx,
+tconv2_dgrad_kernel(const typename ActOf<P>::type* __restrict__ dy, long lddy, const float* __restrict__ w, typename ActOf<P>::type* __restrict__ dx, long ldx,
                     int M, int D, int H, int W, int Cin, int Cout, int ntiles) {
-    typedef typename Elem<P>::type T;
+    typedef typename ActOf<P>::type T;
     constexpr int ES = sizeof(T), CH = P::CH;
     extern __shared__ __attribute__((aligned(16))) char dlds[];
     const int K = 8 * Cout, RB = K * ES, PA = RB + 16, KB = RB / 64, QY = K / CH;
@@ -377,13 +372,13 @@ tconv2_dgrad_kernel(const typename Elem<P>::type* __restrict__ dy, long lddy, co
 }
 
 template <class P, int RT, int CTW>
-void launch_wgrad(int G, int NG, const typename Elem<P>::type* x, long ldx, const typename Elem<P>::type* dy, long lddy, float* ws, int M, int D, int H, int W,
+void launch_wgrad(int G, int NG, const typename ActOf<P>::type* x, long ldx, const typename ActOf<P>::type* dy, long lddy, float* ws, int M, int D, int H, int W,
                   int Cin, int Cout, int ntiles, hipStream_t st) {
     hipLaunchKernelGGL((tconv2_wgrad_kernel<P, RT, CTW>), dim3(G, NG), dim3(256), 0, st, x, ldx, dy, lddy, ws, M, D, H, W, Cin, Cout, ntiles);
 }
 
 template <class P>
-int wgrad2(const typename Elem<P>::type* x, long ldx, const typename Elem<P>::type* dy, long lddy, float* dw, int B, int D, int H, int W, int Cin, int Cout,
+int wgrad2(const typename ActOf<P>::type* x, long ldx, const typename ActOf<P>::type* dy, long lddy, float* dw, int B, int D, int H, int W, int Cin, int Cout,
            float* ws, size_t ws_bytes, hipStream_t st, bool parts_only = false, long* rows_only = nullptr, long* rows_used = nullptr) {
     const long Ml = (long)B * D * H * W;
     const int M = (int)Ml, ntiles = cdiv(M, TV), N = 8 * Cout, RT = Cin / 16;
@@ -404,15 +399,15 @@ int wgrad2(const typename Elem<P>::type* x, long ldx, const typename Elem<P>::ty
 }
 
 template <class P, int KB, int NT>
-void launch_fwd(int G, const typename Elem<P>::type* x, long ldx, const float* w, typename Elem<P>::type* y, long ldy, int M, int D, int H, int W, int Cin, int Cout,
+void launch_fwd(int G, const typename ActOf<P>::type* x, long ldx, const float* w, typename ActOf<P>::type* y, long ldy, int M, int D, int H, int W, int Cin, int Cout,
                 int ntiles, hipStream_t st) {
     hipLaunchKernelGGL((tconv2_fwd_kernel<P, KB, NT>), dim3(G), dim3(256), 0, st, x, ldx, w, y, ldy, M, D, H, W, Cin, Cout, ntiles);
 }
 
 template <class P>
-int fwd2(const typename Elem<P>::type* x, long ldx, const float* w, typename Elem<P>::type* y, long ldy, int B, int D, int H, int W, int Cin, int Cout,
+int fwd2(const typename ActOf<P>::type* x, long ldx, const float* w, typename ActOf<P>::type* y, long ldy, int B, int D, int H, int W, int Cin, int Cout,
          float* ws, size_t ws_bytes, hipStream_t st) {
-    typedef typename Elem<P>::type T;
+    typedef typename ActOf<P>::type T;
     const int M = (int)((long)B * D * H * W), ntiles = cdiv(M, TV), N = 8 * Cout, NT = N / 16;
     const int SK = 4 * P::CH, KB = cdiv(Cin, SK), KP = KB * SK;      // k-block = 4 chunks = 64 bytes per operand row
     (void)ws; (void)ws_bytes; (void)KP;
@@ -425,9 +420,9 @@ int fwd2(const typename Elem<P>::type* x, long ldx, const float* w, typename Ele
 }
 
 template <class P>
-int dgrad2(const typename Elem<P>::type* dy, long lddy, const float* w, typename Elem<P>::type* dx, long ldx, int B, int D, int H, int W, int Cin, int Cout,
+int dgrad2(const typename ActOf<P>::type* dy, long lddy, const float* w, typename ActOf<P>::type* dx, long ldx, int B, int D, int H, int W, int Cin, int Cout,
            float* ws, size_t ws_bytes, hipStream_t st) {
-    typedef typename Elem<P>::type T;
+    typedef typename ActOf<P>::type T;
     const int M = (int)((long)B * D * H * W), ntiles = cdiv(M, TV), K = 8 * Cout, NT = cdiv(Cin, 16);
     const int RB = K * (int)sizeof(T), PA = RB + 16;
     const size_t lds = (size_t)NT * 16 * PA + (size_t)TV * PA + TV * 4;
@@ -463,13 +458,9 @@ extern "C" int unetr_tconv2_wgrad(const void* x, long ldx, const void* dy, long 
     if (!x || !dy || !dw) return UNETR_ERR_ARG;
     if (!unetr_tconv2_wgrad_supported((long)B * D * H * W, Cin, Cout, ldx, lddy) || ((uintptr_t)x & 15) || ((uintptr_t)dy & 15))
         return UNETR_ERR_UNSUPPORTED;
-    if (prec == UNETR_PREC_BF16) {
-        if ((ldx & 7) || (lddy & 7)) return UNETR_ERR_UNSUPPORTED;       // bf16 rows: 16-byte chunks
-        return wgrad2<PrecBF16>((const uint16_t*)x, ldx, (const uint16_t*)dy, lddy, dw, B, D, H, W, Cin, Cout, ws, ws_bytes, (hipStream_t)stream);
-    }
-    if (prec == UNETR_PREC_F32) return wgrad2<PrecF32>((const float*)x, ldx, (const float*)dy, lddy, dw, B, D, H, W, Cin, Cout, ws, ws_bytes, (hipStream_t)stream);
-    if (prec == UNETR_PREC_BF16X3) return wgrad2<PrecBF16x3>((const float*)x, ldx, (const float*)dy, lddy, dw, B, D, H, W, Cin, Cout, ws, ws_bytes, (hipStream_t)stream);
-    return UNETR_ERR_ARG;
+    if (prec == UNETR_PREC_BF16 && ((ldx & 7) || (lddy & 7))) return UNETR_ERR_UNSUPPORTED;       // bf16 rows: 16-byte chunks
+    PREC_DISPATCH(prec, typedef typename ActOf<P>::type AT;
+                  return wgrad2<P>((const AT*)x, ldx, (const AT*)dy, lddy, dw, B, D, H, W, Cin, Cout, ws, ws_bytes, (hipStream_t)stream));
 }
 
 // partial rows of unetr_tconv2_wgrad_parts for this shape (< 0: unsupported)
@@ -488,13 +479,9 @@ extern "C" int unetr_tconv2_wgrad_parts(const void* x, long ldx, const void* dy,
     if (!unetr_tconv2_wgrad_supported((long)B * D * H * W, Cin, Cout, ldx, lddy) || ((uintptr_t)x & 15) || ((uintptr_t)dy & 15))
         return UNETR_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    if (prec == UNETR_PREC_BF16) {
-        if ((ldx & 7) || (lddy & 7)) return UNETR_ERR_UNSUPPORTED;
-        return wgrad2<PrecBF16>((const uint16_t*)x, ldx, (const uint16_t*)dy, lddy, part, B, D, H, W, Cin, Cout, part, part_bytes, st, true, nullptr, rows_out);
-    }
-    if (prec == UNETR_PREC_F32) return wgrad2<PrecF32>((const float*)x, ldx, (const float*)dy, lddy, part, B, D, H, W, Cin, Cout, part, part_bytes, st, true, nullptr, rows_out);
-    if (prec == UNETR_PREC_BF16X3) return wgrad2<PrecBF16x3>((const float*)x, ldx, (const float*)dy, lddy, part, B, D, H, W, Cin, Cout, part, part_bytes, st, true, nullptr, rows_out);
-    return UNETR_ERR_ARG;
+    if (prec == UNETR_PREC_BF16 && ((ldx & 7) || (lddy & 7))) return UNETR_ERR_UNSUPPORTED;
+    PREC_DISPATCH(prec, typedef typename ActOf<P>::type AT;
+                  return wgrad2<P>((const AT*)x, ldx, (const AT*)dy, lddy, part, B, D, H, W, Cin, Cout, part, part_bytes, st, true, nullptr, rows_out));
 }
 
 extern "C" int unetr_tconv2_fwd(const void* x, long ldx, const float* w, void* y, long ldy, int B, int D, int H, int W,
@@ -502,13 +489,9 @@ extern "C" int unetr_tconv2_fwd(const void* x, long ldx, const float* w, void* y
     if (!x || !w || !y) return UNETR_ERR_ARG;
     if (!unetr_tconv2_fwd_supported((long)B * D * H * W, Cin, Cout, ldx, ldy) || ((uintptr_t)x & 15)) return UNETR_ERR_UNSUPPORTED;
     if ((uintptr_t)y & (prec == UNETR_PREC_BF16 ? 7 : 15)) return UNETR_ERR_UNSUPPORTED;      // four channels per store
-    if (prec == UNETR_PREC_BF16) {
-        if (ldx & 7) return UNETR_ERR_UNSUPPORTED;
-        return fwd2<PrecBF16>((const uint16_t*)x, ldx, w, (uint16_t*)y, ldy, B, D, H, W, Cin, Cout, ws, ws_bytes, (hipStream_t)stream);
-    }
-    if (prec == UNETR_PREC_F32) return fwd2<PrecF32>((const float*)x, ldx, w, (float*)y, ldy, B, D, H, W, Cin, Cout, ws, ws_bytes, (hipStream_t)stream);
-    if (prec == UNETR_PREC_BF16X3) return fwd2<PrecBF16x3>((const float*)x, ldx, w, (float*)y, ldy, B, D, H, W, Cin, Cout, ws, ws_bytes, (hipStream_t)stream);
-    return UNETR_ERR_ARG;
+    if (prec == UNETR_PREC_BF16 && (ldx & 7)) return UNETR_ERR_UNSUPPORTED;
+    PREC_DISPATCH(prec, typedef typename ActOf<P>::type AT;
+                  return fwd2<P>((const AT*)x, ldx, w, (AT*)y, ldy, B, D, H, W, Cin, Cout, ws, ws_bytes, (hipStream_t)stream));
 }
 
 extern "C" int unetr_tconv2_dgrad(const void* dy, long lddy, const float* w, void* dx, long ldx, int accumulate,
@@ -518,13 +501,9 @@ extern "C" int unetr_tconv2_dgrad(const void* dy, long lddy, const float* w, voi
     if (accumulate || M < 2048 || M >= (1L << 27) || Cin < 8 || Cin > 64 || Cout % 8 || Cout < 8 || Cout > 32 ||
         (lddy & 3) || ((uintptr_t)dy & 15) || (Cin & 3) || (ldx & 3) || ((uintptr_t)dx & (prec == UNETR_PREC_BF16 ? 7 : 15)))
         return UNETR_ERR_UNSUPPORTED;
-    if (prec == UNETR_PREC_BF16) {
-        if (lddy & 7) return UNETR_ERR_UNSUPPORTED;
-        return dgrad2<PrecBF16>((const uint16_t*)dy, lddy, w, (uint16_t*)dx, ldx, B, D, H, W, Cin, Cout, ws, ws_bytes, (hipStream_t)stream);
-    }
-    if (prec == UNETR_PREC_F32) return dgrad2<PrecF32>((const float*)dy, lddy, w, (float*)dx, ldx, B, D, H, W, Cin, Cout, ws, ws_bytes, (hipStream_t)stream);
-    if (prec == UNETR_PREC_BF16X3) return dgrad2<PrecBF16x3>((const float*)dy, lddy, w, (float*)dx, ldx, B, D, H, W, Cin, Cout, ws, ws_bytes, (hipStream_t)stream);
-    return UNETR_ERR_ARG;
+    if (prec == UNETR_PREC_BF16 && (lddy & 7)) return UNETR_ERR_UNSUPPORTED;
+    PREC_DISPATCH(prec, typedef typename ActOf<P>::type AT;
+                  return dgrad2<P>((const AT*)dy, lddy, w, (AT*)dx, ldx, B, D, H, W, Cin, Cout, ws, ws_bytes, (hipStream_t)stream));
 }
 
 // ---- the SMALL transposed convs (768 channels at 6^3, 64 / 128 channels at 12^3) as plain bf16-storage GEMMs ---------------
