@@ -9,12 +9,14 @@ from .losses import DiceCELoss, ranking_loss  # noqa: F401
 from .optim import AdamW  # noqa: F401
 from .inference import DiceMetric, SlidingWindowInferer, sliding_window_inference  # noqa: F401
 from .metrics import ConfusionMatrixMetric, HausdorffDistanceMetric  # noqa: F401
+from .postprocess import KeepLargestConnectedComponent, connected_components, remove_small_components  # noqa: F401
 from .train_step import TrainStep  # noqa: F401
 from .augment import RandCropAugment, VolumeCache  # noqa: F401
 from .preprocess import resample_orient  # noqa: F401
 from .functional import invalidate_weight_shadows  # noqa: F401
-from . import _capi, augment, ddp, functional, inference, metrics, preprocess, train_step  # noqa: F401
+from . import _capi, augment, ddp, functional, inference, metrics, postprocess, preprocess, train_step  # noqa: F401
 
 __all__ = ["UNETR", "UNETRLogits", "DiceCELoss", "ranking_loss", "AdamW", "default_precision", "sliding_window_inference",
            "SlidingWindowInferer", "DiceMetric", "ConfusionMatrixMetric", "HausdorffDistanceMetric", "TrainStep", "invalidate_weight_shadows",
-           "VolumeCache", "RandCropAugment", "resample_orient"]
+           "VolumeCache", "RandCropAugment", "resample_orient", "KeepLargestConnectedComponent", "connected_components",
+           "remove_small_components"]

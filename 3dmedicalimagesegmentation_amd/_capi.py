@@ -183,6 +183,7 @@ _SIGNATURES = {
     "unetr_aug_sample": [ctypes.POINTER(AugDesc), P, c_int, P, P, P, P],
     "unetr_aug_gather": [ctypes.POINTER(AugDesc), P, c_int, P, P, P, P, c_size_t, P],
     "unetr_resample_orient": [P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_double), c_int, c_int, c_int, P, P, P],
+    "unetr_ccl": [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint, c_int, c_int, c_int, c_int, P, c_size_t, c_int, P],
     "unetr_ranking_loss_fwd": [P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P, P, P, c_size_t, P],
     "unetr_ranking_loss_bwd": [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P],
     "unetr_adamw": [P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_float, P, P, P],
@@ -191,7 +192,7 @@ _SIGNATURES = {
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + ("unetr_conv3_packed_bytes", "unetr_conv3_packed_1x1_bytes", "unetr_ranking_workspace_floats",
                                             "unetr_conv3_wgrad_rows", "unetr_tconv2_wgrad_rows", "unetr_outconv_in_bwd_rows", "unetr_hausdorff_workspace_bytes",
-                                            "unetr_aug_index_ws_ints", "unetr_aug_gather_ws_bytes")
+                                            "unetr_aug_index_ws_ints", "unetr_aug_gather_ws_bytes", "unetr_ccl_workspace_bytes")
 
 _lib = None
 
@@ -229,6 +230,8 @@ def load():
     lib.unetr_ranking_workspace_floats.restype = c_size_t
     lib.unetr_hausdorff_workspace_bytes.argtypes = [c_int] * 7
     lib.unetr_hausdorff_workspace_bytes.restype = c_size_t
+    lib.unetr_ccl_workspace_bytes.argtypes = [c_int] * 4
+    lib.unetr_ccl_workspace_bytes.restype = c_size_t
     lib.unetr_aug_index_ws_ints.argtypes = [c_long]
     lib.unetr_aug_index_ws_ints.restype = c_long
     lib.unetr_aug_gather_ws_bytes.argtypes = [ctypes.POINTER(AugDesc)]

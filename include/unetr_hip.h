@@ -525,6 +525,29 @@ int unetr_aug_gather(const UnetrAugDesc* d, const long long* vols, int nvol, con
 int unetr_resample_orient(const void* img, int img_int16, const unsigned char* lbl, int C, int L, int brats, int n0, int n1, int n2,
                           const double* mat, int D, int H, int W, float* oimg, unsigned char* olbl, void* stream);
 
+/* ---- connected-component post-processing (csrc/postprocess.hip; monai.transforms.KeepLargestConnectedComponent of MONAI 0.6.0
+ * and the min_size rule of skimage.morphology.remove_small_objects) ----
+ * unetr_ccl labels the 3-D connected components of in and filters them, per *plane* of class words w (0 = not filtered):
+ *   mode 0  class-id map [B,1,D,H,W] (float32, integral): one plane per item; w = id where bit id of applied is set
+ *           (ids 1..31; bit 0 must be clear), w = 1 for every applied id when independent = 0;
+ *   mode 1  one-hot / multi-label [B,C,D,H,W] (set where != 0): bit c of applied selects channel c; independent = 1: one plane
+ *           per (item, applied channel); independent = 0: one plane per item, w = 1 where any applied channel is set;
+ *   mode 2  logits [B,C,D,H,W]: first-maximum argmax (as unetr_sw_finalize_post) into out [B,1,D,H,W], then mode 0 in place.
+ * Voxels are connected when they are neighbours under connectivity (1: 6, 2: 18, 3: 26) and carry the same non-zero w.  The
+ * canonical label of a component is 1 + the smallest linear index (z*H + y)*W + x of its voxels.  rule 0 keeps, per (plane, w),
+ * the component with the most voxels (ties: the smallest label); rule 1 keeps components of at least min_size voxels.
+ * Outputs, each optional (NULL): out (layout of in; mode 2: [B,1,D,H,W], required) = in where w == 0 or the component is kept,
+ * else 0; labels / sizes (int32, layout of out) = canonical label / voxel count of the voxel's component, 0 where w == 0;
+ * ncomp [planes][32] (int32) = number of components per (plane, w).  Channels of mode 1 that are not applied are NOT written in
+ * any output.  C <= 16; D, H, W <= 1024 and D*H*W < 2^31 - 1, else UNETR_ERR_UNSUPPORTED.  ws holds
+ * unetr_ccl_workspace_bytes(D, H, W, group) bytes (0 for an unsupported shape): 9 B per voxel for each of the `group` planes
+ * processed together.  Integer atomics only: results are bit-reproducible.  No host synchronisation.
+ * (Additions: no existing signature moved, UNETR_ABI_VERSION stays.) */
+size_t unetr_ccl_workspace_bytes(int D, int H, int W, int group);
+int unetr_ccl(const float* in, float* out, int* labels, int* sizes, int* ncomp, int B, int C, int D, int H, int W, int mode,
+              unsigned applied, int independent, int connectivity, int rule, int min_size, void* ws, size_t ws_bytes, int group,
+              void* stream);
+
 /* ---- fused AdamW over one flat fp32 buffer (torch.optim.AdamW semantics; unetr_segmentation_3d.py:522) */
 int unetr_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                 float eps, float weight_decay, const float* step_dev,
