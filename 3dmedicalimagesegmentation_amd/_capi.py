@@ -54,6 +54,10 @@ class AdamWArena(ctypes.Structure):
                 ("shadow_x3", c_void_p)]
 
 
+class TransposeProblem(ctypes.Structure):
+    _fields_ = [("offset", c_long), ("N", c_int), ("K", c_int)]
+
+
 class PackProblem(ctypes.Structure):
     _fields_ = [("w", c_void_p), ("out", c_void_p), ("Cin", c_int), ("Cout", c_int), ("kind", c_int)]
 
@@ -111,6 +115,8 @@ _SIGNATURES = {
     "unetr_gemm_grouped_wgrad": [ctypes.POINTER(GroupedProblem), c_int, c_int, P],
     "unetr_gemm_bf16_grouped_wgrad": [ctypes.POINTER(GroupedProblem), c_int, P],
     "unetr_gemm_bf16_grouped_wgrad_adamw": [ctypes.POINTER(GroupedProblem), c_int, ctypes.POINTER(AdamWArena), ctypes.POINTER(c_int), P],
+    "unetr_gemm_bf16_grouped_wgrad_adamw_t": [ctypes.POINTER(GroupedProblem), c_int, ctypes.POINTER(AdamWArena), ctypes.POINTER(c_int), P, P],
+    "unetr_transpose_bf16_grouped": [P, P, ctypes.POINTER(TransposeProblem), c_int, P],
     "unetr_adamw_ranges": [ctypes.POINTER(AdamWArena), P, c_int, c_long, P],
     "unetr_gemm_bf16_grouped_wgrad_bf16out": [ctypes.POINTER(GroupedProblem), c_int, P, P, c_long, P],
     "unetr_cast_bf16_ranges": [P, P, P, c_int, c_long, P],

@@ -9,7 +9,8 @@
 //   C[M,N] (+)= alpha * A[M,K] . B^T + epilogue      A: bf16 [M,K] (k contiguous)
 //       b_kn = 0: B is bf16 [N,K] (k contiguous; forward  y = x W^T with W as stored by nn.Linear)
 //       b_kn = 1: B is bf16 [K,N] (n contiguous; data gradient dx = dy W with the same W) -- fragments come out of
-//                 LDS through ds_read_b64_tr_b16, the transposing read, so no transposed weight copy is kept
+//                 LDS through ds_read_b64_tr_b16, the transposing read, so no transposed weight copy is needed (where the fused
+//                 optimizer epilogue below keeps one anyway -- WT --, the data gradients run in the faster b_kn = 0 form on it)
 //
 // LDS image (both operands, b_kn = 0): row r of the tile is 128 bytes = 8 chunks of 8 bf16; chunk c of row r sits
 // in slot c ^ ((r >> 1) & 7).  An LDS-DMA writes wave-uniform base + lane * 16, i.e. lane-linear, so the swizzle
@@ -663,10 +664,12 @@ static int big_tile_width(int M, int N, int K) {
 constexpr int GW_MAX = 64;     // 12 blocks x 4 Linear layers + patch embedding in ONE launch
 struct GwProblem { const uint16_t* dy; const uint16_t* x; float* dw; int M, N, K, tile0, ntn, step_idx; };
 // FUSE: the arenas of the fused optimizer epilogue (dw then only NAMES the arena slice: element offset = dw - gb)
-struct GwFuse { float* pb; const float* gb; float* mb; float* vb; uint16_t* sb; const float* steps; float lr, b1, b2, eps, wd; uint32_t* sw; };
+// st: the transposed bf16 shadow arena (WT kernels only): weight [N, K] at offset o has its [K, N] twin at st + o
+struct GwFuse { float* pb; const float* gb; float* mb; float* vb; uint16_t* sb; const float* steps; float lr, b1, b2, eps, wd; uint32_t* sw; uint16_t* st; };
 struct GwArgs { int n; GwFuse f; GwProblem p[GW_MAX]; };
 
-template <int NS, int BKT, int FUSE>                        // BKT = tokens per stage (64 or 32); FUSE: 0 store dW, 1 AdamW, 2 store bf16(dW)
+// WT (FUSE 1 only): the epilogue also writes the updated weights, transposed, into the second bf16 shadow f.st
+template <int NS, int BKT, int FUSE, bool WT = false>       // BKT = tokens per stage (64 or 32); FUSE: 0 store dW, 1 AdamW, 2 store bf16(dW)
 __global__ void __launch_bounds__(256, GW_WAVES)
 gemm_bf16_grouped_wgrad_kernel(GwArgs ga) {
     constexpr int BT = 128;                                // output tile 128 x 128
@@ -765,6 +768,7 @@ gemm_bf16_grouped_wgrad_kernel(GwArgs ga) {
     const int kcol = k0 + wn * 64 + rc * 4;
     [[maybe_unused]] AdamWCoef c{};
     [[maybe_unused]] long off0 = 0;
+    [[maybe_unused]] u32x4 keep[4];
     if constexpr (FUSE == 1) {
         c = adamw_coef(ga.f.lr, ga.f.b1, ga.f.b2, ga.f.eps, ga.f.wd, ga.f.steps[pr.step_idx]);
         off0 = pr.dw - ga.f.gb;
@@ -808,7 +812,8 @@ gemm_bf16_grouped_wgrad_kernel(GwArgs ga) {
                 bool ok[2];
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
-                    const int r = (it + u) * 4 + rr, n = n0 + wm * 64 + h * 32 + r;
+                    // (WT: a lane takes two ADJACENT rows, so that it holds bf16 pairs along n for the transposed image below)
+                    const int r = WT ? it * 4 + 2 * rr + u : (it + u) * 4 + rr, n = n0 + wm * 64 + h * 32 + r;
                     ok[u] = n < pr.N && kcol < pr.K;
                     idx[u] = off0 + (long)n * pr.K + kcol;
                     gv[u] = *(const f32x4*)(stg + r * 256 + ((rc ^ (r & 15)) << 4));
@@ -832,6 +837,45 @@ gemm_bf16_grouped_wgrad_kernel(GwArgs ga) {
                     __builtin_nontemporal_store(vv[u], (f32x4*)(f.vb + idx[u]));
                     if (f.sb) *(bf16x4*)(f.sb + idx[u]) = __builtin_convertvector(pv[u], bf16x4);
                     if (f.sw) *(u32x4*)(f.sw + idx[u]) = x3_words(__builtin_bit_cast(u32x4, pv[u]));      // (bf16x3 mode: the word shadow)
+                }
+                if constexpr (WT) {
+                    // The 8 fp32 rows this pair of iterations has just consumed (2 KB of the staging image) take the bf16 results in
+                    // transposed order: 16-byte chunk (k = 4 rc + e) holds n = 8 (it / 2) + 0..7, the lane's two rows as one dword.
+                    // Chunk slot = (rc + 2 it) & 15 of the 256-byte line e: distinct banks for these writes and half 0's read-back.
+                    // (N % 8 == 0 and the rows are a pair inside one group of 8: ok[0] == ok[1])
+                    if (ok[0]) {
+                        const s16x4 b0 = __builtin_bit_cast(s16x4, __builtin_convertvector(pv[0], bf16x4));
+                        const s16x4 b1 = __builtin_bit_cast(s16x4, __builtin_convertvector(pv[1], bf16x4));
+                        char* const tp = stg + (it >> 1) * 2048 + (((rc + 2 * it) & 15) << 4) + rr * 4;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            *(uint32_t*)(tp + e * 256) = (uint32_t)(uint16_t)b0[e] | ((uint32_t)(uint16_t)b1[e] << 16);
+                    }
+                }
+            }
+            if constexpr (WT) {
+                // The twin's rows are written as whole 128-byte lines: half 0's transposed image (64 k rows x 32 n) waits in registers
+                // -- lane (kk = lane >> 2, nq = lane & 3) keeps chunk nq of rows 4 kk + e -- until half 1's image stands in LDS, goes
+                // back into the free second KB of each 2 KB region, and eight lanes then store one row's 64 n.  Measured on the 48
+                // weights of the ViT at 432 rows (tools/probe_gw.py; the plain fused launch: 409-455 us depending on the box): 64-byte
+                // pieces per half + 80 us, both halves' pieces back to back + 41-53, whole lines + 38, whole lines non-temporal + 32.
+                const int kk = lane >> 2, nq = lane & 3;
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // the lanes' image writes above, before other lanes read them
+                if (h == 0) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) keep[e] = *(const u32x4*)(stg + nq * 2048 + e * 256 + (((kk + 4 * nq) & 15) << 4));
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) *(u32x4*)(stg + nq * 2048 + 1024 + e * 256 + (((kk + 4 * nq) & 15) << 4)) = keep[e];
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // half 0's chunks stand in LDS before the line reads
+                    const int r8 = lane >> 3, c = lane & 7, q4 = c & 3;          // row within a group of 8, 16-byte chunk of the 128-byte line
+                    const int nc = n0 + wm * 64 + c * 8;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const int kl = j * 8 + r8, k = k0 + wn * 64 + kl;
+                        const u32x4 tv = *(const u32x4*)(stg + q4 * 2048 + (c < 4 ? 1024 : 0) + (kl & 3) * 256 + ((((kl >> 2) + 4 * q4) & 15) << 4));
+                        if (k < pr.K && nc < pr.N) __builtin_nontemporal_store(tv, (u32x4*)(f.st + off0 + (long)k * pr.N + nc));
+                    }
                 }
             }
         }
@@ -962,12 +1006,25 @@ static int gemm_bf16_impl(const unetr_gemm_bf16_desc* d, const void* A, const vo
     //   forward, K = 3072, N = 768: 64x64 + 4 split-K slabs 12.5 ~ 64x32 13.0 < 32x64 13.6 < 64x64 unsplit 16.3
     //   [K,N]-operand data gradients: K = 768: 32x64 (N = 768: 6.4, N = 3072: 11.8) < 64x64 (7.3, 13.1) < 64x128;
     //                                 K = 3072, N = 768: 64x64 + split-K 14.4 < 64x128 + split-K 16.6 < 32x64 24.9
+    //   data gradients in the forward form on the transposed weight twin (functional.weight_bf16_t; M <= 512 only: nothing is measured
+    //   above, and the two forms' K slabs differ there, so functional._dgrad_operand keeps the [K,N] form), against the [K,N] form's best:
+    //     du   N = 3072 K = 768:  64x32 9.7-9.9 ~ 32x64 9.7-9.8 < 64x64 10.1-10.3 < 64x96 11.0 < 64x128 12.9   ([K,N] 32x64: 11.1-11.5)
+    //     datt N = 768  K = 768:  64x32 5.3 < 32x64 5.5 < 64x64 6.5 < 64x96 8.4                                ([K,N] 32x64: 6.6)
+    //     dy2  N = 768  K = 3072: 64x64 + 4 slabs 12.5 < 64x96 12.9 < 64x32 13.0 (4 slabs; unsplit 12.0) < 32x64 13.1  ([K,N] 14.5)
+    //     dx   N = 768  K = 2304: 64x32 + 3 slabs 10.2 (unsplit 9.7) < 32x64 10.3 < 64x64 + 3 slabs 11.2 < 64x96 11.6  ([K,N] 12.6)
+    //   and the forward shapes with N > 1024 on the narrow tiles, which the first table never tried: qkv N = 2304: 32x64 6.5 ~ 64x32 6.6 <
+    //   64x64 7.2; linear1 N = 3072 (+ GELU, pre): 64x32 9.1 < 32x64 9.3 < 64x64 9.7
     // i.e. short reductions want the most workgroups (a CU pulls only ~70 GB/s from L2), long ones the 64x64 tile cut into
-    // K slabs.  cfg codes (UNETR_GEMM_CFG): 6464, 6432, 3264, 64128, 6496.
+    // K slabs.  The K-slab count of a shape is the same in both operand forms (the unsplit 64x32 variants of dy2 / dx are faster still,
+    // but the two forms then differ in their summation order: the step forms that read the twin and those that do not are held bit for
+    // bit).  cfg codes (UNETR_GEMM_CFG): 6464, 6432, 3264, 64128, 6496.
     int cfg = env_cfg;
     if (!big && (cfg == 0 || cfg == 64)) {
         cfg = 6464;
         if (env_cfg == 0 && K <= 1024 && N <= 1024) cfg = d->b_kn ? 3264 : 6432;
+        if (env_cfg == 0 && K <= 1024 && !d->b_kn && N > 1024 && M <= 512) cfg = 6432;
+        // (N = 768, K = 2304: fewer than 192 tiles of 64 x 32, so launch_bf16 cuts K into the slabs the 64 x 64 tile gets)
+        if (env_cfg == 0 && !d->b_kn && K > 1024 && K <= 2560 && N <= 1024 && M <= 512 && (long)cdiv(M, 64) * cdiv(N, 32) < 192) cfg = 6432;
         if (env_cfg == 0 && K <= 1024 && d->b_kn && N > 1024 && N % 64 == 0) cfg = 3264;
         // 512 < M < 1024 (batch 4 at 96^3: 864 rows, the ranking pre-training step; 160^3: 1000 rows): two 64 x 64 tiles per CU move
         // more bytes per CU than one wider tile.  Measured (tools/probe_encoder.py PROBE_M=864 / 1000, us): linear1 64x96 13.1 / 13.7
@@ -1167,9 +1224,12 @@ extern "C" int unetr_add_cast_bf16(const float* a, const float* b, float* out, v
 // dw_i[N_i, K_i] = dy_i[M_i, N_i]^T * x_i[M_i, K_i] on bf16-stored dy / x (dense row-major), one launch per <= 64 problems;
 // a: optimizer arenas -> the epilogue applies AdamW (step count a->steps[step_index[i]]) instead of storing dw;
 // b16: a with only grad / shadow_bf16 / total set -> the epilogue stores bf16(dw) at the arena offset of dw in shadow_bf16
+// shadow_t (AdamW form only, may be NULL): transposed bf16 shadow arena, written by the same epilogue
 static int grouped_wgrad_bf16(const unetr_grouped_problem* probs, int n, const unetr_adamw_arena* a, const int* step_index, void* stream,
-                              bool b16 = false) {
+                              bool b16 = false, void* shadow_t = nullptr) {
     if (!probs || n <= 0) return UNETR_ERR_ARG;
+    if (shadow_t && (!a || b16 || !a->shadow_bf16)) return UNETR_ERR_ARG;
+    if ((uintptr_t)shadow_t & 15) return UNETR_ERR_UNSUPPORTED;
     if (b16 && (!a || !a->grad || !a->shadow_bf16 || a->total <= 0 || ((uintptr_t)a->grad & 15) || ((uintptr_t)a->shadow_bf16 & 7))) return UNETR_ERR_ARG;
     if (a && !b16 && (!a->param || !a->grad || !a->m || !a->v || !a->steps || !step_index || a->total <= 0)) return UNETR_ERR_ARG;
     if (a && !b16 && ((((uintptr_t)a->param | (uintptr_t)a->grad | (uintptr_t)a->m | (uintptr_t)a->v) & 15) || ((uintptr_t)a->shadow_bf16 & 7))) return UNETR_ERR_UNSUPPORTED;
@@ -1179,7 +1239,7 @@ static int grouped_wgrad_bf16(const unetr_grouped_problem* probs, int n, const u
         ga.n = std::min(GW_MAX, n - base);
         ga.f = GwFuse{};
         if (a) ga.f = GwFuse{a->param, a->grad, a->m, a->v, (uint16_t*)a->shadow_bf16, a->steps, a->lr, a->beta1, a->beta2, a->eps, a->weight_decay,
-                             b16 ? nullptr : (uint32_t*)a->shadow_x3};
+                             b16 ? nullptr : (uint32_t*)a->shadow_x3, (uint16_t*)shadow_t};
         int tiles = 0;
         for (int i = 0; i < ga.n; ++i) {
             const unetr_grouped_problem& q = probs[base + i];
@@ -1188,6 +1248,7 @@ static int grouped_wgrad_bf16(const unetr_grouped_problem* probs, int n, const u
             if (a) {       // dw names a slice of the gradient arena
                 const long off = q.dw - a->grad;
                 if (q.dw < a->grad || off + (long)q.N * q.K > a->total || (!b16 && step_index[base + i] < 0)) return UNETR_ERR_ARG;
+                if (shadow_t && off % 8) return UNETR_ERR_UNSUPPORTED;          // 16-byte stores into the bf16 twin at this offset
             }
             GwProblem& g = ga.p[i];
             g.dy = (const uint16_t*)q.dy; g.x = (const uint16_t*)q.x; g.dw = q.dw; g.M = q.M; g.N = q.N; g.K = q.K;
@@ -1199,6 +1260,7 @@ static int grouped_wgrad_bf16(const unetr_grouped_problem* probs, int n, const u
         // K step (7-14 short steps per tile, operands out of HBM / MALL); measured at 432 rows (tools/probe_gw.py, us):
         // 64 tokens x 2 stages (two workgroups per CU) 201, 32 x 2 178, 32 x 3 190, 32 x 4 203, 64 x 3 268, 64 x 4 245
         if (b16) hipLaunchKernelGGL((gemm_bf16_grouped_wgrad_kernel<2, 32, 2>), dim3(tiles), dim3(256), 0, st, ga);
+        else if (a && shadow_t) hipLaunchKernelGGL((gemm_bf16_grouped_wgrad_kernel<2, 32, 1, true>), dim3(tiles), dim3(256), 0, st, ga);
         else if (a) hipLaunchKernelGGL((gemm_bf16_grouped_wgrad_kernel<2, 32, 1>), dim3(tiles), dim3(256), 0, st, ga);
         else hipLaunchKernelGGL((gemm_bf16_grouped_wgrad_kernel<2, 32, 0>), dim3(tiles), dim3(256), 0, st, ga);
     }
@@ -1220,4 +1282,78 @@ extern "C" int unetr_gemm_bf16_grouped_wgrad_adamw(const unetr_grouped_problem* 
                                                    const int* step_index, void* stream) {
     if (!a) return UNETR_ERR_ARG;
     return grouped_wgrad_bf16(probs, n, a, step_index, stream);
+}
+
+// the same launch, whose epilogue also keeps the transposed bf16 shadow current: the updated weight [N, K] at arena offset o is written
+// as [K, N] row-major at shadow_t + o (bf16 elements) next to its a->shadow_bf16 copy.  shadow_t == NULL is exactly the entry point above.
+extern "C" int unetr_gemm_bf16_grouped_wgrad_adamw_t(const unetr_grouped_problem* probs, int n, const unetr_adamw_arena* a,
+                                                     const int* step_index, void* shadow_t, void* stream) {
+    if (!a) return UNETR_ERR_ARG;
+    return grouped_wgrad_bf16(probs, n, a, step_index, stream, false, shadow_t);
+}
+
+// ---- transposed bf16 shadow: the derive launch -------------------------------------------------------------------------------
+// dst + off as [K, N] = transpose of src + off as [N, K], for a table of arena slices, in one launch: 64 x 64 tiles through LDS, 16-byte
+// global accesses on both sides (N, K multiples of 8: a chunk of 8 elements is inside the slice or outside it as a whole).
+namespace {
+constexpr int TR_MAX = 64;
+struct TrProblem { long off; int N, K, tile0, ntn; };
+struct TrArgs { int n; const uint16_t* src; uint16_t* dst; TrProblem p[TR_MAX]; };
+
+__global__ void __launch_bounds__(256) transpose_bf16_grouped_kernel(TrArgs a) {
+    constexpr int PITCH = 66;                           // uint16 elements per tile row: 33 dwords, odd -> column reads spread over the banks
+    __shared__ __attribute__((aligned(16))) uint16_t tile[64 * PITCH];
+    int pi = 0;
+    const int t = blockIdx.x;
+    for (int hi_ = a.n - 1; pi < hi_;) {
+        const int mid = (pi + hi_ + 1) >> 1;
+        if (t >= a.p[mid].tile0) pi = mid; else hi_ = mid - 1;
+    }
+    const TrProblem& pr = a.p[pi];
+    const int lt = t - pr.tile0, n0 = (lt % pr.ntn) * 64, k0 = (lt / pr.ntn) * 64;
+    const uint16_t* __restrict__ src = a.src + pr.off;
+    uint16_t* __restrict__ dst = a.dst + pr.off;
+    const int c = threadIdx.x & 7, r0 = threadIdx.x >> 3;       // 16-byte chunk of a 64-element row, row (two rows per thread)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int r = r0 + 32 * i, n = n0 + r, k = k0 + c * 8;
+        u32x4 v = (u32x4){0u, 0u, 0u, 0u};
+        if (n < pr.N && k < pr.K) v = *(const u32x4*)(src + (long)n * pr.K + k);
+        uint32_t* d = (uint32_t*)(tile + r * PITCH + c * 8);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d[e] = v[e];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int r = r0 + 32 * i, k = k0 + r, n = n0 + c * 8;      // output row k, columns n .. n + 7
+        if (k >= pr.K || n >= pr.N) continue;
+        u32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            v[e] = (uint32_t)tile[(c * 8 + 2 * e) * PITCH + r] | ((uint32_t)tile[(c * 8 + 2 * e + 1) * PITCH + r] << 16);
+        *(u32x4*)(dst + (long)k * pr.N + n) = v;
+    }
+}
+}  // namespace
+
+extern "C" int unetr_transpose_bf16_grouped(const void* src_arena, void* dst_arena, const unetr_transpose_problem* probs, int n, void* stream) {
+    if (!src_arena || !dst_arena || !probs || n <= 0) return UNETR_ERR_ARG;
+    if (((uintptr_t)src_arena | (uintptr_t)dst_arena) & 15) return UNETR_ERR_UNSUPPORTED;
+    for (int base = 0; base < n; base += TR_MAX) {
+        TrArgs a;
+        a.n = std::min(TR_MAX, n - base);
+        a.src = (const uint16_t*)src_arena; a.dst = (uint16_t*)dst_arena;
+        long tiles = 0;
+        for (int i = 0; i < a.n; ++i) {
+            const unetr_transpose_problem& q = probs[base + i];
+            if (q.offset < 0 || q.N < 8 || q.K < 8) return UNETR_ERR_ARG;
+            if (q.offset % 8 || q.N % 8 || q.K % 8) return UNETR_ERR_UNSUPPORTED;
+            a.p[i] = TrProblem{q.offset, q.N, q.K, (int)tiles, cdiv(q.N, 64)};
+            tiles += (long)cdiv(q.N, 64) * cdiv(q.K, 64);
+            if (tiles > 0x7fffffffL) return UNETR_ERR_ARG;
+        }
+        hipLaunchKernelGGL(transpose_bf16_grouped_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, a);
+    }
+    return unetr_check_launch();
 }

@@ -79,6 +79,7 @@ class ArenaState:
 
     def clear(self):
         self.fuse = None
+        drop_wt_shadow(getattr(self, "flat", None))
         for k in list(self.sinks):
             _GRAD_SINK.pop(k, None)
         self.sinks.clear()
@@ -220,7 +221,12 @@ def _launch_deferred(wq, cq, wbq=(), prec=0, fuse=None):
             if fuse.get("kind") == "bf16out":      # data-parallel step, bf16 communication: bf16(dW) straight into the comm buffer
                 call("unetr_gemm_bf16_grouped_wgrad_bf16out", arr, len(fused), fuse["grad"], fuse["out"], fuse["total"], _stream())
             else:
-                call("unetr_gemm_bf16_grouped_wgrad_adamw", arr, len(fused), ctypes.byref(fuse["arena"]), idx, _stream())
+                # (the transposed twins of the weights, if this model keeps them, are written by the same epilogue)
+                wt = fuse["flat"].get("shadow_t") if wt_enabled() and fuse.get("flat") is not None else None
+                call("unetr_gemm_bf16_grouped_wgrad_adamw_t", arr, len(fused), ctypes.byref(fuse["arena"]), idx,
+                     wt.data_ptr() if wt is not None else None, _stream())
+                if wt is not None:
+                    fuse["wt_done"].extend(pi for _, pi in fused)
             fuse["done"].extend(pi for _, pi in fused)
     if wbq:
         arr = (_capi.GroupedProblem * len(wbq))()
@@ -439,6 +445,8 @@ def invalidate_weight_shadows():
         ent[1] = -1
     for ent in _SHADOW_X3.values():
         ent[1] = -1
+    for ent in _SHADOW_T.values():
+        ent[1] = -1
     for ent in _PACKS.values():
         ent[1] = -1
 
@@ -513,6 +521,130 @@ def refresh_x3_shadow(flat, written=False):
         ent = _SHADOW_X3.get(id(p))
         if ent is not None and ent[2]() is p and ent[3] == p.data_ptr():
             ent[1] = p._version
+
+
+# ---- bf16 mode: transposed bf16 shadow of the ViT Linear weights -------------------------------------------------------------
+# The data gradients dx = dy . W read W [out, in] as the [K, N] operand (b_kn = 1: transposing LDS reads).  With flat arenas a second
+# bf16 arena holds every such weight transposed -- W [N, K] at arena offset o has its twin [K, N] at shadow_t + o -- and the data
+# gradient runs in the forward kernel form (b_kn = 0) on it.  The fused weight-gradient + AdamW launch writes the twin next to the
+# bf16 shadow (unetr_gemm_bf16_grouped_wgrad_adamw_t); every other optimizer step of this package re-derives the twins it has
+# invalidated in one grouped launch (refresh_wt_shadow).  Both forms give the same bits, so the arena is
+# only created where it is written for free: by a backward pass with the fused AdamW epilogue armed, outside graph capture.
+# Freshness: the rule of the word shadow above -- valid while torch has not modified the parameter (version counter, address);
+# invalidate_weight_shadows() after ``.data`` writes.  A stale or absent twin never raises: the caller keeps the b_kn form.
+_SHADOW_T = {}        # id(p) -> [twin view [K, N], version, weakref(p), address, arena offset, the twin arena]
+_SHADOW_T_AT = {}     # the same entries by storage address (_prefetch)
+
+
+def drop_wt_shadow(flat):
+    """forget the twin arena of a model and every table entry that points into it (ArenaState.clear)"""
+    arena = flat.pop("shadow_t", None) if flat is not None else None
+    if arena is None:
+        return
+    for tab in (_SHADOW_T, _SHADOW_T_AT):
+        for k in [k for k, e in tab.items() if e[5] is arena]:
+            del tab[k]
+
+
+def wt_enabled():
+    """UNETR_AMD_WT=0 (A/B hook): no transposed shadow, the data gradients stay on the b_kn form"""
+    return os.environ.get("UNETR_AMD_WT", "1") != "0"
+
+
+def _wt_current(ent, w):
+    return ent is not None and ent[2]() is not None and ent[1] == w._version and ent[3] == w.data_ptr()
+
+
+def _wt_derive(flat, ents):
+    """twins of `ents` from the bf16 shadow arena (which the caller knows to be current for them) in ONE grouped launch"""
+    arr = (_capi.TransposeProblem * len(ents))()
+    for i, ent in enumerate(ents):
+        arr[i].offset, arr[i].K, arr[i].N = ent[4], ent[0].shape[0], ent[0].shape[1]      # (the twin is [K, N]: the weight [N, K])
+    call("unetr_transpose_bf16_grouped", flat["shadow"].data_ptr(), flat["shadow_t"].data_ptr(), arr, len(ents), _stream())
+    for ent in ents:
+        p = ent[2]()
+        ent[1], ent[3] = p._version, p.data_ptr()
+
+
+def _arena_shadow_of(flat, p, off):
+    """the bf16 shadow of `p`, current, when it IS the slice of the shadow arena (the derive launch reads the arena); else None"""
+    sh = weight_bf16(p)
+    return sh if sh.data_ptr() == flat["shadow"].data_ptr() + 2 * off else None
+
+
+def _keeps_twin(st):
+    """this backward pass ends in the epilogue that writes the twins (the fused AdamW form, not the bf16 communication form)"""
+    fz = st.fuse if st is not None else None
+    return fz is not None and fz.get("kind") != "bf16out"
+
+
+def weight_bf16_t(w):
+    """The transposed bf16 twin [in, out] of Linear weight `w` [out, in], or None (the caller then reads weight_bf16(w) as the
+    [K, N] operand).  Never launches under graph capture; creates the arena only for a backward pass whose weight-gradient launch
+    will keep it current (the fused AdamW epilogue), and under capture hands a twin out only to such a pass: the optimizer part of
+    any other captured step would leave it behind from the second replay on."""
+    if not wt_enabled() or w.dim() != 2 or w.shape[0] % 8 or w.shape[1] % 8:
+        return None
+    st = _GRAD_SINK.get(w.data_ptr())
+    flat = getattr(st, "flat", None) if st is not None else None
+    if flat is None or flat.get("shadow") is None:
+        return None
+    capturing = torch.cuda.is_current_stream_capturing()
+    keeps = _keeps_twin(st)
+    if capturing and not keeps:
+        return None        # a replay runs no Python: a graph may read the twin only if the graph itself rewrites it every step
+    if flat.get("shadow_t") is None:
+        if capturing or not keeps:
+            return None
+        flat["shadow_t"] = torch.zeros(flat["total"], dtype=torch.bfloat16, device=w.device)
+    ent = _SHADOW_T.get(id(w))
+    if ent is None or ent[2]() is not w or ent[5] is not flat["shadow_t"]:
+        index = flat.get("_index")
+        if index is None:
+            index = flat["_index"] = {id(p): o for p, o in zip(flat["params"], flat["offsets"])}
+        off = index.get(id(w))
+        if off is None or flat["shadow_t"].device != w.device:
+            return None
+        ent = [flat["shadow_t"][off:off + w.numel()].view(w.shape[1], w.shape[0]), -1, weakref.ref(w), w.data_ptr(), off, flat["shadow_t"]]
+        _SHADOW_T[id(w)] = ent
+        _SHADOW_T_AT[w.data_ptr()] = ent
+    if not _wt_current(ent, w):
+        if capturing:
+            return None
+        # this twin and every other registered one of the arena that is stale (after invalidate_weight_shadows: all of them) in one launch
+        todo = []
+        for e in _SHADOW_T.values():
+            p = e[2]()
+            if e[5] is flat["shadow_t"] and p is not None and (e is ent or not _wt_current(e, p)) and _arena_shadow_of(flat, p, e[4]) is not None:
+                todo.append(e)
+        if not any(e is ent for e in todo):          # (identity: the entries hold tensors)
+            return None
+        _wt_derive(flat, todo)
+    return ent[0]
+
+
+def refresh_wt_shadow(flat, stepped, written=()):
+    """optimizer side (flat arenas): kernels of this package have just updated the parameters `stepped` and their bf16 shadow slices.
+    written: those whose twin the same kernels wrote (the fused weight-gradient epilogue) -- such a twin keeps its stamp: current if it
+    was current before the step, stale if it was stale.  Every other registered twin of a parameter that stepped is re-derived from
+    the bf16 shadow arena, all of them in one grouped launch (a step being captured only marks them stale: weight_bf16_t gave its
+    backward pass no twin, so its graph does not read them, and the next eager or fused pass re-derives them)."""
+    if flat is None or flat.get("shadow_t") is None:
+        return
+    written = {id(p) for p in written}
+    todo = []
+    for p in stepped:
+        ent = _SHADOW_T.get(id(p))
+        if ent is None or ent[5] is not flat["shadow_t"] or ent[2]() is not p or id(p) in written:
+            continue
+        sh = _SHADOW.get(id(p))
+        if (sh is not None and sh[4]() is p and sh[1] == p._version and sh[5] == p.data_ptr()
+                and sh[0].data_ptr() == flat["shadow"].data_ptr() + 2 * ent[4] and not torch.cuda.is_current_stream_capturing()):
+            todo.append(ent)
+        else:
+            ent[1] = -1            # (weight_bf16_t re-derives it when a backward pass asks)
+    if todo:
+        _wt_derive(flat, todo)
 
 
 def register_weight_shadow(w, shadow):
@@ -611,13 +743,23 @@ def shadow_ptr_for_update(w):
 PREFETCH_RIDERS = True
 
 
-def _prefetch(host, *weights):
+def _prefetch(host, *weights, dgrad=0):
     """unetr_prefetch over the bf16 shadows of up to two weights for the launch `host`, or None.  Only a shadow that already
-    exists is named (its buffer lives as long as the parameter and is what the GEMM itself reads): no cast is launched from here."""
+    exists is named (its buffer lives as long as the parameter and is what the GEMM itself reads): no cast is launched from here.
+    dgrad (token rows of the pass, or 0): the GEMM behind the launch is a data gradient -- it reads the transposed twin where
+    _dgrad_operand will hand one out (a current one, M <= WT_MAX_ROWS, and under capture only to a pass that rewrites it)."""
     if not PREFETCH_RIDERS or (PREFETCH_RIDERS is not True and host not in PREFETCH_RIDERS):
         return None
     pf, n = _capi.Prefetch(), 0
     for w in weights:
+        if dgrad and w is not None and wt_enabled() and dgrad <= WT_MAX_ROWS:
+            st = _GRAD_SINK.get(w.data_ptr())
+            tw = _SHADOW_T_AT.get(w.data_ptr())
+            if (tw is not None and _wt_current(tw, w) and tw[0].device == w.device and tw[0].numel() == w.numel()
+                    and (_keeps_twin(st) or not torch.cuda.is_current_stream_capturing())):
+                pf.ptr[n], pf.bytes[n] = tw[0].data_ptr(), tw[0].numel() * 2
+                n += 1
+                continue
         # (by storage address: callers hand detached aliases of the next / lower block's parameters)
         ent = _SHADOW_AT.get(w.data_ptr()) if w is not None else None
         owner = ent[4]() if ent is not None else None
@@ -830,18 +972,19 @@ def _stashed_ln(x, gamma, beta):
     return st[0], st[1], st[2]
 
 
-def gemm_ln_bwd_params(A, Bw, M, N, K, x, w, b, mean, rstd, dres=None, dx_bf16=None, b_words=None, pf=None):
+def gemm_ln_bwd_params(A, Bw, M, N, K, x, w, b, mean, rstd, dres=None, dx_bf16=None, b_words=None, pf=None, b_kn=True):
     """(dx, grad_w, grad_b) of a LayerNorm whose output gradient is dy = A[M,K] @ Bw[K,N] (the data gradient of the Linear
     layer behind it, bf16-stored operands, Bw read as the [K, N] operand): unetr_gemm_bf16_ln_bwd -- when the GEMM is cut into K
-    slabs the LayerNorm kernel sums them itself, so the separate split-K reduce launch disappears (bit-identical)."""
+    slabs the LayerNorm kernel sums them itself, so the separate split-K reduce launch disappears (bit-identical).
+    b_kn=False: Bw is the transposed twin [N, K] of the weight (weight_bf16_t), read in the forward kernel form."""
     x3 = A.dtype == torch.float32              # bf16x3 mode: fp32 operands (Bw optionally as its word shadow b_words)
     assert x3 or (A.dtype == torch.bfloat16 and Bw.dtype == torch.bfloat16)
     d = GemmBf16Desc()
     d.x3 = (2 if b_words is not None else 1) if x3 else 0
     if b_words is not None:
         Bw = b_words
-    d.M, d.N, d.K, d.b_kn = M, N, K, 1
-    d.lda, d.ldb, d.ldc, d.ldcb = K, N, N, N
+    d.M, d.N, d.K, d.b_kn = M, N, K, int(bool(b_kn))
+    d.lda, d.ldb, d.ldc, d.ldcb = K, (N if b_kn else K), N, N
     d.alpha = 1.0
     scratch = torch.empty(M, N, dtype=torch.float32, device=x.device)
     dx = torch.empty_like(x)
@@ -1446,6 +1589,17 @@ def _tblock_forward(x, n1w, n1b, wqkv, wp, bp, n2w, n2b, w1, b1, w2, b2, B, L, h
     return x2, (y1, m1, r1, qkv, att, lse, x1, y2, m2, r2, u, a), twins
 
 
+WT_MAX_ROWS = 512     # the two operand forms are measured, and held bit for bit, at the small-M tile rules only (csrc/gemm_bf16.hip)
+
+
+def _dgrad_operand(w, M):
+    """(B, b_kn) of the data gradient dx[M, in] = dy . w on bf16-stored operands: the transposed twin in the forward kernel form
+    where a current one exists (M <= WT_MAX_ROWS: above, the forms take different tiles and K slabs, and no tile was measured for
+    the forward form), else the bf16 shadow read as the [K, N] operand"""
+    wt = weight_bf16_t(w) if M <= WT_MAX_ROWS else None
+    return (wt, False) if wt is not None else (weight_bf16(w), True)
+
+
 class TransformerBlockFn(torch.autograd.Function):
     """MONAI TransformerBlock: x + attn(norm1(x)); then + mlp(norm2(.)).  ``ckpt`` = activation checkpointing
     (BASELINE.json config[3]): only the block input is kept and backward recomputes the block's forward kernels first."""
@@ -1490,14 +1644,16 @@ class TransformerBlockFn(torch.autograd.Function):
         # MLP
         y1b = attb = y2b = ab = dx2b = dub = None
         if fast:
-            # data gradients dX = dY . W read W [out, in] as the [K_reduce, N_out] operand (b_kn) -- no transposed copy
+            # data gradients dX = dY . W: on the transposed twin of W in the forward kernel form where the fused optimizer epilogue
+            # keeps one current (_dgrad_operand), else W [out, in] read as the [K_reduce, N_out] operand (b_kn); same bits
             if twins is not None:
                 y1b, attb, y2b, ab = twins
             dx2b = _twin(dx2)
             # (du exists as bf16 only: the weight gradient of linear1 is formed from these bf16 values, and so is its bias gradient
             # -- the fp32 copy was 5.3 MB written and read back per block for the column sum alone)
             du, dub = None, torch.empty(M, mlp, dtype=torch.bfloat16, device=x.device)
-            gemm_bf16(dx2b, weight_bf16(w2), M, mlp, hid, b_kn=True, Cb=dub, act=2, aux=u, ldaux=mlp)
+            wo, bkn = _dgrad_operand(w2, M)
+            gemm_bf16(dx2b, wo, M, mlp, hid, b_kn=bkn, Cb=dub, act=2, aux=u, ldaux=mlp)
         else:
             du = linear_dgrad(dx2, w2, prec, aux=u)
         dw2 = wgrad_or_defer(dx2, a, prec, w2, dx2b, ab)
@@ -1506,8 +1662,9 @@ class TransformerBlockFn(torch.autograd.Function):
         db1 = colsum_or_defer(dub if fast else du, M, mlp, mlp, b1)
         if fast:
             dx1b = bf16_like(x)
-            dx1, dn2w, dn2b = gemm_ln_bwd_params(dub, weight_bf16(w1), M, hid, mlp, x1, n2w, n2b, m2, r2, dres=dx2, dx_bf16=dx1b,
-                                                 pf=_prefetch("ln2_bwd", wp))
+            wo, bkn = _dgrad_operand(w1, M)
+            dx1, dn2w, dn2b = gemm_ln_bwd_params(dub, wo, M, hid, mlp, x1, n2w, n2b, m2, r2, dres=dx2, dx_bf16=dx1b,
+                                                 pf=_prefetch("ln2_bwd", wp, dgrad=M), b_kn=bkn)
         else:
             dx1b = None
             if prec == _capi.PREC_BF16X3 and ln_ride_enabled() and x3_ride_ok(M, hid, mlp):
@@ -1520,25 +1677,28 @@ class TransformerBlockFn(torch.autograd.Function):
         b16att = fast and qkv.dtype == torch.bfloat16
         if b16att:
             dattb = bf16_like(x)
-            gemm_bf16(dx1b, weight_bf16(wp), M, hid, hid, b_kn=True, Cb=dattb)
+            wo, bkn = _dgrad_operand(wp, M)
+            gemm_bf16(dx1b, wo, M, hid, hid, b_kn=bkn, Cb=dattb)
         elif fast:
             datt = torch.empty(M, hid, **f32)
-            gemm_bf16(dx1b, weight_bf16(wp), M, hid, hid, b_kn=True, C=datt)
+            wo, bkn = _dgrad_operand(wp, M)
+            gemm_bf16(dx1b, wo, M, hid, hid, b_kn=bkn, C=datt)
         else:
             datt = linear_dgrad(dx1, wp, prec)
         dwp = wgrad_or_defer(dx1, att, prec, wp, dx1b, attb)
         dbp = colsum_or_defer(dx1, M, hid, hid, bp)
         if b16att:
             dqkv = None
-            dqkvb = attention_bf16_bwd(qkv, attb, dattb, lse, B, L, heads, dh, pf=_prefetch("attn_bwd", wqkv))
+            dqkvb = attention_bf16_bwd(qkv, attb, dattb, lse, B, L, heads, dh, pf=_prefetch("attn_bwd", wqkv, dgrad=M))
         else:
             dqkvb = torch.empty(M, 3 * hid, dtype=torch.bfloat16, device=x.device) if fast else None
             dqkv = attention_bwd(qkv, att, datt, lse, B, L, heads, dh, prec, dqkv_bf16=dqkvb)
         dwqkv = wgrad_or_defer(dqkv, y1, prec, wqkv, dqkvb, y1b)
         if fast:
             dxb = bf16_like(x)
-            dx, dn1w, dn1b = gemm_ln_bwd_params(dqkvb, weight_bf16(wqkv), M, hid, 3 * hid, x, n1w, n1b, m1, r1, dres=dx1, dx_bf16=dxb,
-                                                pf=_prefetch("ln1_bwd", *ctx.below))
+            wo, bkn = _dgrad_operand(wqkv, M)
+            dx, dn1w, dn1b = gemm_ln_bwd_params(dqkvb, wo, M, hid, 3 * hid, x, n1w, n1b, m1, r1, dres=dx1, dx_bf16=dxb,
+                                                pf=_prefetch("ln1_bwd", *ctx.below, dgrad=M), b_kn=bkn)
         else:
             dxb = None
             if prec == _capi.PREC_BF16X3 and ln_ride_enabled() and x3_ride_ok(M, hid, 3 * hid):
@@ -1571,7 +1731,7 @@ class LayerNormFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, w, mean, rstd, b = ctx.saved_tensors
         dxb = bf16_like(x) if ctx.twin else None    # bf16 operand for the last transformer block's backward GEMMs
-        dx, dw, db = layernorm_bwd_params(dy.contiguous(), x, w, b, mean, rstd, dx_bf16=dxb, pf=_prefetch("ln1_bwd", *ctx.below))
+        dx, dw, db = layernorm_bwd_params(dy.contiguous(), x, w, b, mean, rstd, dx_bf16=dxb, pf=_prefetch("ln1_bwd", *ctx.below, dgrad=x.numel() // x.shape[-1]))
         if dxb is not None:
             _attach_twin(dx, dxb)
         return dx, dw, db, None, None, None

@@ -78,6 +78,7 @@ class AdamW(torch.optim.Optimizer):
                      Fn.shadow_ptr_for_update(p), stream)
         if self._flat is not None and per_tensor:
             Fn.refresh_x3_shadow(self._flat)      # (per-tensor launches do not write the bf16x3 word shadow: one derive launch)
+            Fn.refresh_wt_shadow(self._flat, [p for g in self.param_groups for p in g["params"] if p.grad is not None])
         Fn.refresh_conv_packs()          # one grouped launch: packed conv weights follow the update
         return loss
 
@@ -130,6 +131,7 @@ class AdamW(torch.optim.Optimizer):
         if flat.get("shadow") is not None:           # the kernel rewrote the bf16 shadow slices of every parameter that stepped
             Fn.mark_flat_maintained([p for p, has in zip(params, pattern) if has], flat.get("state"))
         Fn.refresh_x3_shadow(flat, written=True)     # (bf16x3 mode: the optimizer kernels wrote the word shadow)
+        Fn.refresh_wt_shadow(flat, [p for p, has in zip(params, pattern) if has])      # (bf16 mode: they did not write the transposed twins)
         return True
 
     # ---- single-GPU fused step: AdamW of the ViT Linear weights rides on the grouped weight-gradient launch ----------------
@@ -167,7 +169,7 @@ class AdamW(torch.optim.Optimizer):
                                  group["lr"], b1, b2, group["eps"], group["weight_decay"], words.data_ptr() if words is not None else None)
         gbase = flat["grad"].data_ptr()
         index = {gbase + o * 4: i for i, (o, has) in enumerate(zip(flat["offsets"], pattern)) if has}
-        self._fused = dict(pattern=pattern, arena=arena, index=index, done=[], keep=(m, v, steps))
+        self._fused = dict(pattern=pattern, arena=arena, index=index, done=[], keep=(m, v, steps), flat=flat, wt_done=[])
         flat["state"].fuse = self._fused
 
     @torch.no_grad()
@@ -215,6 +217,7 @@ class AdamW(torch.optim.Optimizer):
         Fn.refresh_x3_shadow(flat, written=True)
         if flat.get("shadow") is not None:
             Fn.mark_flat_maintained([p for p, has in zip(params, pattern) if has], flat.get("state"))
+        Fn.refresh_wt_shadow(flat, [p for p, has in zip(params, pattern) if has], written=[params[i] for i in fz["wt_done"]])
         Fn.refresh_conv_packs()
 
     # ---- data-parallel arena update: all-reduce pieces overlap the optimizer kernels of the pieces before them ----
@@ -250,6 +253,7 @@ class AdamW(torch.optim.Optimizer):
         Fn.refresh_x3_shadow(self._flat, written=True)
         if self._flat.get("shadow") is not None:
             Fn.mark_flat_maintained([p for p, has in zip(self.param_groups[0]["params"], plan["pattern"]) if has], self._flat.get("state"))
+        Fn.refresh_wt_shadow(self._flat, [p for p, has in zip(self.param_groups[0]["params"], plan["pattern"]) if has])
         Fn.refresh_conv_packs()
 
     @torch.no_grad()
@@ -276,4 +280,5 @@ class AdamW(torch.optim.Optimizer):
         Fn.refresh_x3_shadow(self._flat, written=True)
         if self._flat.get("shadow") is not None:
             Fn.mark_flat_maintained([p for p, has in zip(params, plan["pattern"]) if has], self._flat.get("state"))
+        Fn.refresh_wt_shadow(self._flat, [p for p, has in zip(params, plan["pattern"]) if has])
         Fn.refresh_conv_packs()

@@ -588,6 +588,24 @@ int unetr_cast_bf16_ranges(const float* src_arena, void* dst_arena, const long* 
  * arena packs them), index into a->steps, first block of the range (blocks of 4096 elements, running sum); n_blocks = total. */
 int unetr_adamw_ranges(const unetr_adamw_arena* a, const long* table_dev, int n_ranges, long n_blocks, void* stream);
 
+/* ---- transposed bf16 weight shadow (bf16 mode, flat arenas): the ViT data gradients dx = dy W on the forward (b_kn = 0) kernel form ----
+ * shadow_t is a second bf16 arena addressed with the element offsets of the parameter arena: a weight [N, K] at offset o has its
+ * transposed twin, [K, N] row-major, at shadow_t + o.  dx[M, K] = dy[M, N] . W is then unetr_gemm_bf16 with b_kn = 0, B = shadow_t + o,
+ * ldb = N (the reduction length).
+ * unetr_gemm_bf16_grouped_wgrad_adamw_t: unetr_gemm_bf16_grouped_wgrad_adamw whose epilogue also writes the twin of every weight it
+ * updates (whole 128-byte lines of its rows, 2 bytes per weight more than the plain form; needs a->shadow_bf16, shadow_t 16-byte
+ * aligned and every probs[i].dw at an arena offset that is a multiple of 8 elements, else UNETR_ERR_UNSUPPORTED).  shadow_t == NULL runs the
+ * kernel of the plain entry point; the other outputs are bit-identical either way.  Bytes of shadow_t outside the updated slices are
+ * not touched.
+ * unetr_transpose_bf16_grouped: the derive launch -- dst_arena + offset as [K, N] = transpose of src_arena + offset as [N, K] for every
+ * table entry, in one launch (offset, N, K multiples of 8).  Used when a twin is missing or stale (first use, invalidation, optimizer
+ * steps that did not go through the entry point above).
+ * (Additions: no existing signature or struct moved, UNETR_ABI_VERSION stays.) */
+typedef struct { long offset; int N, K; } unetr_transpose_problem;
+int unetr_gemm_bf16_grouped_wgrad_adamw_t(const unetr_grouped_problem* probs, int n, const unetr_adamw_arena* a,
+                                          const int* step_index, void* shadow_t, void* stream);
+int unetr_transpose_bf16_grouped(const void* src_arena, void* dst_arena, const unetr_transpose_problem* probs, int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

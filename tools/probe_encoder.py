@@ -56,7 +56,7 @@ res = {}
 
 env()
 res["layernorm_fwd (bf16 out)"] = timeit(lambda: Fn.layernorm_fwd(x, gam, bet, bf16_out=y1b, want_fp32=False))
-for cfg in ("6464", "64128", "6496"):
+for cfg in ("6464", "64128", "6496", "6432", "3264"):
     env(UNETR_GEMM_CFG=cfg)
     res[f"gemm_bf16 qkv   N=2304 K=768  cfg {cfg}"] = timeit(lambda: Fn.gemm_bf16(xb, w["qkv"], M, 3 * H, H, C=qkv))
     res[f"gemm_bf16 mlp1  N=3072 K=768  cfg {cfg} (+gelu, bf16 out, pre)"] = timeit(
@@ -85,6 +85,21 @@ for cfg in ("6464", "3264", "64128"):
             lambda: Fn.gemm_bf16(dyb, w["w2"], M, MLP, H, b_kn=True, C=du, Cb=dub2, act=2, aux=u, ldaux=MLP))
         res[f"dgrad dy2  N=768  K=3072 cfg {cfg} {tag}"] = timeit(lambda: Fn.gemm_bf16(dub, w["w1"], M, H, MLP, b_kn=True, C=dx))
         res[f"dgrad datt N=768  K=768  cfg {cfg} {tag}"] = timeit(lambda: Fn.gemm_bf16(dyb, w["p"], M, H, H, b_kn=True, C=dx))
+# the same data gradients in the forward (b_kn = 0) form on the transposed weight twin [in, out] (functional.weight_bf16_t), and
+# dx of the qkv weight ([M x 768], K = 2304: a shape the forward form does not meet in the forward pass)
+wt = {n: t.t().contiguous() for n, t in w.items()}
+dqb_ = torch.randn(M, 3 * H, device=dev).bfloat16()
+for cfg in ("6464", "6432", "3264", "64128", "6496"):
+    for sp in (0, 1):
+        env(UNETR_GEMM_CFG=cfg, **({"UNETR_GEMM_SPLITS": 1} if sp else {}))
+        tag = "no split" if sp else "auto split"
+        res[f"dgrad-NT du   N=3072 K=768  cfg {cfg} {tag} (gelu', fp32+bf16 out)"] = timeit(
+            lambda: Fn.gemm_bf16(dyb, wt["w2"], M, MLP, H, C=du, Cb=dub2, act=2, aux=u, ldaux=MLP))
+        res[f"dgrad-NT dy2  N=768  K=3072 cfg {cfg} {tag}"] = timeit(lambda: Fn.gemm_bf16(dub, wt["w1"], M, H, MLP, C=dx))
+        res[f"dgrad-NT datt N=768  K=768  cfg {cfg} {tag}"] = timeit(lambda: Fn.gemm_bf16(dyb, wt["p"], M, H, H, C=dx))
+        res[f"dgrad-NT dx   N=768  K=2304 cfg {cfg} {tag}"] = timeit(lambda: Fn.gemm_bf16(dqb_, wt["qkv"], M, H, 3 * H, C=dx))
+        if cfg in ("6464", "3264", "64128"):
+            res[f"dgrad dx   N=768  K=2304 cfg {cfg} {tag}"] = timeit(lambda: Fn.gemm_bf16(dqb_, w["qkv"], M, H, 3 * H, b_kn=True, C=dx))
 env()
 B, L, heads = M // 216 if M % 216 == 0 else 1, 216 if M % 216 == 0 else M, 12
 att = None
