@@ -51,7 +51,11 @@ class GroupedProblem(ctypes.Structure):
 class AdamWArena(ctypes.Structure):
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("m", c_void_p), ("v", c_void_p), ("shadow_bf16", c_void_p), ("steps", c_void_p),
                 ("total", c_long), ("lr", c_float), ("beta1", c_float), ("beta2", c_float), ("eps", c_float), ("weight_decay", c_float),
-                ("shadow_x3", c_void_p)]
+                ("shadow_x3", c_void_p), ("hyper", c_void_p)]
+
+
+class LrSchedule(ctypes.Structure):
+    _fields_ = [("kind", c_int), ("base_lr", c_float), ("min_lr", c_float), ("warmup", c_float), ("total", c_float), ("power", c_float)]
 
 
 class TransposeProblem(ctypes.Structure):
@@ -166,6 +170,8 @@ _SIGNATURES = {
     "unetr_nhwc_to_nchw": [P, c_long, P, c_int, c_int, c_long, c_int, c_int, P],
     "unetr_patch_gather": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P],
     "unetr_counter_add": [P, P, c_int, P],
+    "unetr_counter_add_lr": [P, P, c_int, P, ctypes.POINTER(LrSchedule), P],
+    "unetr_adamw_hyper_set": [P, c_int, c_float, c_float, c_float, P],
     "unetr_add_cast_bf16": [P, P, P, P, c_long, P],
     "unetr_copy_rows": [P, c_long, P, c_long, c_long, c_int, c_int, c_int, P],
     "unetr_outconv_fwd": [P, c_long, P, P, P, c_int, c_long, c_int, c_int, c_int, P],
@@ -194,6 +200,7 @@ _SIGNATURES = {
     "unetr_ranking_loss_bwd": [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P],
     "unetr_adamw": [P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_float, P, P, P],
     "unetr_adamw_reduced": [P, P, c_int, c_float, P, P, c_long, c_float, c_float, c_float, c_float, c_float, P, P, P, P],
+    "unetr_adamw_hyper": [P, P, c_int, c_float, P, P, c_long, P, c_float, c_float, c_float, P, P, P, P],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + ("unetr_conv3_packed_bytes", "unetr_conv3_packed_1x1_bytes", "unetr_ranking_workspace_floats",

@@ -183,6 +183,25 @@ __device__ __forceinline__ AdamWCoef adamw_coef(float lr, float b1, float b2, fl
     const float bc1 = 1.f - powf(b1, step), bc2 = 1.f - powf(b2, step);
     return AdamWCoef{1.f - lr * wd, b1, b2, eps, lr / bc1, rsqrtf(bc2)};
 }
+// lr / weight decay of a launch: the hyper row {lr, weight_decay, t, reserved} in device memory when the launch was given one (read
+// when the kernel runs: a captured step follows the host's or the in-graph schedule's learning rate), else the by-value arguments.
+// A wave-uniform load; the same float lr gives the same coefficients either way.
+__device__ __forceinline__ AdamWCoef adamw_coef_at(const float* __restrict__ hyper, float lr, float b1, float b2, float eps, float wd, float step) {
+    if (hyper) { lr = hyper[0]; wd = hyper[1]; }
+    return adamw_coef(lr, b1, b2, eps, wd, step);
+}
+// the learning rate of optimizer step s (0-based) under a schedule (include/unetr_hip.h: unetr_lr_schedule): f in double, one rounding
+__device__ __forceinline__ float lr_schedule_at(const unetr_lr_schedule& sc, float t) {
+    const double s = (double)t, warm = (double)sc.warmup, total = (double)sc.total;
+    double f = 1.0;
+    if (sc.kind == 1) {
+        if (s < warm) f = s / fmax(1.0, warm);
+        else f = 0.5 * (1.0 + cospi(fmin(1.0, (s - warm) / fmax(1.0, total - warm))));      // cospi: exact at 1/2 and 1
+    } else if (sc.kind == 2) {
+        f = pow(1.0 - fmin(s, total) / total, (double)sc.power);
+    }
+    return fmaxf(sc.min_lr, (float)((double)sc.base_lr * f));
+}
 __device__ __forceinline__ void adamw_elem(float& p, float& m, float& v, float g, const AdamWCoef& c) {
     // every multiply-add is spelled out (contraction off, explicit fmaf): left to the compiler, the same expression was fused
     // differently in the streaming kernel and in the GEMM epilogue and ~0.6 % of the elements differed in the last bit

@@ -665,7 +665,7 @@ constexpr int GW_MAX = 64;     // 12 blocks x 4 Linear layers + patch embedding 
 struct GwProblem { const uint16_t* dy; const uint16_t* x; float* dw; int M, N, K, tile0, ntn, step_idx; };
 // FUSE: the arenas of the fused optimizer epilogue (dw then only NAMES the arena slice: element offset = dw - gb)
 // st: the transposed bf16 shadow arena (WT kernels only): weight [N, K] at offset o has its [K, N] twin at st + o
-struct GwFuse { float* pb; const float* gb; float* mb; float* vb; uint16_t* sb; const float* steps; float lr, b1, b2, eps, wd; uint32_t* sw; uint16_t* st; };
+struct GwFuse { float* pb; const float* gb; float* mb; float* vb; uint16_t* sb; const float* steps; float lr, b1, b2, eps, wd; uint32_t* sw; uint16_t* st; const float* hyper; };
 struct GwArgs { int n; GwFuse f; GwProblem p[GW_MAX]; };
 
 // WT (FUSE 1 only): the epilogue also writes the updated weights, transposed, into the second bf16 shadow f.st
@@ -770,7 +770,7 @@ gemm_bf16_grouped_wgrad_kernel(GwArgs ga) {
     [[maybe_unused]] long off0 = 0;
     [[maybe_unused]] u32x4 keep[4];
     if constexpr (FUSE == 1) {
-        c = adamw_coef(ga.f.lr, ga.f.b1, ga.f.b2, ga.f.eps, ga.f.wd, ga.f.steps[pr.step_idx]);
+        c = adamw_coef_at(ga.f.hyper, ga.f.lr, ga.f.b1, ga.f.b2, ga.f.eps, ga.f.wd, ga.f.steps[pr.step_idx]);
         off0 = pr.dw - ga.f.gb;
     }
 #pragma unroll
@@ -1233,13 +1233,14 @@ static int grouped_wgrad_bf16(const unetr_grouped_problem* probs, int n, const u
     if (b16 && (!a || !a->grad || !a->shadow_bf16 || a->total <= 0 || ((uintptr_t)a->grad & 15) || ((uintptr_t)a->shadow_bf16 & 7))) return UNETR_ERR_ARG;
     if (a && !b16 && (!a->param || !a->grad || !a->m || !a->v || !a->steps || !step_index || a->total <= 0)) return UNETR_ERR_ARG;
     if (a && !b16 && ((((uintptr_t)a->param | (uintptr_t)a->grad | (uintptr_t)a->m | (uintptr_t)a->v) & 15) || ((uintptr_t)a->shadow_bf16 & 7))) return UNETR_ERR_UNSUPPORTED;
+    if (a && !b16 && ((uintptr_t)a->hyper & 3)) return UNETR_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     for (int base = 0; base < n; base += GW_MAX) {
         GwArgs ga;
         ga.n = std::min(GW_MAX, n - base);
         ga.f = GwFuse{};
         if (a) ga.f = GwFuse{a->param, a->grad, a->m, a->v, (uint16_t*)a->shadow_bf16, a->steps, a->lr, a->beta1, a->beta2, a->eps, a->weight_decay,
-                             b16 ? nullptr : (uint32_t*)a->shadow_x3, (uint16_t*)shadow_t};
+                             b16 ? nullptr : (uint32_t*)a->shadow_x3, (uint16_t*)shadow_t, b16 ? nullptr : a->hyper};
         int tiles = 0;
         for (int i = 0; i < ga.n; ++i) {
             const unetr_grouped_problem& q = probs[base + i];

@@ -1247,6 +1247,24 @@ __global__ void counter_add_kernel(float* __restrict__ y, const float* __restric
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) y[i] += inc[i];
 }
+// the same launch also keeps the optimizer's hyper row {lr, weight_decay, t, reserved}: thread 0 sets lr for THIS step from the schedule
+// at t (kind < 0: no schedule, lr stays what the host wrote) and counts the step.  The AdamW kernels behind it in the stream read the row.
+__global__ void counter_add_lr_kernel(float* __restrict__ y, const float* __restrict__ inc, int n, float* __restrict__ row, unetr_lr_schedule sc) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) y[i] += inc[i];
+    if (i == 0) {
+        const float t = row[2];
+        if (sc.kind >= 0) row[0] = lr_schedule_at(sc, t);
+        row[2] = t + 1.f;
+    }
+}
+__global__ void adamw_hyper_set_kernel(float* __restrict__ row, int fields, float lr, float wd, float t) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (fields & 1) row[0] = lr;
+        if (fields & 2) row[1] = wd;
+        if (fields & 4) row[2] = t;
+    }
+}
 
 template <class T>
 __global__ void add_rows_kernel(T* __restrict__ y, long ldy, const T* __restrict__ a, long lda, long rows, int cols, int accumulate) {
@@ -1641,8 +1659,8 @@ template <bool GB16>
 __global__ void __launch_bounds__(256)
 adamw_kernel(float* __restrict__ p, const void* __restrict__ gsrc, float gscale, float* __restrict__ m, float* __restrict__ v,
              long n4, long n, float lr, float b1, float b2, float eps, float wd, const float* __restrict__ step_dev,
-             uint16_t* __restrict__ shadow, uint32_t* __restrict__ words) {
-    const AdamWCoef c = adamw_coef(lr, b1, b2, eps, wd, *step_dev);
+             uint16_t* __restrict__ shadow, uint32_t* __restrict__ words, const float* __restrict__ hyper) {
+    const AdamWCoef c = adamw_coef_at(hyper, lr, b1, b2, eps, wd, *step_dev);
     auto grad1 = [&](long i) -> float {
         if (GB16) { uint32_t u = (uint32_t)((const uint16_t*)gsrc)[i] << 16; return __builtin_bit_cast(float, u) * gscale; }
         return ((const float*)gsrc)[i] * gscale;
@@ -1678,7 +1696,7 @@ constexpr int AR_BLOCK = 4096;
 __global__ void __launch_bounds__(256)
 adamw_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                     uint16_t* __restrict__ shadow, const float* __restrict__ steps, const long* __restrict__ table, int nr,
-                    float lr, float b1, float b2, float eps, float wd, uint32_t* __restrict__ words) {
+                    float lr, float b1, float b2, float eps, float wd, uint32_t* __restrict__ words, const float* __restrict__ hyper) {
     int lo_r = 0, hi_r = nr - 1;
     const long blk = blockIdx.x;
     while (lo_r < hi_r) {                                  // last range whose first block <= blk (uniform: scalar loads)
@@ -1686,7 +1704,7 @@ adamw_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* _
         if (table[4 * mid + 3] <= blk) lo_r = mid; else hi_r = mid - 1;
     }
     const long lo = table[4 * lo_r], hi = table[4 * lo_r + 1];
-    const AdamWCoef c = adamw_coef(lr, b1, b2, eps, wd, steps[table[4 * lo_r + 2]]);
+    const AdamWCoef c = adamw_coef_at(hyper, lr, b1, b2, eps, wd, steps[table[4 * lo_r + 2]]);
     const long beg = lo + (blk - table[4 * lo_r + 3]) * AR_BLOCK, end = min(hi, beg + AR_BLOCK);
     for (long i = beg / 4 + threadIdx.x; i < end / 4; i += 256) {
         f32x4 pv = __builtin_nontemporal_load((f32x4*)p + i), mv = __builtin_nontemporal_load((f32x4*)m + i), vv = __builtin_nontemporal_load((f32x4*)v + i);
@@ -2111,6 +2129,25 @@ extern "C" int unetr_counter_add(float* y, const float* inc, int n, void* stream
     return unetr_check_launch();
 }
 
+extern "C" int unetr_counter_add_lr(float* y, const float* inc, int n, float* hyper_row, const unetr_lr_schedule* s, void* stream) {
+    if (!y || !inc || n <= 0 || !hyper_row || ((uintptr_t)hyper_row & 15)) return UNETR_ERR_ARG;
+    unetr_lr_schedule sc{};
+    sc.kind = -1;
+    if (s) {
+        sc = *s;
+        if (sc.kind < 0 || sc.kind > 2 || !(sc.base_lr >= 0.f) || !(sc.min_lr >= 0.f) || !(sc.warmup >= 0.f)) return UNETR_ERR_ARG;
+        if (sc.kind == 2 && !(sc.total > 0.f)) return UNETR_ERR_ARG;
+    }
+    hipLaunchKernelGGL(counter_add_lr_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, y, inc, n, hyper_row, sc);
+    return unetr_check_launch();
+}
+
+extern "C" int unetr_adamw_hyper_set(float* hyper_row, int fields, float lr, float weight_decay, float t, void* stream) {
+    if (!hyper_row || ((uintptr_t)hyper_row & 15) || fields <= 0 || fields > 7) return UNETR_ERR_ARG;
+    hipLaunchKernelGGL(adamw_hyper_set_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, hyper_row, fields, lr, weight_decay, t);
+    return unetr_check_launch();
+}
+
 extern "C" int unetr_copy_rows(void* y, long ldy, const void* a, long lda, long rows, int cols, int accumulate, int act16, void* stream) {
     const int W = act16 ? 8 : 4;
     if (!y || !a || (cols % W) || (ldy % W) || (lda % W)) return UNETR_ERR_ARG;
@@ -2229,7 +2266,8 @@ extern "C" int unetr_outconv_in_bwd(const float* dlogits, const void* c2, long l
 }
 
 static int adamw_launch(float* p, const void* g, int g_bf16, float gscale, float* m, float* v, long n, float lr, float beta1,
-                        float beta2, float eps, float weight_decay, const float* step_dev, void* shadow_bf16, void* shadow_x3, void* stream) {
+                        float beta2, float eps, float weight_decay, const float* step_dev, void* shadow_bf16, void* shadow_x3, void* stream,
+                        const float* hyper = nullptr) {
     if (!p || !g || !m || !v || !step_dev || n <= 0 || (reinterpret_cast<uintptr_t>(shadow_bf16) & 7) || (reinterpret_cast<uintptr_t>(shadow_x3) & 15)) return UNETR_ERR_ARG;
     if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) return UNETR_ERR_ARG;
     if (reinterpret_cast<uintptr_t>(g) & (g_bf16 ? 7 : 15)) return UNETR_ERR_ARG;
@@ -2242,10 +2280,10 @@ static int adamw_launch(float* p, const void* g, int g_bf16, float gscale, float
     dim3 grid(grid_for(std::max<long>(n4, 1), 256, cap));
     if (g_bf16)
         hipLaunchKernelGGL(adamw_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p, g, gscale, m, v, n4, n, lr, beta1, beta2, eps,
-                           weight_decay, step_dev, (uint16_t*)shadow_bf16, (uint32_t*)shadow_x3);
+                           weight_decay, step_dev, (uint16_t*)shadow_bf16, (uint32_t*)shadow_x3, hyper);
     else
         hipLaunchKernelGGL(adamw_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p, g, gscale, m, v, n4, n, lr, beta1, beta2, eps,
-                           weight_decay, step_dev, (uint16_t*)shadow_bf16, (uint32_t*)shadow_x3);
+                           weight_decay, step_dev, (uint16_t*)shadow_bf16, (uint32_t*)shadow_x3, hyper);
     return unetr_check_launch();
 }
 
@@ -2260,7 +2298,7 @@ extern "C" int unetr_adamw_ranges(const unetr_adamw_arena* a, const long* table_
     if (n_blocks > 0x7fffffffL) return UNETR_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(adamw_ranges_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, a->param, a->grad, a->m, a->v,
                        (uint16_t*)a->shadow_bf16, a->steps, table_dev, n_ranges, a->lr, a->beta1, a->beta2, a->eps, a->weight_decay,
-                       (uint32_t*)a->shadow_x3);
+                       (uint32_t*)a->shadow_x3, a->hyper);
     return unetr_check_launch();
 }
 
@@ -2270,4 +2308,11 @@ extern "C" int unetr_adamw_reduced(float* p, const void* g, int g_is_bf16, float
                                    float beta1, float beta2, float eps, float weight_decay, const float* step_dev,
                                    void* shadow_bf16, void* shadow_x3, void* stream) {
     return adamw_launch(p, g, g_is_bf16, gscale, m, v, n, lr, beta1, beta2, eps, weight_decay, step_dev, shadow_bf16, shadow_x3, stream);
+}
+
+// the same launch with lr / weight decay read from the hyper row in device memory when the kernel runs
+extern "C" int unetr_adamw_hyper(float* p, const void* g, int g_is_bf16, float gscale, float* m, float* v, long n, const float* hyper_dev,
+                                 float beta1, float beta2, float eps, const float* step_dev, void* shadow_bf16, void* shadow_x3, void* stream) {
+    if (!hyper_dev || ((uintptr_t)hyper_dev & 3)) return UNETR_ERR_ARG;
+    return adamw_launch(p, g, g_is_bf16, gscale, m, v, n, 0.f, beta1, beta2, eps, 0.f, step_dev, shadow_bf16, shadow_x3, stream, hyper_dev);
 }

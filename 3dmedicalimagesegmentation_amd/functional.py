@@ -451,6 +451,38 @@ def invalidate_weight_shadows():
         ent[1] = -1
 
 
+def refresh_derived_weights(model):
+    """Re-derive, eagerly and into the SAME buffers, every derived weight copy of ``model`` (bf16 shadows, bf16x3 words, transposed
+    twins, packed conv weights) that is out of step with its parameter.  A captured TrainStep reads the copies its optimizer kernels
+    maintain as they are -- a replay runs no Python that could notice a change -- so this is the call to make after
+    ``model.load_state_dict()`` (or any other write torch can see) on a model whose training step is ALREADY captured: resuming
+    from a checkpoint after capture.  Copies that are current are left alone; before capture nothing is needed (the first forward
+    re-derives on demand).  ``.data`` writes behind the version counter still need invalidate_weight_shadows() first."""
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("refresh_derived_weights launches derive kernels: not while a hipGraph is being captured")
+    params = {id(p): p for p in model.parameters()}
+    for p in params.values():
+        ent = _SHADOW.get(id(p))
+        if ent is not None and ent[4]() is p:
+            weight_bf16(p)
+        ent = _SHADOW_X3.get(id(p))
+        if ent is not None and ent[2]() is p:
+            weight_x3(p)
+    for key, ent in list(_PACKS.items()):
+        p = params.get(key[0])
+        if p is not None and ent[4]() is p:
+            conv_pack_get(p, key[1], key[2])
+    flat = getattr(model, "_flat", None)
+    if flat is not None and flat.get("shadow_t") is not None:       # the twins, from the bf16 shadow arena made current above
+        todo = []
+        for e in _SHADOW_T.values():
+            p = e[2]()
+            if e[5] is flat["shadow_t"] and p is not None and not _wt_current(e, p) and _arena_shadow_of(flat, p, e[4]) is not None:
+                todo.append(e)
+        if todo:
+            _wt_derive(flat, todo)
+
+
 def begin_forward(state=None):
     """Called by UNETR.forward.  (1) A derived weight copy that no optimizer of this package keeps in step is trusted for
     ONE forward/backward pass only: a new pass starts a new weight epoch, so the first use re-derives it (a ``.data``

@@ -7,11 +7,47 @@ captured in a hipGraph together with forward and backward.
 
 ``flat=model.use_flat_buffers()``: parameters, gradients and both moments live in flat arenas, and one kernel
 launch covers every contiguous run of parameters that received a gradient (2 launches for the full model:
-MONAI's unused ``cls_token`` splits the arena), instead of one launch per tensor."""
+MONAI's unused ``cls_token`` splits the arena), instead of one launch per tensor.
+
+The scalars that change during a run live on the device too: one ``hyper`` row ``{lr, weight_decay, t, reserved}`` per param group,
+read by every AdamW kernel when it RUNS.  ``sync_hyper()`` uploads ``group["lr"]`` / ``group["weight_decay"]`` when they changed (a
+``torch.optim.lr_scheduler`` keeps working under hipGraph replay), ``set_schedule()`` moves the schedule itself into the captured
+step (it rides on the step-counter launch), and ``state_dict()`` / ``load_state_dict()`` speak torch.optim.AdamW's schema in both
+modes, loading in place so that captured graphs stay valid."""
+import ctypes
+import math
+import struct
+
 import torch
 
 from . import functional as Fn
-from ._capi import call
+from ._capi import LrSchedule, call
+
+SCHEDULES = {"constant": 0, "warmup_cosine": 1, "poly": 2}
+# what torch.optim.AdamW expects to find in a param group it loads (its __setstate__ would otherwise default to the coupled L2 form)
+_TORCH_GROUP_KEYS = dict(amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
+                         decoupled_weight_decay=True)
+
+
+def _f32(x):
+    """x rounded to float32 (what a by-value float kernel argument or a device scalar holds), as a Python float"""
+    return struct.unpack("f", struct.pack("f", float(x)))[0]
+
+
+def schedule_lr(sched, s):
+    """The learning rate of optimizer step ``s`` (0-based) under the schedule description ``sched`` (AdamW.set_schedule): the formula
+    of the in-graph schedule (include/unetr_hip.h: unetr_lr_schedule) in Python floats, rounded once to float32."""
+    kind, warm, total = SCHEDULES[sched["kind"]], float(sched["warmup"]), float(sched["total"])
+    s = float(s)
+    f = 1.0
+    if kind == 1:
+        if s < warm:
+            f = s / max(1.0, warm)
+        else:
+            f = 0.5 * (1.0 + math.cos(math.pi * min(1.0, (s - warm) / max(1.0, total - warm))))
+    elif kind == 2:
+        f = (1.0 - min(s, total) / total) ** float(sched["power"])
+    return max(_f32(sched["min_lr"]), _f32(_f32(sched["base_lr"]) * f))
 
 
 class AdamW(torch.optim.Optimizer):
@@ -21,6 +57,11 @@ class AdamW(torch.optim.Optimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._steps = {}   # group index -> flat device tensor of per-parameter step counts
         self._masks = {}   # (group index, pattern) -> 0/1 increment tensor
+        self._hyper = None       # device tensor [groups, 4]: {lr, weight_decay, t, reserved} per group, read by the kernels
+        self._uploaded = [[None, None] for _ in self.param_groups]      # (lr, weight_decay) as float32, last written to the row by the host
+        self._schedule = [None] * len(self.param_groups)               # per group: (description dict, LrSchedule) once set_schedule ran
+        self._captured = False   # a hipGraph capture has recorded launches of this optimizer (their by-value arguments are frozen)
+        self._runs_captured = set()  # flat mode: (first, last) parameter index of every run a captured launch steps with ONE shared counter
         self._flat = flat
         self._flat_state = None
         if flat is not None:
@@ -28,16 +69,227 @@ class AdamW(torch.optim.Optimizer):
                 raise ValueError("flat= needs a single param group holding model.parameters() in order")
             self._host_steps = [0] * len(flat["params"])
 
-    def _advance_steps(self, gi, params, pattern, dev):
+    # ---- device-resident hyper-parameters --------------------------------------------------------------------------------
+    def _device(self):
+        return self._flat["param"].device if self._flat is not None else self.param_groups[0]["params"][0].device
+
+    def _hyper_ptr(self, gi):
+        return self._hyper.data_ptr() + 16 * gi
+
+    def _step_tensor(self, gi, dev):
         steps = self._steps.get(gi)
         if steps is None:
-            steps = torch.zeros(len(params), dtype=torch.float32, device=dev)
-            self._steps[gi] = steps
+            steps = self._steps[gi] = torch.zeros(len(self.param_groups[gi]["params"]), dtype=torch.float32, device=dev)
+        return steps
+
+    def sync_hyper(self):
+        """Write ``group["lr"]`` / ``group["weight_decay"]`` of every group to its device row if they differ from what was last
+        uploaded: a stream-ordered single-thread launch with the values as arguments, no host synchronisation.  Called by every
+        stepping entry point and by ``TrainStep.run()`` before a replay.  While the current stream is capturing nothing may be
+        uploaded -- the write would become part of the graph and reset the rate on every replay -- so a pending change raises
+        there.  With an in-graph schedule attached (``set_schedule``) ``group["lr"]`` is not read."""
+        capturing = torch.cuda.is_current_stream_capturing()
+        if len(self._uploaded) != len(self.param_groups):
+            if self._hyper is not None:
+                raise RuntimeError("AdamW: param groups cannot be added after the first step (one device row per group exists)")
+            self._uploaded = [[None, None] for _ in self.param_groups]
+            self._schedule = [None] * len(self.param_groups)
+        if self._hyper is None:
+            if capturing:
+                raise RuntimeError("AdamW: the hyper-parameter row does not exist yet and cannot be created while a hipGraph is being "
+                                   "captured; run one eager step (or sync_hyper()) before the capture")
+            self._hyper = torch.zeros(len(self.param_groups), 4, dtype=torch.float32, device=self._device())
+        for gi, group in enumerate(self.param_groups):
+            have = self._uploaded[gi]
+            lr = None if self._schedule[gi] is not None else _f32(group["lr"])
+            wd = _f32(group["weight_decay"])
+            fields = (1 if lr is not None and lr != have[0] else 0) | (2 if wd != have[1] else 0)
+            if not fields:
+                continue
+            if capturing:
+                raise RuntimeError("AdamW.sync_hyper: lr / weight_decay changed on the host while a hipGraph is being captured -- the "
+                                   "upload would be replayed with every step; call sync_hyper() before the capture")
+            if (lr is not None and lr < 0) or wd < 0:
+                raise ValueError("invalid AdamW hyper-parameter")
+            call("unetr_adamw_hyper_set", self._hyper_ptr(gi), fields, lr or 0.0, wd, 0.0, torch.cuda.current_stream().cuda_stream)
+            self._uploaded[gi] = [lr if fields & 1 else have[0], wd]
+
+    def set_schedule(self, kind, *, warmup=0, total=None, power=0.9, min_lr=0.0):
+        """Attach the in-graph learning-rate schedule ``lr(s) = max(min_lr, base_lr * f(s))``, s = optimizer steps taken so far, to
+        every group (``base_lr`` = the group's ``lr`` now).  kind: "constant" (f = 1), "warmup_cosine" (linear 0 -> 1 over ``warmup``
+        steps, then half a cosine down to 0 at ``total``), "poly" (f = (1 - s / total) ** power).  The step-counter launch computes
+        it on the device, so a captured step schedules itself with no extra launch and no host work; the description is a launch
+        argument, hence it must be attached BEFORE a TrainStep captures."""
+        if kind not in SCHEDULES:
+            raise ValueError(f"unknown schedule {kind!r}: one of {sorted(SCHEDULES)}")
+        if self._captured:
+            raise RuntimeError("set_schedule: a captured step already uses this optimizer (the schedule is a launch argument frozen "
+                               "in the graph); attach the schedule before TrainStep captures")
+        if total is None:
+            if kind != "constant":
+                raise ValueError(f"schedule {kind!r} needs total=")
+            total = 0
+        if warmup < 0 or total < 0 or min_lr < 0 or (kind == "poly" and total <= 0):
+            raise ValueError("invalid schedule")
+        for gi, group in enumerate(self.param_groups):
+            desc = dict(kind=kind, warmup=int(warmup), total=int(total), power=float(power), min_lr=float(min_lr), base_lr=float(group["lr"]))
+            self._attach(gi, desc)
+
+    def _attach(self, gi, desc):
+        self._schedule[gi] = (desc, LrSchedule(SCHEDULES[desc["kind"]], desc["base_lr"], desc["min_lr"], desc["warmup"], desc["total"], desc["power"]))
+        self._uploaded[gi][0] = None
+
+    def schedule_lr(self, s, group=0):
+        """the rate the attached schedule gives optimizer step ``s`` (0-based): the device formula on the host, for logging and tests"""
+        if self._schedule[group] is None:
+            return _f32(self.param_groups[group]["lr"])
+        return schedule_lr(self._schedule[group][0], s)
+
+    def current_lr(self, group=0):
+        """the learning rate in device memory: what the last step used (synchronises with the device)"""
+        if self._hyper is None:
+            return self.schedule_lr(0, group)
+        return float(self._hyper[group, 0])
+
+    # ---- checkpoints in torch.optim.AdamW's schema ------------------------------------------------------------------------
+    def _arena_mode(self):
+        """the moments live in the flat arenas (self.state stays empty: begin_fused_step relies on that)"""
+        return self._flat is not None and not any(len(st) for st in self.state.values())
+
+    @torch.no_grad()
+    def state_dict(self):
+        """``{"state": {i: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups": [...]}`` as torch.optim.AdamW writes it, for every
+        parameter that has stepped -- in flat mode synthesised from the arenas (copies).  The groups also carry the schedule
+        description and the group's step count ``t``.  Loads into torch.optim.AdamW over the same parameters, and back."""
+        arena = self._arena_mode()
+        state, groups, base = {}, [], 0
+        for gi, group in enumerate(self.param_groups):
+            params = group["params"]
+            steps = self._steps[gi].cpu().tolist() if gi in self._steps else [0.0] * len(params)
+            for i, p in enumerate(params):
+                if steps[i] <= 0:
+                    continue
+                if arena:
+                    if self._flat_state is None:
+                        continue
+                    o, n = self._flat["offsets"][i], p.numel()
+                    m, v = (a[o:o + n].view(p.shape).clone() for a in self._flat_state)
+                else:
+                    st = self.state.get(p)
+                    if not st:
+                        continue
+                    m, v = st["exp_avg"].clone(), st["exp_avg_sq"].clone()
+                state[base + i] = {"step": torch.tensor(float(steps[i]), dtype=torch.float32), "exp_avg": m, "exp_avg_sq": v}
+            g = {k: v for k, v in group.items() if k != "params"}
+            g.update({k: v for k, v in _TORCH_GROUP_KEYS.items() if k not in g})
+            sched = self._schedule[gi] if gi < len(self._schedule) else None
+            g["schedule"] = dict(sched[0]) if sched is not None else None
+            g["t"] = int(self._hyper[gi, 2]) if self._hyper is not None else 0
+            if sched is not None and self._hyper is not None and g["t"] > 0:
+                g["lr"] = float(self._hyper[gi, 0])          # informational: the rate of the last step (the schedule recomputes it)
+            g["params"] = list(range(base, base + len(params)))
+            groups.append(g)
+            base += len(params)
+        return {"state": state, "param_groups": groups}
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        """Load a dict written by ``state_dict()`` or by torch.optim.AdamW over the same parameters.  Everything is copied IN PLACE
+        -- into the moment arenas (flat mode) or the existing per-tensor moments, the device step counters and the hyper rows --
+        so graphs captured before the call stay valid; it may run before or after capture, not during one."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("AdamW.load_state_dict cannot run while a hipGraph is being captured")
+        saved = state_dict["param_groups"]
+        if len(saved) != len(self.param_groups) or any(len(s["params"]) != len(g["params"]) for s, g in zip(saved, self.param_groups)):
+            raise ValueError("loaded state dict has different param groups than this optimizer")
+        if any(s.get("amsgrad") or s.get("maximize") for s in saved):
+            raise ValueError("HIP AdamW has no amsgrad / maximize variant")
+        if any(s.get("decoupled_weight_decay") is False for s in saved):
+            raise ValueError("the loaded state belongs to Adam with coupled (L2) weight decay, not AdamW")
+        arena = self._arena_mode()
+        dev = self._device()
+        # everything that can refuse is checked before the first byte is written
+        plans = []
+        for gi, (sg, group) in enumerate(zip(saved, self.param_groups)):
+            entries = [state_dict["state"].get(k) for k in sg["params"]]
+            steps = [float(e["step"]) if e else 0.0 for e in entries]
+            for p, e in zip(group["params"], entries):
+                if e and (tuple(e["exp_avg"].shape) != tuple(p.shape) or tuple(e["exp_avg_sq"].shape) != tuple(p.shape)):
+                    raise ValueError("loaded optimizer state does not match the parameter shapes")
+            if arena:
+                for i, j in self._runs_captured:
+                    if len(set(steps[i:j + 1])) > 1:
+                        raise RuntimeError("load_state_dict: parameters that an already captured launch steps with ONE shared counter "
+                                           f"(indices {i}..{j}) have different step counts in the loaded state")
+            cur = self._schedule[gi][0] if self._schedule[gi] is not None else None
+            desc = sg.get("schedule") if "schedule" in sg else cur       # (a dict from torch.optim.AdamW says nothing about schedules)
+            if desc is not None:
+                desc = dict(desc)
+                if desc.get("kind") not in SCHEDULES:
+                    raise ValueError(f"unknown schedule {desc.get('kind')!r} in the loaded state")
+            if self._captured and desc != cur:
+                raise RuntimeError("load_state_dict: the loaded schedule differs from the one frozen in an already captured step; "
+                                   "attach it with set_schedule() before TrainStep captures")
+            plans.append((entries, steps, desc))
+        self.sync_hyper()          # (creates the rows)
+        stream = torch.cuda.current_stream().cuda_stream
+        for gi, (sg, group) in enumerate(zip(saved, self.param_groups)):
+            entries, steps, desc = plans[gi]
+            for k in ("lr", "betas", "eps", "weight_decay"):
+                if k in sg:
+                    group[k] = tuple(sg[k]) if k == "betas" else sg[k]
+            if desc is not None:
+                self._attach(gi, desc)
+            elif self._schedule[gi] is not None:
+                self._schedule[gi] = None
+            params = group["params"]
+            self._step_tensor(gi, dev).copy_(torch.tensor(steps, dtype=torch.float32))
+            if arena:
+                if self._flat_state is None:
+                    self._flat_state = (torch.zeros_like(self._flat["param"]), torch.zeros_like(self._flat["param"]))
+                m, v = self._flat_state
+                m.zero_()
+                v.zero_()
+                for p, o, e in zip(params, self._flat["offsets"], entries):
+                    if e:
+                        m[o:o + p.numel()].copy_(e["exp_avg"].reshape(-1))
+                        v[o:o + p.numel()].copy_(e["exp_avg_sq"].reshape(-1))
+                self._host_steps = [int(t) for t in steps]
+            else:
+                for p, e in zip(params, entries):
+                    st = self.state.get(p)
+                    if not e:
+                        if st:
+                            st["exp_avg"].zero_()
+                            st["exp_avg_sq"].zero_()
+                        continue
+                    if not st:
+                        st = self.state[p]
+                        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                        st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                    st["exp_avg"].copy_(e["exp_avg"])
+                    st["exp_avg_sq"].copy_(e["exp_avg_sq"])
+                if self._flat is not None:
+                    self._host_steps = [int(t) for t in steps]
+            # (a group never took fewer steps than one of its parameters: a dict that went through torch.optim.AdamW carries no
+            # "t", or the one it was given when it loaded a dict of ours)
+            t = max(float(sg.get("t", 0)), max(steps, default=0.0))
+            call("unetr_adamw_hyper_set", self._hyper_ptr(gi), 4, 0.0, 0.0, t, stream)
+        self.sync_hyper()          # the loaded lr / weight_decay
+
+    def _advance_steps(self, gi, params, pattern, dev):
+        self.sync_hyper()
+        if torch.cuda.is_current_stream_capturing():
+            self._captured = True
+        steps = self._step_tensor(gi, dev)
         mask = self._masks.get((gi, pattern))
         if mask is None:
             mask = torch.tensor([1.0 if f else 0.0 for f in pattern], dtype=torch.float32, device=dev)
             self._masks[(gi, pattern)] = mask
-        call("unetr_counter_add", steps.data_ptr(), mask.data_ptr(), steps.numel(), torch.cuda.current_stream().cuda_stream)
+        # one launch: the per-parameter counters, the group's step count t and -- with a schedule attached -- this step's lr
+        sched = self._schedule[gi]
+        call("unetr_counter_add_lr", steps.data_ptr(), mask.data_ptr(), steps.numel(), self._hyper_ptr(gi),
+             ctypes.byref(sched[1]) if sched is not None else None, torch.cuda.current_stream().cuda_stream)
         return steps
 
     @torch.no_grad()
@@ -73,9 +325,8 @@ class AdamW(torch.optim.Optimizer):
                 if not st:
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                call("unetr_adamw", p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(),
-                     group["lr"], b1, b2, group["eps"], group["weight_decay"], steps.data_ptr() + 4 * i,
-                     Fn.shadow_ptr_for_update(p), stream)
+                call("unetr_adamw_hyper", p.data_ptr(), g.data_ptr(), 0, 1.0, st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(),
+                     self._hyper_ptr(gi), b1, b2, group["eps"], steps.data_ptr() + 4 * i, Fn.shadow_ptr_for_update(p), None, stream)
         if self._flat is not None and per_tensor:
             Fn.refresh_x3_shadow(self._flat)      # (per-tensor launches do not write the bf16x3 word shadow: one derive launch)
             Fn.refresh_wt_shadow(self._flat, [p for g in self.param_groups for p in g["params"] if p.grad is not None])
@@ -110,9 +361,11 @@ class AdamW(torch.optim.Optimizer):
         sptr = shadow.data_ptr() + lo * 2 if shadow is not None else None
         words = flat.get("shadow_x3")          # bf16x3 mode: the word shadow (functional.weight_x3), written by the same kernel
         wptr = words.data_ptr() + lo * 4 if words is not None else None
-        call("unetr_adamw_reduced", flat["param"].data_ptr() + lo * 4, gptr + lo * (2 if g_bf16 else 4), int(g_bf16), gscale,
-             m.data_ptr() + lo * 4, v.data_ptr() + lo * 4, hi - lo, group["lr"], b1, b2, group["eps"], group["weight_decay"],
+        call("unetr_adamw_hyper", flat["param"].data_ptr() + lo * 4, gptr + lo * (2 if g_bf16 else 4), int(g_bf16), gscale,
+             m.data_ptr() + lo * 4, v.data_ptr() + lo * 4, hi - lo, self._hyper_ptr(0), b1, b2, group["eps"],
              steps.data_ptr() + 4 * i, sptr, wptr, stream)
+        if torch.cuda.is_current_stream_capturing():
+            self._runs_captured.add((i, j))
         for k in range(i, j + 1):
             self._host_steps[k] += 1
 
@@ -166,7 +419,8 @@ class AdamW(torch.optim.Optimizer):
         words = flat.get("shadow_x3")
         arena = _capi.AdamWArena(flat["param"].data_ptr(), flat["grad"].data_ptr(), m.data_ptr(), v.data_ptr(),
                                  shadow.data_ptr() if shadow is not None else None, steps.data_ptr(), flat["param"].numel(),
-                                 group["lr"], b1, b2, group["eps"], group["weight_decay"], words.data_ptr() if words is not None else None)
+                                 group["lr"], b1, b2, group["eps"], group["weight_decay"], words.data_ptr() if words is not None else None,
+                                 self._hyper_ptr(0))      # (the kernels read lr / weight_decay from the row; the by-value fields are not used)
         gbase = flat["grad"].data_ptr()
         index = {gbase + o * 4: i for i, (o, has) in enumerate(zip(flat["offsets"], pattern)) if has}
         self._fused = dict(pattern=pattern, arena=arena, index=index, done=[], keep=(m, v, steps), flat=flat, wt_done=[])
@@ -196,6 +450,8 @@ class AdamW(torch.optim.Optimizer):
         # their boundaries are part of the key (alternating patterns -- the feat / recon passes of the ranking pre-training --
         # make counts diverge between two uses of the same pattern)
         runs = self._flat_runs(params, rest)
+        if torch.cuda.is_current_stream_capturing():
+            self._runs_captured.update((i, j) for i, j, _, _ in runs)
         key = (pattern, tuple(sorted(done)), tuple((i, j) for i, j, _, _ in runs))
         cache = getattr(self, "_range_tables", None)
         if cache is None:

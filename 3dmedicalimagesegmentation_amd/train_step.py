@@ -371,6 +371,11 @@ class TrainStep:
 
     def run(self):
         """one training step; returns nothing (self.loss is the device scalar of this step)"""
+        # lr / weight_decay changed on the host since the last step (a torch.optim.lr_scheduler, a plain assignment): written to the
+        # optimizer's device row on the launching stream, ahead of the replay -- the captured kernels read them from there
+        sync = getattr(self.opt, "sync_hyper", None)
+        if sync is not None:
+            sync()
         if self.graphs is None:
             self._eager_step()
         elif not self.dp or self.one_graph:

@@ -372,6 +372,21 @@ int unetr_nhwc_to_nchw(const void* x /* feature map */, long ldx, float* y /* fp
 int unetr_patch_gather(const float* x, float* patches, void* patches_bf16, int B, int C, int D, int H, int W, int P, void* stream);
 /* y[i] += inc[i], i < n: AdamW's per-parameter step counters (device-resident so that the step can be a hipGraph) */
 int unetr_counter_add(float* y, const float* inc, int n, void* stream);
+/* ---- AdamW hyper-parameter row: four floats in DEVICE memory, {lr, weight_decay, t, reserved}, one row per param group.  The
+ * optimizer kernels that are given a row read lr / weight_decay from it when they run, not when they are launched: a captured step
+ * follows a learning-rate change without being captured again.  t = number of optimizer steps taken (a float like the per-parameter
+ * counters: exact to 2^24 steps).
+ * unetr_lr_schedule (passed BY VALUE into the launch): lr = max(min_lr, base_lr * f(s)), s = t before the increment -- the first
+ * step uses f(0), as torch.optim.lr_scheduler does.  kind 0 constant: f = 1.  kind 1 warm-up + cosine: s < warmup: f = s / max(1, warmup),
+ * else f = 0.5 (1 + cos(pi min(1, (s - warmup) / max(1, total - warmup)))).  kind 2 poly (nnU-Net): f = (1 - min(s, total) / total)^power,
+ * total > 0.  f is computed in double and lr rounded once to float. */
+typedef struct { int kind; float base_lr, min_lr, warmup, total, power; } unetr_lr_schedule;
+/* unetr_counter_add that also keeps a hyper row, in the SAME launch (the captured step gains no launch): one thread sets
+ * row.lr from the schedule at row.t (s == NULL: lr is left as the host wrote it), then row.t += 1. */
+int unetr_counter_add_lr(float* y, const float* inc, int n, float* hyper_row, const unetr_lr_schedule* s, void* stream);
+/* stream-ordered write of the row fields selected by `fields` (bit 0: lr, bit 1: weight_decay, bit 2: t) from by-value arguments:
+ * one single-thread launch, no host synchronisation, no staging buffer */
+int unetr_adamw_hyper_set(float* hyper_row, int fields, float lr, float weight_decay, float t, void* stream);
 /* y[r, 0:cols] (+)= a[r, 0:cols] for row-pitched matrices (skip -> concat buffer, gradient sums) */
 int unetr_copy_rows(void* y, long ldy, const void* a, long lda, long rows, int cols, int accumulate, int act16, void* stream);
 
@@ -561,6 +576,11 @@ int unetr_adamw_reduced(float* p, const void* g, int g_is_bf16, float gscale, fl
                         void* shadow_bf16, void* shadow_x3 /* optional: bf16x3 word shadow of the updated p (unetr_split_words), or NULL */,
                         void* stream);
 
+/* the streaming form that reads lr / weight_decay from a hyper row (see unetr_counter_add_lr) when the kernel runs: the argument set of
+ * unetr_adamw_reduced with hyper_dev in place of (lr, weight_decay).  The same float lr gives the same bits as the by-value forms. */
+int unetr_adamw_hyper(float* p, const void* g, int g_is_bf16, float gscale, float* m, float* v, long n, const float* hyper_dev,
+                      float beta1, float beta2, float eps, const float* step_dev, void* shadow_bf16, void* shadow_x3, void* stream);
+
 /* ---- the single-GPU step's optimizer fused into the producer of the gradients (train_step.TrainStep(fuse_update=True)) ------
  * The four arenas (parameters, gradients, both moments; fp32, `total` elements, identical layout) and the optional bf16 shadow
  * arena of the parameters; steps = per-parameter step counts (float, already advanced for this step). */
@@ -568,6 +588,11 @@ typedef struct {
     float* param; const float* grad; float* m; float* v; void* shadow_bf16; const float* steps; long total;
     float lr, beta1, beta2, eps, weight_decay;
     void* shadow_x3;                  /* optional arena of bf16x3 words (unetr_split_words layout), written next to shadow_bf16; or NULL */
+    const float* hyper;               /* optional hyper row in device memory: lr / weight_decay are read from it by the kernels (unetr_adamw_ranges,
+                                         unetr_gemm_bf16_grouped_wgrad_adamw[_t]) instead of the by-value fields above; or NULL.
+                                         (A trailing addition: a caller that zero-initialises the struct and sets the fields above keeps
+                                         the by-value behaviour.  No existing signature moved, UNETR_ABI_VERSION stays -- a binding that
+                                         knows this field also declares unetr_adamw_hyper, which an older library does not export.) */
 } unetr_adamw_arena;
 /* grouped ViT weight gradients (unetr_gemm_bf16_grouped_wgrad) whose epilogue APPLIES AdamW instead of storing dW: every
  * probs[i].dw must address a slice of a->grad (it is not written); the parameter / moment / shadow slices at the same arena
