@@ -12,12 +12,12 @@ from .metrics import ConfusionMatrixMetric, HausdorffDistanceMetric  # noqa: F40
 from .postprocess import KeepLargestConnectedComponent, connected_components, remove_small_components  # noqa: F401
 from .train_step import TrainStep  # noqa: F401
 from .augment import RandCropAugment, VolumeCache  # noqa: F401
-from .preprocess import resample_orient  # noqa: F401
+from .preprocess import Geometry, resample_orient, restore_native  # noqa: F401
 from .functional import invalidate_weight_shadows, refresh_derived_weights  # noqa: F401
 from . import _capi, augment, ddp, functional, inference, metrics, postprocess, preprocess, train_step  # noqa: F401
 
 __all__ = ["UNETR", "UNETRLogits", "DiceCELoss", "ranking_loss", "AdamW", "default_precision", "sliding_window_inference",
            "SlidingWindowInferer", "DiceMetric", "ConfusionMatrixMetric", "HausdorffDistanceMetric", "TrainStep", "invalidate_weight_shadows",
            "refresh_derived_weights",
-           "VolumeCache", "RandCropAugment", "resample_orient", "KeepLargestConnectedComponent", "connected_components",
+           "VolumeCache", "RandCropAugment", "resample_orient", "restore_native", "Geometry", "KeepLargestConnectedComponent", "connected_components",
            "remove_small_components"]

@@ -96,6 +96,10 @@ class SwVolume(ctypes.Structure):
                 ("cval", c_float), ("rows", c_int), ("cursor", c_int)]
 
 
+class RestoreGeom(ctypes.Structure):      # unetr_restore_geom, passed by value
+    _fields_ = [("m", c_double * 12), ("full", c_int * 3), ("origin", c_int * 3), ("crop", c_int * 3)]
+
+
 SW_MAX_BATCH = 16                      # = UNETR_SW_MAX_BATCH
 SW_ROW_INTS = 4 + 4 * SW_MAX_BATCH     # = UNETR_SW_ROW_INTS
 
@@ -195,6 +199,7 @@ _SIGNATURES = {
     "unetr_aug_sample": [ctypes.POINTER(AugDesc), P, c_int, P, P, P, P],
     "unetr_aug_gather": [ctypes.POINTER(AugDesc), P, c_int, P, P, P, P, c_size_t, P],
     "unetr_resample_orient": [P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_double), c_int, c_int, c_int, P, P, P],
+    "unetr_restore_native": [P, c_int, c_int, RestoreGeom, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
     "unetr_ccl": [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint, c_int, c_int, c_int, c_int, P, c_size_t, c_int, P],
     "unetr_ranking_loss_fwd": [P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P, P, P, c_size_t, P],
     "unetr_ranking_loss_bwd": [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P],

@@ -41,6 +41,8 @@ class VolumeCache:
         self._vols = []          # (image, label, fg, bg)
         self.shapes = []         # (C, L, D, H, W) per volume
         self._affines = {}       # volume id -> 4x4 affine after add_raw's Spacing -> Orientation
+        self._geometry = {}      # volume id -> preprocess.Geometry of add_raw (with the foreground crop): the way back
+        self._origins = []       # per volume: (z0, y0, x0) of CropForegroundd's box on the grid add() was given
         self._table = None
 
     def __len__(self):
@@ -103,6 +105,7 @@ class VolumeCache:
                  bg.data_ptr(), st)
         self._vols.append((oimg, olbl, fg[:nfg], bg[:nbg]))
         self.shapes.append((C, L, d, h, w))
+        self._origins.append((z0, y0, x0))
         self._table = None
         return len(self._vols) - 1
 
@@ -115,6 +118,8 @@ class VolumeCache:
         img, lbl, new_affine = preprocess.resample_orient(image, label, affine, pixdim, axcodes, label_converter)
         i = self.add(img, lbl, scale_range=scale_range, crop_foreground=crop_foreground)
         self._affines[i] = new_affine
+        geom = preprocess.geometry(image.shape[1:], affine, pixdim, axcodes)
+        self._geometry[i] = geom.cropped(self._origins[i], self.shapes[i][2:])
         return i
 
     def affine(self, i: int):
@@ -125,6 +130,19 @@ class VolumeCache:
         if i not in self._affines:
             raise ValueError(f"volume {i} was added with add(): no affine is known")
         return self._affines[i].copy()
+
+    def geometry(self, i: int) -> "preprocess.Geometry":
+        """what add_raw's Spacing -> Orientation -> CropForeground did to volume i (preprocess.Geometry): the record
+        ``restore`` needs to map a prediction back onto the scan's own voxel grid"""
+        if not 0 <= i < len(self._vols):
+            raise IndexError(f"volume {i} out of range")
+        if i not in self._geometry:
+            raise ValueError(f"volume {i} was added with add(): no affine is known")
+        return self._geometry[i]
+
+    def restore(self, i: int, pred: torch.Tensor, **kw) -> torch.Tensor:
+        """preprocess.restore_native(pred, self.geometry(i), **kw): a prediction on volume i's grid -> the scan's native grid"""
+        return preprocess.restore_native(pred, self.geometry(i), **kw)
 
     def image(self, i: int) -> torch.Tensor:
         return self._vols[i][0].unsqueeze(0)

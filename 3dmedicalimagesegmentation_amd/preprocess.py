@@ -6,18 +6,27 @@ Both transforms are affine maps on voxel indices, so ``plan`` folds them on the 
 and ``resample_orient`` runs one HIP gather (csrc/preprocess.hip): trilinear for the image, round-half-even nearest for the label,
 border clamping, MONAI 0.6.0 semantics (align_corners=False, diagonal=False) as restated in tests/preprocess_ref.py and
 DESIGN.md section 13.  ``VolumeCache.add_raw`` puts it in front of ``VolumeCache.add``.  No CPU fallback.
+
+The way back: ``geometry`` records what ``plan`` decided (and ``VolumeCache.add_raw`` the foreground crop), and ``restore_native``
+maps a prediction on the cropped 1 mm grid onto the scan's own voxel grid with one HIP gather (csrc/restore.hip): the inverse of
+Spacingd -> Orientationd -> CropForegroundd, with argmax / sigmoid threshold / the BraTS label rule fused in (DESIGN.md section 17,
+restated in tests/restore_ref.py).
 """
 import ctypes
+import dataclasses
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import functional as Fn
-from ._capi import call
+from ._capi import RestoreGeom, call
 
 LABEL_CONVERTERS = (None, "brats")
+RESTORE_MODES = ("nearest", "linear")
+RESTORE_POST = {None: 0, "argmax": 1, "sigmoid": 2}
 _MAXC = 8
+_RESTORE_MAXC = 16
 _AXCODE_LABELS = (("L", "R"), ("P", "A"), ("I", "S"))
 
 
@@ -153,3 +162,127 @@ def resample_orient(image: torch.Tensor, label: Optional[torch.Tensor], affine, 
              C, L, int(label_converter == "brats"), n[0], n[1], n[2], m, out_shape[0], out_shape[1], out_shape[2], oimg.data_ptr(),
              olbl.data_ptr() if olbl is not None else None, Fn._stream())
     return oimg, olbl, new_affine
+
+
+# ---------------------------------------------------------------- the way back: native grid <- cropped 1 mm grid
+def _frozen(a, shape):
+    a = np.array(a, dtype=np.float64).reshape(shape)
+    a.setflags(write=False)
+    return a
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class Geometry:
+    """What Spacing -> Orientation -> CropForeground did to one scan, as far as the way back needs it (host, float64):
+
+    native_shape      (n0, n1, n2) of the file
+    affine            the file's 4x4 affine (what a NIfTI of the restored mask is written with)
+    pixdim, axcodes   as given to ``plan``
+    full_shape        the resampled and oriented grid before any crop
+    forward           4x4 ``T @ M`` exactly as ``plan`` decided it (``T = I`` under the copy rule): native index = forward @ [j, 1]
+    oriented_affine   the affine after Orientation (``VolumeCache.affine``)
+    crop_origin, crop_shape   the foreground box on the full grid; origin 0 and the full shape when there was no crop
+    """
+    native_shape: Tuple[int, int, int]
+    affine: np.ndarray
+    pixdim: Tuple[float, float, float]
+    axcodes: str
+    full_shape: Tuple[int, int, int]
+    forward: np.ndarray
+    oriented_affine: np.ndarray
+    crop_origin: Tuple[int, int, int]
+    crop_shape: Tuple[int, int, int]
+
+    def cropped(self, origin: Sequence[int], shape: Sequence[int]) -> "Geometry":
+        """a copy whose box is ``origin`` .. ``origin + shape - 1`` of the full grid; nothing else changes"""
+        o, s = tuple(int(v) for v in origin), tuple(int(v) for v in shape)
+        if len(o) != 3 or len(s) != 3 or any(a < 0 or b < 1 or a + b > f for a, b, f in zip(o, s, self.full_shape)):
+            raise ValueError(f"crop box origin {o} shape {s} does not lie inside the grid {self.full_shape}")
+        return dataclasses.replace(self, crop_origin=o, crop_shape=s)
+
+    def inverse_matrix(self) -> np.ndarray:
+        """3x4 float64: native index (i, 1) -> coordinate on the full resampled grid, the exact inverse of ``forward`` (MONAI
+        0.6.0's Spacingd.inverse resamples with inv(new_affine) @ old_affine).  A scan that was copied forward (an all-integer
+        ``forward``: a signed permutation with integer offsets) has an all-integer inverse and is copied back."""
+        inv = np.linalg.inv(self.forward)
+        if np.array_equal(self.forward, np.rint(self.forward)) and np.abs(inv - np.rint(inv)).max() < 1e-9:
+            inv = np.rint(inv) + 0.0                    # + 0.0: no negative zeros
+        return np.ascontiguousarray(inv[:3])
+
+
+def geometry(shape: Sequence[int], affine, pixdim: Sequence[float] = (1.0, 1.0, 1.0), axcodes: str = "RAS") -> Geometry:
+    """the Geometry of a volume of spatial ``shape`` with the 4x4 ``affine`` under ``plan(shape, affine, pixdim, axcodes)``, uncropped"""
+    out_shape, mat, new_affine = plan(shape, affine, pixdim, axcodes)
+    A = np.array(affine.detach().cpu().numpy() if isinstance(affine, torch.Tensor) else affine, dtype=np.float64)
+    return Geometry(native_shape=tuple(int(s) for s in shape), affine=_frozen(A, (4, 4)),
+                    pixdim=tuple(float(p) for p in np.array(pixdim, dtype=np.float64).reshape(-1)), axcodes="".join(axcodes),
+                    full_shape=tuple(out_shape), forward=_frozen(np.vstack([mat, [0.0, 0.0, 0.0, 1.0]]), (4, 4)),
+                    oriented_affine=_frozen(new_affine, (4, 4)), crop_origin=(0, 0, 0), crop_shape=tuple(out_shape))
+
+
+def restore_native(pred: torch.Tensor, geometry: Geometry, mode: str = "nearest", post: Optional[str] = None,
+                   label_converter: Optional[str] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A prediction on the (cropped) resampled grid -> the scan's own voxel grid: the inverse of CropForegroundd, Orientationd
+    and Spacingd in one gather.  pred [C, d, h, w] or [1, C, d, h, w] with (d, h, w) = geometry.crop_shape, float32 (what
+    SlidingWindowInferer returns for every ``post``) or, for mode="nearest", uint8 (cache labels); C <= 16.
+
+        mode="nearest"                    [C, n0, n1, n2] of pred's dtype: the picked voxel (class ids, one-hot, multi-label)
+        mode="linear"                     float32 [C, ...]: trilinear scores
+        mode="linear", post="argmax"      uint8 [1, ...] class ids, first maximal channel; the C-channel volume is never stored
+        mode="linear", post="sigmoid"     uint8 [C, ...]: interpolated logit >= 0
+        ... + label_converter="brats"     (any discrete result of the 4 channels BG / TC / WT / ET) uint8 [1, ...] label map:
+                                          1 where WT, then 2 where TC, then 3 where ET, else 0
+
+    Native voxels whose nearest grid point lies outside the crop box are background: 0 in every output.  ``out`` receives the
+    result when given (contiguous, on pred's device).  Launches one kernel on the current stream; no host synchronisation."""
+    if not isinstance(geometry, Geometry):
+        raise ValueError(f"geometry must be a preprocess.Geometry, got {type(geometry).__name__}")
+    if mode not in RESTORE_MODES:
+        raise ValueError(f"mode must be one of {RESTORE_MODES}, got {mode!r}")
+    if post not in RESTORE_POST:
+        raise ValueError(f"post must be one of {list(RESTORE_POST)}, got {post!r}")
+    if label_converter not in LABEL_CONVERTERS:
+        raise ValueError(f"label_converter must be one of {LABEL_CONVERTERS}, got {label_converter!r}")
+    if post is not None and mode == "nearest":
+        raise ValueError(f"post={post!r} reduces interpolated scores: it needs mode='linear'")
+    if pred.dim() == 5:
+        if pred.shape[0] != 1:
+            raise ValueError(f"one scan per call (each has its own geometry), got a batch of {pred.shape[0]}")
+        pred = pred[0]
+    if pred.dim() != 4:
+        raise ValueError(f"pred [C, d, h, w] or [1, C, d, h, w] expected, got {tuple(pred.shape)}")
+    C = pred.shape[0]
+    if tuple(pred.shape[1:]) != tuple(geometry.crop_shape):
+        raise ValueError(f"pred's spatial shape {tuple(pred.shape[1:])} is not the geometry's crop shape {tuple(geometry.crop_shape)}")
+    if not 0 < C <= _RESTORE_MAXC:
+        raise ValueError(f"1..{_RESTORE_MAXC} channels supported, got {C}")
+    linear, brats = mode == "linear", label_converter == "brats"
+    if pred.dtype != torch.float32 and not (pred.dtype == torch.uint8 and not linear):
+        raise ValueError(f"pred must be float32 (or uint8 with mode='nearest'), got {pred.dtype} with mode={mode!r}")
+    if brats and C != 4:
+        raise ValueError(f"label_converter='brats' takes the 4 channels background / TC / WT / ET, got {C}")
+    if brats and linear and post is None:
+        raise ValueError("label_converter='brats' needs a discrete result: mode='nearest', or post='argmax' / 'sigmoid'")
+    n = tuple(geometry.native_shape)
+    if n[0] * n[1] * n[2] >= 2 ** 31 or int(np.prod(geometry.full_shape, dtype=np.int64)) >= 2 ** 31:
+        raise ValueError("volumes of at most 2**31 - 1 voxels (native and resampled) are supported")
+    out_dtype = torch.uint8 if (post is not None or brats) else pred.dtype
+    out_shape = (1 if (brats or post == "argmax") else C, *n)
+    if out is not None:
+        if tuple(out.shape) != out_shape or out.dtype != out_dtype:
+            raise ValueError(f"out {list(out_shape)} of {out_dtype} expected, got {list(out.shape)} of {out.dtype}")
+        if not out.is_contiguous() or out.device != pred.device:
+            raise ValueError("out must be contiguous and on pred's device")
+    if not pred.is_cuda:
+        raise RuntimeError("3dmedicalimagesegmentation_amd: the HIP backend needs tensors on a ROCm device "
+                           "(got a CPU tensor); there is no CPU fallback.")
+    g = RestoreGeom()
+    g.m[:] = geometry.inverse_matrix().reshape(-1).tolist()
+    g.full[:], g.origin[:], g.crop[:] = geometry.full_shape, geometry.crop_origin, geometry.crop_shape
+    with torch.cuda.device(pred.device):
+        src = pred.detach().contiguous()
+        if out is None:
+            out = torch.empty(out_shape, dtype=out_dtype, device=pred.device)
+        call("unetr_restore_native", src.data_ptr(), int(src.dtype == torch.uint8), C, g, n[0], n[1], n[2], int(linear),
+             RESTORE_POST[post], int(brats), out.data_ptr(), Fn._stream())
+    return out

@@ -540,6 +540,33 @@ int unetr_aug_gather(const UnetrAugDesc* d, const long long* vols, int nvol, con
 int unetr_resample_orient(const void* img, int img_int16, const unsigned char* lbl, int C, int L, int brats, int n0, int n1, int n2,
                           const double* mat, int D, int H, int W, float* oimg, unsigned char* olbl, void* stream);
 
+/* ---- predictions back onto a scan's own voxel grid (csrc/restore.hip) ----
+ * The inverse of Spacingd -> Orientationd -> CropForegroundd as one gather (MONAI 0.6.0's Spacingd.inverse / Orientationd.inverse /
+ * CropForegroundd.inverse; for BraTS the label rule of ConvertFromMultiChannelToRGB, unetr_segmentation_3d.py:95-101).  src
+ * [C, crop[0], crop[1], crop[2]] (float32, or uint8 when src_u8) lives on the box origin .. origin + crop - 1 of the resampled and
+ * oriented grid of extents full.  Every native voxel (i0, i1, i2) of the grid [n0, n1, n2]: s = clamp(m @ (i0, i1, i2, 1), 0,
+ * full - 1) in fp64 (m: 3x4 row-major, the inverse of the forward matrix); r = rint(s), half to even; r outside the box on any
+ * axis: background, every output for the voxel is 0; else nearest reads src[r - origin] and linear blends the eight taps around
+ * clamp(s - origin, 0, crop - 1) with fp32 weights.  An all-integer m takes the one-tap path in every mode (bits returned).
+ *   linear = 0            out = the picked voxel: float32 / uint8 [C, n0, n1, n2] (dtype of src); post must be 0
+ *   linear = 1, post = 0  out = float32 [C, ...] trilinear scores (float32 src only)
+ *   linear = 1, post = 1  out = uint8 [1, ...]: argmax over the C interpolated channels, first maximal channel
+ *   linear = 1, post = 2  out = uint8 [C, ...]: interpolated logit >= 0
+ *   brats = 1             (linear = 0, or post != 0; C = 4: background / TC / WT / ET) out = uint8 [1, ...]: 1 where WT, then 2
+ *                         where TC, then 3 where ET, else 0.  A channel is set where the picked value == 1 (linear = 0), the
+ *                         logit >= 0 (post = 2) or it is the argmax (post = 1).
+ * 1 <= C <= 16.  The struct is passed BY VALUE; no workspace, no allocation, no host synchronisation.  UNETR_ERR_UNSUPPORTED for
+ * more than 2^31 - 1 voxels on either grid or a launch-grid dimension over 65535.
+ * (Additions: no existing signature moved, UNETR_ABI_VERSION stays.) */
+typedef struct {
+    double m[12];
+    int full[3];
+    int origin[3];
+    int crop[3];
+} unetr_restore_geom;
+int unetr_restore_native(const void* src, int src_u8, int C, unetr_restore_geom g, int n0, int n1, int n2, int linear, int post,
+                         int brats, void* out, void* stream);
+
 /* ---- connected-component post-processing (csrc/postprocess.hip; monai.transforms.KeepLargestConnectedComponent of MONAI 0.6.0
  * and the min_size rule of skimage.morphology.remove_small_objects) ----
  * unetr_ccl labels the 3-D connected components of in and filters them, per *plane* of class words w (0 = not filtered):
