@@ -8,7 +8,8 @@ from .unetr import UNETR, UNETRLogits, default_precision  # noqa: F401
 from .losses import DiceCELoss, ranking_loss  # noqa: F401
 from .optim import AdamW  # noqa: F401
 from .inference import DiceMetric, SlidingWindowInferer, sliding_window_inference  # noqa: F401
-from .metrics import ConfusionMatrixMetric, HausdorffDistanceMetric  # noqa: F401
+from .metrics import (ConfusionMatrixMetric, HausdorffDistanceMetric, SurfaceDiceMetric, SurfaceDistanceMetric,  # noqa: F401
+                      surface_metrics)
 from .postprocess import KeepLargestConnectedComponent, connected_components, remove_small_components  # noqa: F401
 from .train_step import TrainStep  # noqa: F401
 from .augment import RandCropAugment, VolumeCache  # noqa: F401
@@ -20,4 +21,4 @@ __all__ = ["UNETR", "UNETRLogits", "DiceCELoss", "ranking_loss", "AdamW", "defau
            "SlidingWindowInferer", "DiceMetric", "ConfusionMatrixMetric", "HausdorffDistanceMetric", "TrainStep", "invalidate_weight_shadows",
            "refresh_derived_weights",
            "VolumeCache", "RandCropAugment", "resample_orient", "restore_native", "Geometry", "KeepLargestConnectedComponent", "connected_components",
-           "remove_small_components"]
+           "remove_small_components", "surface_metrics", "SurfaceDistanceMetric", "SurfaceDiceMetric"]

@@ -192,6 +192,8 @@ _SIGNATURES = {
     "unetr_sw_accumulate_batch": [P, P, P, c_int, c_int, c_int, c_int, c_int, P],
     "unetr_sw_finalize_post": [P, P, P, c_int, c_int, c_long, c_int, P],
     "unetr_hausdorff": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, P, P, c_size_t, c_int, P],
+    "unetr_surface_metrics": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_double), ctypes.POINTER(c_double), c_int,
+                              ctypes.POINTER(c_double), P, P, c_size_t, c_int, P],
     "unetr_aug_prep": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, P, P, P],
     "unetr_aug_crop": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P],
     "unetr_aug_index_count": [P, P, c_int, c_int, c_long, c_float, P, c_size_t, P],
@@ -210,7 +212,8 @@ _SIGNATURES = {
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + ("unetr_conv3_packed_bytes", "unetr_conv3_packed_1x1_bytes", "unetr_ranking_workspace_floats",
                                             "unetr_conv3_wgrad_rows", "unetr_tconv2_wgrad_rows", "unetr_outconv_in_bwd_rows", "unetr_hausdorff_workspace_bytes",
-                                            "unetr_aug_index_ws_ints", "unetr_aug_gather_ws_bytes", "unetr_ccl_workspace_bytes")
+                                            "unetr_aug_index_ws_ints", "unetr_aug_gather_ws_bytes", "unetr_ccl_workspace_bytes",
+                                            "unetr_surface_metrics_workspace_bytes")
 
 _lib = None
 
@@ -248,6 +251,8 @@ def load():
     lib.unetr_ranking_workspace_floats.restype = c_size_t
     lib.unetr_hausdorff_workspace_bytes.argtypes = [c_int] * 7
     lib.unetr_hausdorff_workspace_bytes.restype = c_size_t
+    lib.unetr_surface_metrics_workspace_bytes.argtypes = [c_int] * 7
+    lib.unetr_surface_metrics_workspace_bytes.restype = c_size_t
     lib.unetr_ccl_workspace_bytes.argtypes = [c_int] * 4
     lib.unetr_ccl_workspace_bytes.restype = c_size_t
     lib.unetr_aug_index_ws_ints.argtypes = [c_long]

@@ -303,11 +303,11 @@ def _as_act(t, prec):
     return t if t.dtype == dt else t.to(dt)
 
 
-def _require_gpu(t, act=False):
+def _require_gpu(t, act=False, ids=False):
     if not t.is_cuda:
         raise RuntimeError("3dmedicalimagesegmentation_amd: the HIP backend needs tensors on a ROCm device "
                            "(got a CPU tensor); there is no CPU fallback.")
-    if t.dtype != torch.float32 and not (act and t.dtype == torch.bfloat16):
+    if t.dtype != torch.float32 and not (act and t.dtype == torch.bfloat16) and not (ids and t.dtype == torch.uint8):
         raise RuntimeError(f"3dmedicalimagesegmentation_amd: fp32 storage expected, got {t.dtype}")
     if t.device.index != torch.cuda.current_device():
         # kernels are launched on the CURRENT device's stream with raw pointers: a tensor of another GPU would fault

@@ -200,6 +200,11 @@ class Geometry:
             raise ValueError(f"crop box origin {o} shape {s} does not lie inside the grid {self.full_shape}")
         return dataclasses.replace(self, crop_origin=o, crop_shape=s)
 
+    def native_spacing(self) -> Tuple[float, float, float]:
+        """voxel sizes of the file's own grid (the column norms of ``affine[:3, :3]``) in the file's axis order: the ``spacing``
+        that goes with a ``restore_native`` mask.  ``pixdim`` is the spacing of the resampled grid."""
+        return tuple(float(v) for v in np.sqrt((self.affine[:3, :3] ** 2).sum(axis=0)))
+
     def inverse_matrix(self) -> np.ndarray:
         """3x4 float64: native index (i, 1) -> coordinate on the full resampled grid, the exact inverse of ``forward`` (MONAI
         0.6.0's Spacingd.inverse resamples with inv(new_affine) @ old_affine).  A scan that was copied forward (an all-integer

@@ -480,6 +480,22 @@ int unetr_sw_finalize_post(float* out, const float* count, float* dst, int B, in
 size_t unetr_hausdorff_workspace_bytes(int B, int C, int D, int H, int W, int group, int use_percentile);
 int unetr_hausdorff(const float* pred, const float* y, int B, int C, int D, int H, int W, int c0, int from_logits,
                     int use_percentile, double q, int directed, double* out, void* ws, size_t ws_bytes, int group, void* stream);
+/* unetr_surface_metrics: every surface metric of one (pred, gt) batch from ONE spacing-aware exact distance transform, in the
+ * units of spacing[3] (float64 per step along D, H, W; host memory, each finite and > 0).  Same front end, edge rule and limits as
+ * unetr_hausdorff.  input_form 0: one-hot float32 [B,C,D,H,W] for both (mask = value == 1); 1: float32 logits [B,C,D,H,W] and
+ * float32 class ids [B,1,D,H,W]; 2: uint8 class ids [B,1,D,H,W] for both.  percentiles: npct <= 8 fractions in [0, 1] (host),
+ * np.percentile's linear rule; thresholds: C - c0 tolerances, one per evaluated class (host), or NULL.
+ * out (float64, device) is [8 + 2 * npct][B * (C - c0)]: edge counts n_pred, n_gt; max d(P->G), max d(G->P); mean d(P->G),
+ * mean d(G->P); #(d(P->G) <= tau_c), #(d(G->P) <= tau_c); then the npct percentiles of d(P->G) and those of d(G->P).  A direction
+ * without query edges gives nan for max / mean / percentile; one with query edges but nothing to measure to gives inf / inf /
+ * nan.  Sums are reduced in a fixed order: two calls on the same input give the same bits.  ws holds
+ * unetr_surface_metrics_workspace_bytes(B, C, D, H, W, group, npct) bytes: 8 B per voxel of the batch plus, per slot, 17 B per
+ * voxel of one volume + 8752 B (+ 32 KiB with percentiles).  No host synchronisation.
+ * (Additions: no existing signature moved, UNETR_ABI_VERSION stays.) */
+size_t unetr_surface_metrics_workspace_bytes(int B, int C, int D, int H, int W, int group, int npct);
+int unetr_surface_metrics(const void* pred, const void* y, int B, int C, int D, int H, int W, int c0, int input_form,
+                          const double* spacing, const double* percentiles, int npct, const double* thresholds, double* out,
+                          void* ws, size_t ws_bytes, int group, void* stream);
 
 /* ---- ranking pre-training losses (unetr_ranking_pretraining_3d.py:59-133 triplet construction, :202-217 BTLoss,
  * :219-236 ContrastiveLoss), fused: feat is the NCDHW feature map [4, C, S1, S2, S3] (2 volumes x 2 transforms: enc4 in

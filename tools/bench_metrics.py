@@ -1,11 +1,13 @@
 """GPU time of the validation metrics HausdorffDistanceMetric and ConfusionMatrixMetric.
 
-    python tools/bench_metrics.py [--iters 20] [--no-cpu]
+    python tools/bench_metrics.py [--iters 20] [--no-cpu] [--spacing 5,0.8,0.8]
 
 Prints ONE JSON line: per case the median of --iters warmed calls timed with HIP events (each call ends in the metric's
 [B, C] result on the device), and, where scipy is importable, the wall time of the CPU restatement of MONAI 0.6.0
 (tests/metrics_ref.py::hd_monai_scipy) on the same inputs, run once.  Cases: [2,4,96,96,96] one-hot, and [1,14,256,256,160]
-from_logits on synthetic ellipsoid "organs" with a perturbed prediction.
+from_logits on synthetic ellipsoid "organs" with a perturbed prediction.  --spacing adds the millimetre path at the same shapes
+(one unetr_surface_metrics call each): the Hausdorff distance alone, HD + 3 percentiles + average surface distance + surface
+Dice in one call, the same from uint8 class ids, and scipy's `sampling=` restatement (tests/surface_ref.py) on the host.
 """
 import argparse
 import importlib
@@ -67,10 +69,46 @@ def time_gpu(fn, iters):
     return statistics.median(ts)
 
 
+SM_PERCENTILES = (50, 95, 100)
+
+
+def surface_rows(pkg, yp, yt, from_logits, logits, labels, C, spacing, iters, have_scipy):
+    """the --spacing rows of one case"""
+    taus = tuple(1.0 + 0.5 * (c % 3) for c in range(C))
+    kw = dict(spacing=spacing, include_background=True)
+    hd = pkg.HausdorffDistanceMetric(**kw)
+    everything = lambda a, b, **form: pkg.surface_metrics(a, b, percentiles=SM_PERCENTILES, thresholds=taus, **form, **kw)
+    ip, it = logits.argmax(1, keepdim=True).to(torch.uint8), labels.to(torch.uint8)
+    r = {"spacing": list(spacing),
+         "mm_hd_ms": time_gpu(lambda: hd(yp, yt, from_logits=from_logits), iters),
+         "mm_all_ms": time_gpu(lambda: everything(yp, yt, from_logits=from_logits), iters),
+         "mm_all_class_ids_ms": time_gpu(lambda: everything(ip, it, class_ids=C), iters)}
+    if have_scipy:
+        import surface_ref as S
+        got = everything(ip, it, class_ids=C)
+        pm, gm = ip[:, 0].cpu(), it[:, 0].cpu()
+        t0 = time.perf_counter()
+        recs = [S.record_ref(pm[b] == c, gm[b] == c, spacing, SM_PERCENTILES, taus[c]) for b in range(pm.shape[0]) for c in range(C)]
+        r["mm_all_cpu_scipy_s"] = time.perf_counter() - t0
+        worst = 0.0
+        for key, k in [("max_pg", None), ("max_gp", None), ("mean_pg", None), ("mean_gp", None)] + \
+                      [(f, k) for f in ("pct_pg", "pct_gp") for k in range(len(SM_PERCENTILES))]:
+            a = (getattr(got, key) if k is None else getattr(got, key)[k]).cpu().reshape(-1)
+            b = torch.tensor([x[key] if k is None else x[key][k] for x in recs], dtype=torch.float64)
+            worst = max(worst, float(((a - b).abs() / b.abs().clamp_min(1e-300)).max()))
+        r["mm_max_rel_diff_vs_cpu"] = worst
+        r["mm_counts_equal_cpu"] = all(
+            torch.equal(getattr(got, key).cpu().reshape(-1), torch.tensor([x[key] for x in recs], dtype=torch.float64))
+            for key in ("n_pred", "n_gt", "within_pg", "within_gp"))
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--no-cpu", action="store_true", help="skip the scipy restatement")
+    ap.add_argument("--spacing", type=lambda v: tuple(float(x) for x in v.split(",")), default=None,
+                    help="mm per step along D,H,W: also time the spacing-aware surface metrics")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_metrics: no GPU")
@@ -95,6 +133,8 @@ def main():
         r = {"hd_ms": time_gpu(lambda: hd(yp, yt, from_logits=from_logits), a.iters),
              "hd95_ms": time_gpu(lambda: hd95(yp, yt, from_logits=from_logits), a.iters),
              "confusion_ms": time_gpu(lambda: cm(yp, yt, from_logits=from_logits), a.iters)}
+        if a.spacing:
+            r.update(surface_rows(pkg, yp, yt, from_logits, logits, labels, C, a.spacing, a.iters, have_scipy))
         if have_scipy:
             import metrics_ref as R
             p1 = onehot(logits.argmax(1, keepdim=True), C).cpu()
