@@ -12,8 +12,10 @@ import weakref
 
 import torch
 
-from . import _capi
+from . import _capi, grad_arena
 from ._capi import GemmDesc, GemmBf16Desc, call, call_rc
+from .grad_arena import (ArenaState, _DEFAULT_STATE, _gout, _ret, clear_grad_sinks, flush_deferred,  # noqa: F401
+                         register_grad_sinks)
 
 LN_EPS = 1e-5
 IN_EPS = 1e-5
@@ -57,230 +59,39 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-# ---- gradient sinks: parameters registered here get their gradients written straight into a slice of one flat
-# arena (UNETR.use_flat_buffers), so AdamW is one launch and the data-parallel all-reduce needs no flatten copies.
-# Everything mutable about that fast path -- the sink table, the deferred weight-gradient queues, the readiness
-# callbacks of the data-parallel reducer -- belongs to ONE ArenaState per model (UNETR.use_flat_buffers creates it), so
-# several models in one process do not share a queue.  The module-level table only maps a parameter's storage address
-# to its owner; entries are validated against the live parameter (weak reference + address) on every lookup.
-class ArenaState:
-    def __init__(self):
-        self.sinks = {}            # data_ptr -> (weakref(param), arena view)
-        self.ready_cb = []         # data-parallel reducers: called with a parameter once its arena gradient is final
-        self.defer = {"wgrad": [], "wgrad_b": [], "colsum": [], "reduce": [], "params": [], "armed": False, "prec": 0}
-        self.unmaintained = 0      # arena shadows of THIS model re-derived since its flat optimizer last vouched for them
-        self.fuse = None           # optim.AdamW.begin_fused_step: the deferred weight-gradient launch applies AdamW itself
-
-    def reset_deferred(self):
-        """Drop whatever a backward pass that raised left queued (its end-of-pass callback never ran): without this the
-        queue stays armed, no later pass re-arms the flush, and AdamW steps on stale arena gradients."""
-        d = self.defer
-        d["wgrad"], d["wgrad_b"], d["colsum"], d["reduce"], d["params"], d["armed"] = [], [], [], [], [], False
-
-    def clear(self):
-        self.fuse = None
-        drop_wt_shadow(getattr(self, "flat", None))
-        for k in list(self.sinks):
-            _GRAD_SINK.pop(k, None)
-        self.sinks.clear()
-        self.reset_deferred()
-
-
-_DEFAULT_STATE = ArenaState()
-_GRAD_SINK = {}                    # data_ptr -> ArenaState owning that parameter
-
-
-def register_grad_sinks(params_and_views, state=None):
-    state = state if state is not None else _DEFAULT_STATE
-    for p, view in params_and_views:
-        state.sinks[p.data_ptr()] = (weakref.ref(p), view)
-        _GRAD_SINK[p.data_ptr()] = state
-    return state
-
-
-def clear_grad_sinks(state=None):
-    """forget the arena registrations (of one model's state, or of every model when called without one)"""
-    if state is not None:
-        state.clear()
-        return
-    for st in set(_GRAD_SINK.values()):
-        st.clear()
-    _DEFAULT_STATE.clear()
-    _GRAD_SINK.clear()
-
-
-def _sink(w):
-    """(state, param, view) when tensor `w` IS a registered, still-living parameter at its registered address"""
-    st = _GRAD_SINK.get(w.data_ptr())
-    if st is None:
-        return None
-    ent = st.sinks.get(w.data_ptr())
-    if ent is None:
-        return None
-    p = ent[0]()
-    if p is None or p.data_ptr() != w.data_ptr() or ent[1].shape != w.shape:
-        return None
-    return st, p, ent[1]
-
-
-def _gout(w):
-    """Destination for the gradient of parameter tensor `w`: its arena slice when registered and no gradient is
-    currently attached (accumulating into an existing .grad must not alias it), else None (fresh tensor)."""
-    ent = _sink(w)
-    if ent is None or ent[1].grad is not None:
-        return None
-    return ent[2]
-
-
-def _ret(w, g, deferred=False):
-    """What a Function.backward returns for parameter `w`: when `g` was (or, if deferred, will be) written into
-    w's arena slice, attach the slice as .grad directly (autograd would clone it: the arena keeps a second
-    reference) and return None.  Readiness callbacks (data-parallel buckets) fire now, or at flush if deferred."""
-    ent = _sink(w) if g is not None else None
-    if ent is not None and g.data_ptr() == ent[2].data_ptr():
-        st, p, view = ent
-        p.grad = view
-        if deferred:
-            st.defer["params"].append(p)
-        else:
-            for cb in st.ready_cb:
-                cb(p)
-        return None
-    return g
-
-
-# ---- deferred, grouped weight gradients -------------------------------------------------------------------
-# In arena mode the Linear weight/bias gradients of the ViT are not needed by anything inside backward, so they
-# are queued (per ArenaState) and executed at the end of the backward pass as ONE grouped GEMM launch + ONE grouped
-# column-sum launch (csrc: gemm_grouped_wgrad_kernel, colsum_grouped_kernel) instead of ~90 small latency-bound launches.
-def _arm_flush(st):
-    if not st.defer["armed"]:
-        st.defer["armed"] = True
-        torch.autograd.Variable._execution_engine.queue_callback(lambda: flush_deferred(st))
-
-
+# ---- arena gradients (grad_arena.py): where a parameter's gradient goes, and the work deferred to the end of backward ----
+# In arena mode the Linear weight / bias gradients of the ViT are not needed by anything inside backward, so they are queued on
+# the model's ArenaState and executed at the end of the backward pass as ONE grouped GEMM launch + ONE grouped column-sum launch
+# (csrc: gemm_grouped_wgrad_kernel, colsum_grouped_kernel) instead of ~90 small latency-bound launches.
 def wgrad_or_defer(dy, x, prec, w, dyb=None, xb=None):
     """dw[N,K] = dy^T x for Linear weight `w`; returns (grad_or_None_for_autograd).  dyb / xb: bf16 twins of dy / x -- the
     deferred launch then runs the bf16-storage grouped kernel (unetr_gemm_bf16_grouped_wgrad)."""
-    out = _gout(w)
+    st, out = grad_arena.dest(w)
     twins = dyb is not None and xb is not None and dyb.shape[0] % 8 == 0 and dyb.shape[1] % 8 == 0 and xb.shape[1] % 8 == 0
-    if out is None:
+    if st is None:
         if not twins:
             return linear_wgrad(dy, x, prec)
         dw = torch.empty(dyb.shape[1], xb.shape[1], dtype=torch.float32, device=dyb.device)
-        _launch_deferred((), (), [(dyb, xb, dw)])
+        grad_arena.launch_wgrad_bf16([(dyb, xb, dw)])
         return dw
-    st = _GRAD_SINK[w.data_ptr()]
     if twins:
-        st.defer["wgrad_b"].append((dyb, xb, out))
-        _arm_flush(st)
-        return _ret(w, out, deferred=True)
-    st.defer["wgrad"].append((dy, x, out))
-    st.defer["prec"] = prec
-    _arm_flush(st)
+        st.queue_wgrad_bf16(dyb, xb, out)
+    else:
+        st.queue_wgrad(dy, x, out, prec)
     return _ret(w, out, deferred=True)
 
 
 def colsum_or_defer(x, M, N, ld, b, view_shape=None):
-    out = _gout(b)
-    if out is None:
+    st, out = grad_arena.dest(b)
+    if st is None:
         if x.dtype == torch.bfloat16:          # (bf16 rows: the grouped kernel reads them; one problem, launched now)
             r = torch.empty(N, dtype=torch.float32, device=x.device)
-            _launch_deferred((), [(x, r, M, N, ld)])
+            grad_arena.launch_colsums([(x, r, M, N, ld)])
         else:
             r = colsum(x, M, N, ld)
         return r.view(view_shape) if view_shape is not None else r
-    st = _GRAD_SINK[b.data_ptr()]
-    st.defer["colsum"].append((x, out, M, N, ld))
-    _arm_flush(st)
+    st.queue_colsum(x, out, M, N, ld)
     return _ret(b, out, deferred=True)
-
-
-def _launch_reduces(rq):
-    """every queued weight-gradient reduction (dst[i] = sum over rows of part[row][i]) in ONE launch"""
-    arr = (_capi.ReduceProblem * len(rq))()
-    for i, (part, dst, n, rows) in enumerate(rq):
-        arr[i].part, arr[i].dst, arr[i].n, arr[i].rows = part.data_ptr(), dst.data_ptr(), n, rows
-    call("unetr_reduce_rows_grouped", arr, len(rq), _stream())
-
-
-def _launch_deferred(wq, cq, wbq=(), prec=0, fuse=None):
-    if wbq and fuse is not None:
-        # the optimizer rides on the launch: problems whose destination is a registered arena slice get AdamW in the epilogue
-        # (their gradient is never stored); anything else keeps the plain launch below
-        index = fuse["index"]
-        fused = [(q, index[q[2].data_ptr()]) for q in wbq if q[2].data_ptr() in index]
-        wbq = [q for q in wbq if q[2].data_ptr() not in index]
-        if fused:
-            arr = (_capi.GroupedProblem * len(fused))()
-            idx = (ctypes.c_int * len(fused))()
-            for i, ((dyb, xb, out), pi) in enumerate(fused):
-                arr[i].dy, arr[i].x, arr[i].dw = dyb.data_ptr(), xb.data_ptr(), out.data_ptr()
-                arr[i].M, arr[i].N, arr[i].K = dyb.shape[0], dyb.shape[1], xb.shape[1]
-                idx[i] = pi
-            if fuse.get("kind") == "bf16out":      # data-parallel step, bf16 communication: bf16(dW) straight into the comm buffer
-                call("unetr_gemm_bf16_grouped_wgrad_bf16out", arr, len(fused), fuse["grad"], fuse["out"], fuse["total"], _stream())
-            else:
-                # (the transposed twins of the weights, if this model keeps them, are written by the same epilogue)
-                wt = fuse["flat"].get("shadow_t") if wt_enabled() and fuse.get("flat") is not None else None
-                call("unetr_gemm_bf16_grouped_wgrad_adamw_t", arr, len(fused), ctypes.byref(fuse["arena"]), idx,
-                     wt.data_ptr() if wt is not None else None, _stream())
-                if wt is not None:
-                    fuse["wt_done"].extend(pi for _, pi in fused)
-            fuse["done"].extend(pi for _, pi in fused)
-    if wbq:
-        arr = (_capi.GroupedProblem * len(wbq))()
-        for i, (dyb, xb, out) in enumerate(wbq):
-            arr[i].dy, arr[i].x, arr[i].dw = dyb.data_ptr(), xb.data_ptr(), out.data_ptr()
-            arr[i].M, arr[i].N, arr[i].K = dyb.shape[0], dyb.shape[1], xb.shape[1]
-        call("unetr_gemm_bf16_grouped_wgrad", arr, len(wbq), _stream())
-    if wq and prec == _capi.PREC_BF16X3:
-        # bf16x3: dW = dY^T X over (hi, lo) halves is the bf16 kernel's contraction over three times the rows of the stacks
-        # [dYh; dYh; dYl] / [Xh; Xl; Xh] (two streaming split launches per problem) -- the generic fp32-storage grouped kernel spends
-        # 2.2 ms per step on these 76 GF, the bf16 kernel 0.2 ms per 432 rows; with an optimizer epilogue armed it rides here too
-        rest, stacked, splits = [], [], []
-        for dy, x, out in wq:
-            M, N, K = dy.shape[0], dy.shape[1], x.shape[1]
-            if (M * N) % 8 or (M * K) % 8 or (3 * M) % 8 or N % 8 or K % 8 or not dy.is_contiguous() or not x.is_contiguous():
-                rest.append((dy, x, out))
-                continue
-            dys = torch.empty(3 * M, N, dtype=torch.bfloat16, device=dy.device)
-            xs = torch.empty(3 * M, K, dtype=torch.bfloat16, device=dy.device)
-            splits += [(dy, dys, M, N, 0), (x, xs, M, K, 1)]
-            stacked.append((dys, xs, out))
-        wq = rest
-        if stacked:
-            arr = (_capi.SplitProblem * len(splits))()
-            for i, (src, dst, rows, cols, second) in enumerate(splits):
-                arr[i].src, arr[i].dst, arr[i].rows, arr[i].cols, arr[i].second = src.data_ptr(), dst.data_ptr(), rows, cols, second
-            call("unetr_split_stack_bf16_grouped", arr, len(splits), _stream())          # every stack of the pass in one launch
-            _launch_deferred((), (), stacked, prec, fuse)
-    if wq:
-        arr = (_capi.GroupedProblem * len(wq))()
-        for i, (dy, x, out) in enumerate(wq):
-            arr[i].dy, arr[i].x, arr[i].dw = dy.data_ptr(), x.data_ptr(), out.data_ptr()
-            arr[i].M, arr[i].N, arr[i].K = dy.shape[0], dy.shape[1], x.shape[1]
-        call("unetr_gemm_grouped_wgrad", arr, len(wq), prec, _stream())
-    if cq:
-        arr = (_capi.ColsumProblem * len(cq))()
-        for i, (x, out, M, N, ld) in enumerate(cq):
-            arr[i].x, arr[i].out, arr[i].ld, arr[i].M, arr[i].N = x.data_ptr(), out.data_ptr(), ld, M, N
-            arr[i].x_bf16 = int(x.dtype == torch.bfloat16)
-        call("unetr_colsum_grouped", arr, len(cq), _stream())
-
-
-def flush_deferred(st=None):
-    """Runs at the end of the backward pass (autograd engine callback) on the backward stream."""
-    st = st if st is not None else _DEFAULT_STATE
-    d = st.defer
-    wq, cq, wbq, params, prec, rq = d["wgrad"], d["colsum"], d["wgrad_b"], d["params"], d["prec"], d["reduce"]
-    st.reset_deferred()
-    if rq:
-        _launch_reduces(rq)
-    _launch_deferred(wq, cq, wbq, prec, st.fuse)
-    for p in params:
-        for cb in st.ready_cb:
-            cb(p)
 
 
 def act_dtype(prec):
@@ -412,7 +223,7 @@ def mark_flat_maintained(params, state=None):
     of these parameters is in step again.  Only walks the table after something of THIS model had to be re-derived: the
     count lives in the model's ArenaState (a process-wide one let model A's step clear what model B still had to redo)."""
     if state is None and params:
-        state = _GRAD_SINK.get(params[0].data_ptr())
+        state = grad_arena.owner(params[0])
     if state is not None and not state.unmaintained:
         return
     for w in params:
@@ -519,8 +330,8 @@ def weight_x3(w):
     """the weight as split words (int32 view, same shape) when `w` lives in a flat arena; else None (the kernel splits the fp32 weight)"""
     if not x3_words_enabled():
         return None
-    st = _GRAD_SINK.get(w.data_ptr())
-    flat = getattr(st, "flat", None) if st is not None else None
+    st = grad_arena.owner(w)
+    flat = st.flat if st is not None else None
     if flat is None:
         return None
     if flat.get("shadow_x3") is None:
@@ -583,6 +394,14 @@ def wt_enabled():
     return os.environ.get("UNETR_AMD_WT", "1") != "0"
 
 
+def _epilogue_twin_arena(flat):
+    """the twin arena of a model for the fused weight-gradient + AdamW launch to write, or None"""
+    return flat.get("shadow_t") if wt_enabled() and flat is not None else None
+
+
+grad_arena._stream, grad_arena._drop_twins, grad_arena._twin_arena = _stream, drop_wt_shadow, _epilogue_twin_arena
+
+
 def _wt_current(ent, w):
     return ent is not None and ent[2]() is not None and ent[1] == w._version and ent[3] == w.data_ptr()
 
@@ -617,8 +436,8 @@ def weight_bf16_t(w):
     any other captured step would leave it behind from the second replay on."""
     if not wt_enabled() or w.dim() != 2 or w.shape[0] % 8 or w.shape[1] % 8:
         return None
-    st = _GRAD_SINK.get(w.data_ptr())
-    flat = getattr(st, "flat", None) if st is not None else None
+    st = grad_arena.owner(w)
+    flat = st.flat if st is not None else None
     if flat is None or flat.get("shadow") is None:
         return None
     capturing = torch.cuda.is_current_stream_capturing()
@@ -699,7 +518,7 @@ def weight_bf16(w):
         # re-derived here = somebody other than this package's optimizer changed the weight (or may have): the copy is no
         # longer optimizer-maintained until that optimizer steps again (shadow_ptr_for_update / mark_flat_maintained)
         ent[1], ent[2], ent[5], ent[3] = w._version, _WEIGHT_EPOCH[0], w.data_ptr(), False
-        st = _GRAD_SINK.get(w.data_ptr())
+        st = grad_arena.owner(w)
         if st is not None:
             st.unmaintained += 1
     return ent[0]
@@ -785,7 +604,7 @@ def _prefetch(host, *weights, dgrad=0):
     pf, n = _capi.Prefetch(), 0
     for w in weights:
         if dgrad and w is not None and wt_enabled() and dgrad <= WT_MAX_ROWS:
-            st = _GRAD_SINK.get(w.data_ptr())
+            st = grad_arena.owner(w)
             tw = _SHADOW_T_AT.get(w.data_ptr())
             if (tw is not None and _wt_current(tw, w) and tw[0].device == w.device and tw[0].numel() == w.numel()
                     and (_keeps_twin(st) or not torch.cuda.is_current_stream_capturing())):
@@ -921,36 +740,44 @@ def layernorm_fwd(x, w, b, bf16_out=None, want_fp32=True, pf=None):
     return y, mean, rstd
 
 
-def layernorm_bwd(dy, x, w, mean, rstd, dres=None, out_w=None, out_b=None, dx_bf16=None, pf=None):
+def layernorm_bwd(dy, x, w, mean, rstd, dres=None, out_w=None, out_b=None, dx_bf16=None, pf=None, part=None):
+    """part: a private buffer [ceil(M / 4), 2H] -- the kernel leaves its dgamma | dbeta partials per row block there and writes no
+    dw / db (returned as None); without it the partials go through the workspace and are reduced into dw / db"""
     M, H = x.shape
     dx = torch.empty_like(x)
-    dw = out_w if out_w is not None else torch.empty(H, dtype=torch.float32, device=x.device)
-    db = out_b if out_b is not None else torch.empty(H, dtype=torch.float32, device=x.device)
-    ws = workspace(x.device)
+    dw = db = None
+    if part is None:
+        dw = out_w if out_w is not None else torch.empty(H, dtype=torch.float32, device=x.device)
+        db = out_b if out_b is not None else torch.empty(H, dtype=torch.float32, device=x.device)
+    buf = part if part is not None else workspace(x.device)
     call("unetr_layernorm_bwd_pf", dy.data_ptr(), x.data_ptr(), w.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
-         _p(dx_bf16), dres.data_ptr() if dres is not None else None, dw.data_ptr(), db.data_ptr(), M, H, ws.data_ptr(), ws.numel() * 4, _stream(), pf)
+         _p(dx_bf16), _p(dres), _p(dw), _p(db), M, H, buf.data_ptr(), buf.numel() * 4, _stream(), pf)
     return dx, dw, db
 
 
-def layernorm_bwd_params(dy, x, w, b, mean, rstd, dres=None, dx_bf16=None, pf=None):
-    """LayerNorm backward returning (dx, grad_w, grad_b) as autograd wants them.  In arena mode the dgamma/dbeta
-    reduction over row blocks is not needed inside backward: the kernel leaves its partials in a private buffer and the
-    two column sums join the grouped launch at the end of the pass (one launch for all 25 LayerNorms)."""
-    ow, ob = _gout(w), _gout(b)
-    if ow is None or ob is None:
-        dx, dw, db = layernorm_bwd(dy, x, w, mean, rstd, dres=dres, out_w=ow, out_b=ob, dx_bf16=dx_bf16, pf=pf)
-        return dx, _ret(w, dw), _ret(b, db)
-    M, H = x.shape
+def _ln_param_grads(w, b, M, H, device, kernel):
+    """What the two LayerNorm backward forms share: (dx, grad_w, grad_b) as autograd wants them from ``kernel(dw, db, part) -> dx``.
+    In arena mode the dgamma/dbeta reduction over row blocks is not needed inside backward: the kernel is handed a private buffer
+    `part` for its partials (and no dw / db) and the two column sums over the halves of that buffer join the grouped launch at the
+    end of the pass (one launch for all 25 LayerNorms).  Otherwise it reduces into dw / db itself (part is None)."""
+    st, (ow, ob) = grad_arena.dests(w, b)
+    if st is None:
+        dw = ow if ow is not None else torch.empty(H, dtype=torch.float32, device=device)
+        db = ob if ob is not None else torch.empty(H, dtype=torch.float32, device=device)
+        return kernel(dw, db, None), _ret(w, dw), _ret(b, db)
     nblk = (M + 3) // 4
-    part = torch.empty(nblk * 2 * H, dtype=torch.float32, device=x.device)
-    dx = torch.empty_like(x)
-    call("unetr_layernorm_bwd_pf", dy.data_ptr(), x.data_ptr(), w.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
-         _p(dx_bf16), _p(dres), None, None, M, H, part.data_ptr(), part.numel() * 4, _stream(), pf)
-    st = _GRAD_SINK[w.data_ptr()]
-    st.defer["colsum"].append((part, ow, nblk, H, 2 * H))
-    st.defer["colsum"].append((part[H:], ob, nblk, H, 2 * H))
-    _arm_flush(st)
+    part = torch.empty(nblk * 2 * H, dtype=torch.float32, device=device)
+    dx = kernel(None, None, part)
+    st.queue_colsum(part, ow, nblk, H, 2 * H)
+    st.queue_colsum(part[H:], ob, nblk, H, 2 * H)
     return dx, _ret(w, ow, deferred=True), _ret(b, ob, deferred=True)
+
+
+def layernorm_bwd_params(dy, x, w, b, mean, rstd, dres=None, dx_bf16=None, pf=None):
+    """LayerNorm backward returning (dx, grad_w, grad_b) as autograd wants them"""
+    M, H = x.shape
+    return _ln_param_grads(w, b, M, H, x.device, lambda dw, db, part: layernorm_bwd(
+        dy, x, w, mean, rstd, dres=dres, out_w=dw, out_b=db, dx_bf16=dx_bf16, pf=pf, part=part)[0])
 
 
 def x3_ride_ok(M, N, K):
@@ -1021,25 +848,14 @@ def gemm_ln_bwd_params(A, Bw, M, N, K, x, w, b, mean, rstd, dres=None, dx_bf16=N
     scratch = torch.empty(M, N, dtype=torch.float32, device=x.device)
     dx = torch.empty_like(x)
     ws = workspace(x.device)
-    ow, ob = _gout(w), _gout(b)
-    nblk = (M + 3) // 4
-    if ow is None or ob is None:
-        dw = ow if ow is not None else torch.empty(N, dtype=torch.float32, device=x.device)
-        db = ob if ob is not None else torch.empty(N, dtype=torch.float32, device=x.device)
-        lnws = torch.empty(nblk * 2 * N, dtype=torch.float32, device=x.device)
+
+    def kernel(dw, db, part):
+        lnws = part if part is not None else torch.empty((M + 3) // 4 * 2 * N, dtype=torch.float32, device=x.device)
         call("unetr_gemm_bf16_ln_bwd_pf", ctypes.byref(d), A.data_ptr(), Bw.data_ptr(), scratch.data_ptr(), x.data_ptr(), w.data_ptr(),
-             mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(), _p(dx_bf16), _p(dres), dw.data_ptr(), db.data_ptr(),
+             mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(), _p(dx_bf16), _p(dres), _p(dw), _p(db),
              lnws.data_ptr(), lnws.numel() * 4, ws.data_ptr(), ws.numel() * 4, _stream(), pf)
-        return dx, _ret(w, dw), _ret(b, db)
-    part = torch.empty(nblk * 2 * N, dtype=torch.float32, device=x.device)
-    call("unetr_gemm_bf16_ln_bwd_pf", ctypes.byref(d), A.data_ptr(), Bw.data_ptr(), scratch.data_ptr(), x.data_ptr(), w.data_ptr(),
-         mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(), _p(dx_bf16), _p(dres), None, None,
-         part.data_ptr(), part.numel() * 4, ws.data_ptr(), ws.numel() * 4, _stream(), pf)
-    st = _GRAD_SINK[w.data_ptr()]
-    st.defer["colsum"].append((part, ow, nblk, N, 2 * N))
-    st.defer["colsum"].append((part[N:], ob, nblk, N, 2 * N))
-    _arm_flush(st)
-    return dx, _ret(w, ow, deferred=True), _ret(b, ob, deferred=True)
+        return dx
+    return _ln_param_grads(w, b, M, N, x.device, kernel)
 
 
 def attention_fwd(qkv, B, L, heads, dh, prec, out_bf16=None):
@@ -1278,17 +1094,19 @@ def conv3_dgrad_fused(dc1, dc3, w1, w3, dx, dims, prec):
     return rc == 0
 
 
-def conv3_wgrad(x, ldx, dy, lddy, dims, cin, cout, prec, out=None, dy3=None, out3=None, defer=None):
-    """dw of the 3x3x3 conv; with dy3/out3 also the weight gradient of the 1x1x1 conv sharing the input x.
-    defer = the ArenaState owning `out` (and `out3`): returns (dw, True) when the reduction of the partial sums was queued for the
-    end-of-backward grouped launch; plain calls return dw."""
-    want = defer is not None                 # such callers get (dw, queued)
+def conv3_wgrad(x, ldx, dy, lddy, dims, cin, cout, prec, out=None, dy3=None, out3=None):
+    """dw of the 3x3x3 conv; with dy3/out3 also the weight gradient of the 1x1x1 conv sharing the input x"""
+    return _conv3_wgrad_queued(None, x, ldx, dy, lddy, dims, cin, cout, prec, out, dy3, out3)[0]
+
+
+def _conv3_wgrad_queued(st, x, ldx, dy, lddy, dims, cin, cout, prec, out=None, dy3=None, out3=None):
+    """conv3_wgrad for a block's backward: (dw, queued).  st = the ArenaState owning `out` (and `out3`), or None.  With a state the
+    kernel leaves its per-workgroup partial sums in a buffer of its own and the reduction joins the ONE grouped reduce launch at
+    the end of the backward pass (queued = True) -- where the shape allows; otherwise dw is complete on return (queued = False)."""
     B, D, H, W = dims
     dw = out if out is not None else torch.empty(cout, cin, 3, 3, 3, dtype=torch.float32, device=x.device)
     x_f32 = int(prec == _capi.PREC_BF16 and x.dtype == torch.float32)
-    if defer is not None:
-        # arena mode: the kernel leaves its per-workgroup partial sums in a buffer of its own and the reduction joins the ONE grouped
-        # reduce launch at the end of the backward pass (functional.flush_deferred)
+    if st is not None:
         rows = _capi.load().unetr_conv3_wgrad_rows(B, D, H, W, cin, cout, prec, x_f32, int(dy3 is not None))
         n, n3 = 27 * cin * cout, (cin * cout if dy3 is not None else 0)
         if rows > 0 and rows * (n + n3) * 4 <= (256 << 20):
@@ -1298,16 +1116,14 @@ def conv3_wgrad(x, ldx, dy, lddy, dims, cin, cout, prec, out=None, dy3=None, out
                          ctypes.byref(got), B, D, H, W, cin, cout, prec, x_f32, _stream())
             if rc == 0:
                 g = got.value
-                defer.defer["reduce"].append((part, dw, n, g))
+                st.queue_reduce(part, dw, n, g)
                 if dy3 is not None:
-                    defer.defer["reduce"].append((part[g * n:], out3, n3, g))
-                _arm_flush(defer)
+                    st.queue_reduce(part[g * n:], out3, n3, g)
                 return dw, True
     ws = workspace(x.device)
-    call("unetr_conv3_wgrad", x.data_ptr(), ldx, dy.data_ptr(), lddy, dw.data_ptr(),
-         dy3.data_ptr() if dy3 is not None else None, cout, out3.data_ptr() if out3 is not None else None,
+    call("unetr_conv3_wgrad", x.data_ptr(), ldx, dy.data_ptr(), lddy, dw.data_ptr(), _p(dy3), cout, _p(out3),
          B, D, H, W, cin, cout, prec, x_f32, ws.data_ptr(), ws.numel() * 4, _stream())
-    return (dw, False) if want else dw
+    return dw, False
 
 
 def conv_pack(w, mode):
@@ -1454,8 +1270,7 @@ def tconv_bwd(x, ldx, xb, dy, lddy, w, dims, cin, cout, prec, need_dx):
     if prec == _capi.PREC_BF16 and dy.dtype != torch.bfloat16:
         dy = dy.to(torch.bfloat16).contiguous(); lddy = cout
     dx = tconv_dgrad(dy, lddy, w, dims, cin, cout, prec) if need_dx else None
-    gw = _gout(w)
-    st = _GRAD_SINK.get(w.data_ptr()) if gw is not None else None
+    st, gw = grad_arena.dest(w)
     if st is not None:
         # arena mode: the partial sums of the weight gradient stay in a buffer of their own; their reduction joins the grouped launch
         # at the end of the backward pass
@@ -1466,8 +1281,7 @@ def tconv_bwd(x, ldx, xb, dy, lddy, w, dims, cin, cout, prec, need_dx):
             got = ctypes.c_long(0)
             if call_rc("unetr_tconv2_wgrad_parts", x.data_ptr(), ldx, dy.data_ptr(), lddy, part.data_ptr(), part.numel() * 4, ctypes.byref(got),
                        B, D, H, W, cin, cout, prec, _stream()) == 0:
-                st.defer["reduce"].append((part, gw, n, got.value))
-                _arm_flush(st)
+                st.queue_reduce(part, gw, n, got.value)
                 return dx, _ret(w, gw, deferred=True)
     dw = tconv_wgrad(x, ldx, dy, lddy, dims, cin, cout, prec, out=gw)
     return dx, _ret(w, dw)
@@ -1911,20 +1725,12 @@ def _resblock_bwd(dout, x, ldx, dims, cin, cout, w1, w2, w3, saved, prec, need_d
         dc2, dc3 = img3[0], None
     else:
         dc2, dc3 = instnorm_bwd(dout, lddo, c2, s2, B, V, cout, True, x2=c3, sb=s3)
-    # conv3 (1x1x1)
-    g3 = _gout(w3)
-    dw3 = g3 if g3 is not None else torch.empty(cout, cin, 1, 1, 1, dtype=torch.float32, device=x.device)
     # arena mode: the three weight gradients' partial-sum reductions join the grouped launch at the end of the backward pass
-    g1, g2 = _gout(w1), _gout(w2)
-    st = _GRAD_SINK.get(w1.data_ptr()) if (g1 is not None and g2 is not None and g3 is not None) else None
-    if st is not None and (_GRAD_SINK.get(w2.data_ptr()) is not st or _GRAD_SINK.get(w3.data_ptr()) is not st):
-        st = None
-    q1 = q2 = False
+    st, (g1, g2, g3) = grad_arena.dests(w1, w2, w3)
+    # conv3 (1x1x1)
+    dw3 = g3 if g3 is not None else torch.empty(cout, cin, 1, 1, 1, dtype=torch.float32, device=x.device)
     # conv2
-    if st is not None:
-        dw2, q2 = conv3_wgrad(a1, cout, dc2, cout, dims, cout, cout, prec, out=g2, defer=st)
-    else:
-        dw2 = conv3_wgrad(a1, cout, dc2, cout, dims, cout, cout, prec, out=g2)
+    dw2, q2 = _conv3_wgrad_queued(st, a1, cout, dc2, cout, dims, cout, cout, prec, out=g2)
     dc1 = None
     if in_fuse_level() & 2:
         # the backward sums of the first norm come out of the data-gradient conv's epilogue: no reduction pass over (da1, c1)
@@ -1935,17 +1741,13 @@ def _resblock_bwd(dout, x, ldx, dims, cin, cout, w1, w2, w3, saved, prec, need_d
     if dc1 is None:
         da1 = conv3(dc2, cout, w2, dims, prec, mode=1)
         dc1, _ = instnorm_bwd(da1, cout, c1, s1, B, V, cout, True)
-    o3 = dw3 if dc3 is not None else None
-    if st is not None:
-        dw1, q1 = conv3_wgrad(x, ldx, dc1, cout, dims, cin, cout, prec, out=g1, dy3=dc3, out3=o3, defer=st)
-    else:
-        dw1 = conv3_wgrad(x, ldx, dc1, cout, dims, cin, cout, prec, out=g1, dy3=dc3, out3=o3)
+    dw1, q1 = _conv3_wgrad_queued(st, x, ldx, dc1, cout, dims, cin, cout, prec, out=g1, dy3=dc3, out3=dw3 if dc3 is not None else None)
     if img3 is not None:
-        rq = [(img3[1], dw3, cout * cin, img3[2])]
-        if st is not None and q1:
-            st.defer["reduce"].append(rq[0])           # joins the grouped reduce at the end of the backward pass (armed by conv3_wgrad)
+        rq = (img3[1], dw3, cout * cin, img3[2])
+        if q1:
+            st.queue_reduce(*rq)           # joins the grouped reduce at the end of the backward pass
         else:
-            _launch_reduces(rq)
+            grad_arena.launch_reduces([rq])
     dx = None
     if need_dx:
         dx = torch.empty(B, D, H, W, cin, dtype=act_dtype(prec), device=x.device)

@@ -108,7 +108,7 @@ def _flat_worker(rank, world, port, q):
         v0 = Fn._gout(params[0])
         assert Fn._ret(params[0], v0, deferred=True) is None
         v0.fill_(float(rank + 1))              # the deferred kernel "runs" here
-        Fn._DEFAULT_STATE.defer["armed"] = True
+        Fn._DEFAULT_STATE.deferred.armed = True
         Fn.flush_deferred()
         red.finish()
         for i in (4, 2, 1, 0):

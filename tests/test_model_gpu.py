@@ -258,7 +258,7 @@ def test_flat_buffers_match_per_tensor_path(pkg, dev):
 
 def test_bf16x3_flat_arena_weight_gradients(pkg, dev):
     """bf16x3 mode with the flat arenas: the ViT weight gradients run on the bf16 grouped kernel over (hi, lo) row stacks
-    (functional._launch_deferred) -- same gradients as the per-tensor path's generic split-operand GEMM, to rounding"""
+    (grad_arena.launch_wgrad_x3) -- same gradients as the per-tensor path's generic split-operand GEMM, to rounding"""
     from oracle.unetr_oracle import synthetic_volume
     torch.manual_seed(3)
     a = pkg.UNETRLogits(**C1).to(dev)
@@ -926,7 +926,7 @@ def test_two_models_and_failed_backward(pkg, dev):
     with pytest.raises(RuntimeError, match="boom"):
         torch.autograd.backward([r for r, _ in stages[0]], [l.grad for _, l in stages[0]])
     st = fa["state"]
-    assert st.defer["armed"] and len(st.defer["wgrad_b"]) + len(st.defer["wgrad"]) >= 8       # blocks 11 and 10 were queued
+    assert st.deferred.armed and len(st.deferred.wgrad_bf16) + len(st.deferred.wgrad) >= 8       # blocks 11 and 10 were queued
     del stages, logits, hs9
     a.zero_grad(set_to_none=True)
     fa["grad"].zero_()
