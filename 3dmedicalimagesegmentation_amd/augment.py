@@ -9,16 +9,23 @@ model's static input tensors with no host synchronisation, so one call can be re
 
 Kernels: csrc/augment.hip.  Semantics (MONAI 0.6.0) and the random-number assignment: DESIGN.md section 12 and
 tests/augment_ref.py, which replays the params table of every call bit for bit on the CPU.  No CPU fallback.
+
+``affine_prob > 0`` adds a random rotation and zoom per sample, taken at crop time from the whole cached volume in the same
+single gather (trilinear image, nearest label, border padding); its semantics are this project's own (RandCropAugment's
+docstring, DESIGN.md section 12, tests/augment_affine_ref.py).
 """
 import ctypes
+import math
 from typing import Optional, Sequence, Tuple, Union
 
 import torch
 
 from . import functional as Fn
 from . import preprocess
-from ._capi import AugDesc, call, load
+from ._capi import AugAffineDesc, AugDesc, call, load
 
+AFFINE_COLS = 16        # affine row (float32): flag, angle about spatial axis 0, 1, 2, zoom of axis 0, 1, 2, M [3][3] row-major
+_MAXDIM_AFFINE = 1 << 24  # volume extent up to which a float32 coordinate still names every voxel
 PARAM_COLS = 8          # params row: volume, corner z, y, x, flip mask (bit a = spatial axis a), k, shift flag, offset (float bits)
 _VCOLS = 12             # device volume table row: img ptr, lbl ptr, fg ptr, nfg, bg ptr, nbg, C, L, D, H, W, 0
 _MAXC = 8
@@ -178,13 +185,28 @@ class RandCropAugment:
     """One training batch per call: B // num_samples volumes from the schedule, num_samples crops of each (item-major, MONAI's
     list collate order), each followed by RandFlipd per axis, RandRotate90d, RandShiftIntensityd and optionally
     NormalizeIntensityd(nonzero=True, channel_wise=True).  ``aug(x, y)`` writes x [B, C, *S] and y [B, L, *S] (float32) and
-    ``aug.params`` [B, 8] (int32) records what it drew.  Launches only, on the current stream; graph-capturable."""
+    ``aug.params`` [B, 8] (int32) records what it drew.  Launches only, on the current stream; graph-capturable.
+
+    ``affine_prob > 0`` takes each sample, with that probability, through a random rotation (``rotate_range``: one value or
+    three, radians; the angle about spatial axis a is uniform in [-r_a, r_a]) and zoom (``zoom_range`` = (lo, hi), uniform; z > 1
+    makes structures z times larger; ``zoom_per_axis`` draws one zoom per axis) and records it in ``aug.affine`` [B, 16]
+    (float32: flag, 3 angles, 3 zooms, M row-major).  An output voxel goes back through rot90^k and the flips to crop position
+    p as before; then, with c0 the crop corner and q = p - (S - 1) / 2, it reads the volume at
+    ``c0 + (S - 1) / 2 + M q``,  ``M = R0(t0) R1(t1) R2(t2) diag(1 / z)``  (R2 turns (q0, q1); R0, R1 cyclically),
+    trilinear for the image, nearest (floor(src + 0.5)) for the label.  The position is looked up in the whole cached volume, so
+    real anatomy beside the crop comes into view; taps outside the volume take the nearest voxel (border padding).  Per sample:
+    affine at crop time, flips, rot90, shift, normalize.  The crop corner is drawn as without the affine: the crop box lies in
+    the volume, its warped footprint need not.  This is NOT bit parity with MONAI's RandAffined: that one warps the already
+    cropped patch (so it pads where this reads the neighbouring anatomy), pads by reflection by default and orders and
+    parametrises its matrix differently.  Unflagged samples are bit-identical to what ``affine_prob=0`` writes."""
 
     def __init__(self, cache: VolumeCache, spatial_size: Union[int, Sequence[int]] = 96, num_samples: int = 4, pos: float = 1,
                  neg: float = 1, sampling: str = "pos_neg", flip_prob: Union[float, Sequence[float], None] = (0.1, 0.1, 0.1),
                  rot90_prob: float = 0.1, max_k: int = 3, spatial_axes: Tuple[int, int] = (0, 1),
                  shift_offsets: Union[float, Sequence[float]] = 0.1, shift_prob: float = 0.5, normalize: Optional[str] = None,
-                 seed: int = 0, batch_size: Optional[int] = None, order_capacity: Optional[int] = None):
+                 seed: int = 0, batch_size: Optional[int] = None, order_capacity: Optional[int] = None,
+                 affine_prob: float = 0.0, rotate_range: Union[float, Sequence[float], None] = None,
+                 zoom_range: Optional[Sequence[float]] = None, zoom_per_axis: bool = False):
         S = tuple(int(s) for s in _triple(spatial_size, "spatial_size"))
         if any(not 0 < s <= _MAXS for s in S):
             raise ValueError(f"spatial_size must be in 1..{_MAXS} per axis, got {S}")
@@ -217,6 +239,18 @@ class RandCropAugment:
                 raise ValueError(f"shift_offsets: low > high ({lo} > {hi})")
         if not 0 <= int(seed) < 2 ** 64:
             raise ValueError("seed must be in [0, 2**64)")
+        if not 0.0 <= float(affine_prob) <= 1.0:
+            raise ValueError(f"affine_prob must be in [0, 1], got {affine_prob}")
+        if float(affine_prob) > 0 and rotate_range is None and zoom_range is None:
+            raise ValueError("affine_prob > 0 needs rotate_range or zoom_range")
+        rot = (0.0, 0.0, 0.0) if rotate_range is None else tuple(float(r) for r in _triple(rotate_range, "rotate_range"))
+        if any(not (math.isfinite(r) and r >= 0) for r in rot):
+            raise ValueError(f"rotate_range must be finite and nonnegative, got {rotate_range!r}")
+        zlo, zhi = (1.0, 1.0) if zoom_range is None else (float(v) for v in zoom_range)
+        if not (math.isfinite(zlo) and math.isfinite(zhi) and zlo > 0 and zhi > 0):
+            raise ValueError(f"zoom_range: positive finite bounds expected, got {zoom_range!r}")
+        if zlo > zhi:
+            raise ValueError(f"zoom_range: low > high ({zlo} > {zhi})")
         shapes = list(cache.shapes)
         if not shapes:
             raise ValueError("the VolumeCache holds no volume")
@@ -226,6 +260,8 @@ class RandCropAugment:
                 raise ValueError(f"volume {i} has {c} image / {l} label channels, volume 0 has {C} / {L}")
             if any(d < s for d, s in zip(dims, S)):
                 raise ValueError(f"volume {i} of spatial shape {tuple(dims)} is smaller than the crop {S}")
+            if float(affine_prob) > 0 and any(d > _MAXDIM_AFFINE for d in dims):
+                raise ValueError(f"volume {i} of spatial shape {tuple(dims)}: the affine gather supports extents up to 2**24")
         n = len(shapes)
         cap = max(n, 4096) if order_capacity is None else int(order_capacity)
         if cap < n:
@@ -237,6 +273,7 @@ class RandCropAugment:
         self.flip_prob, self.rot90_prob, self.max_k, self.spatial_axes = fp, float(rot90_prob), int(max_k), ax
         self.shift_range, self.shift_prob, self.normalize, self.seed = (lo, hi), float(shift_prob), normalize, int(seed)
         self.channels, self.label_channels, self.num_volumes = C, L, n
+        self.affine_prob, self.rotate_range, self.zoom_range, self.zoom_per_axis = float(affine_prob), rot, (zlo, zhi), bool(zoom_per_axis)
 
         d = AugDesc()
         d.B, d.num_samples, d.C, d.L = B, self.num_samples, C, L
@@ -257,7 +294,17 @@ class RandCropAugment:
         self._order[:n] = torch.arange(n, dtype=torch.int32, device=dev)
         self._state = torch.tensor([0, 0, n, 0], dtype=torch.int64, device=dev)
         self.params = torch.zeros(B, PARAM_COLS, dtype=torch.int32, device=dev)
+        self.affine = None                     # [B, 16] float32 once affine_prob > 0
+        self._adesc = None
         ws = load().unetr_aug_gather_ws_bytes(ctypes.byref(d))
+        if self.affine_prob > 0:
+            a = AugAffineDesc()
+            a.prob, a.zoom_lo, a.zoom_hi, a.zoom_per_axis = self.affine_prob, zlo, zhi, int(self.zoom_per_axis)
+            a.rotate[0], a.rotate[1], a.rotate[2] = rot
+            self._adesc = a
+            self.affine = torch.zeros(B, AFFINE_COLS, dtype=torch.float32, device=dev)
+            self.affine[:, [4, 5, 6, 7, 11, 15]] = 1.0
+            ws = load().unetr_aug_gather_affine_ws_bytes(ctypes.byref(d))
         self._ws = torch.empty(max(ws, 8), dtype=torch.uint8, device=dev)
 
     # ---------------------------------------------------------------- schedule
@@ -302,14 +349,33 @@ class RandCropAugment:
         self._check_out(x, y)
         st = Fn._stream()
         d = ctypes.byref(self._desc)
-        call("unetr_aug_sample", d, self._table.data_ptr(), self.num_volumes, self._order.data_ptr(), self._state.data_ptr(),
-             self.params.data_ptr(), st)
-        call("unetr_aug_gather", d, self._table.data_ptr(), self.num_volumes, self.params.data_ptr(), x.data_ptr(), y.data_ptr(),
-             self._ws.data_ptr(), self._ws.numel(), st)
+        if self.affine is None:
+            call("unetr_aug_sample", d, self._table.data_ptr(), self.num_volumes, self._order.data_ptr(), self._state.data_ptr(),
+                 self.params.data_ptr(), st)
+            call("unetr_aug_gather", d, self._table.data_ptr(), self.num_volumes, self.params.data_ptr(), x.data_ptr(),
+                 y.data_ptr(), self._ws.data_ptr(), self._ws.numel(), st)
+        else:
+            call("unetr_aug_sample_affine", d, ctypes.byref(self._adesc), self._table.data_ptr(), self.num_volumes,
+                 self._order.data_ptr(), self._state.data_ptr(), self.params.data_ptr(), self.affine.data_ptr(), st)
+            call("unetr_aug_gather_affine", d, self._table.data_ptr(), self.num_volumes, self.params.data_ptr(),
+                 self.affine.data_ptr(), x.data_ptr(), y.data_ptr(), self._ws.data_ptr(), self._ws.numel(), st)
 
-    def apply(self, params: torch.Tensor, x: torch.Tensor, y: torch.Tensor) -> None:
-        """the gather alone with an explicit [B, 8] table (int32); a host table is checked against the volume shapes"""
+    def apply(self, params: torch.Tensor, x: torch.Tensor, y: torch.Tensor, affine: Optional[torch.Tensor] = None) -> None:
+        """the gather alone with an explicit [B, 8] table (int32) and, on an augment built with affine_prob > 0, an explicit
+        [B, 16] affine table (float32; None: no sample is flagged); host tables are checked (crop inside the volume, affine
+        values finite, flag 0 or 1)"""
         self._check_out(x, y)
+        if affine is not None:
+            if self.affine is None:
+                raise ValueError("an affine table needs an augment built with affine_prob > 0")
+            if tuple(affine.shape) != (self.batch_size, AFFINE_COLS):
+                raise ValueError(f"affine [{self.batch_size}, {AFFINE_COLS}] expected, got {tuple(affine.shape)}")
+            if not affine.is_cuda:
+                h = affine.to(torch.float32)
+                if not bool(torch.isfinite(h).all()):
+                    raise ValueError("affine: every value must be finite")
+                if not bool(((h[:, 0] == 0) | (h[:, 0] == 1)).all()):
+                    raise ValueError("affine: the flag (column 0) must be 0 or 1")
         if tuple(params.shape) != (self.batch_size, PARAM_COLS):
             raise ValueError(f"params [{self.batch_size}, {PARAM_COLS}] expected, got {tuple(params.shape)}")
         if not params.is_cuda:
@@ -320,5 +386,10 @@ class RandCropAugment:
                 if any(c < 0 or c + s > dm for c, s, dm in zip(r[1:4], self.spatial_size, dims)):
                     raise ValueError(f"params row {r}: the crop leaves the volume {tuple(dims)}")
         p = params.to(device=self.device, dtype=torch.int32).contiguous()
-        call("unetr_aug_gather", ctypes.byref(self._desc), self._table.data_ptr(), self.num_volumes, p.data_ptr(), x.data_ptr(),
-             y.data_ptr(), self._ws.data_ptr(), self._ws.numel(), Fn._stream())
+        if affine is None:
+            call("unetr_aug_gather", ctypes.byref(self._desc), self._table.data_ptr(), self.num_volumes, p.data_ptr(),
+                 x.data_ptr(), y.data_ptr(), self._ws.data_ptr(), self._ws.numel(), Fn._stream())
+        else:
+            a = affine.to(device=self.device, dtype=torch.float32).contiguous()
+            call("unetr_aug_gather_affine", ctypes.byref(self._desc), self._table.data_ptr(), self.num_volumes, p.data_ptr(),
+                 a.data_ptr(), x.data_ptr(), y.data_ptr(), self._ws.data_ptr(), self._ws.numel(), Fn._stream())

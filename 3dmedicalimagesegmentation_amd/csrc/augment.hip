@@ -10,9 +10,12 @@
 //   aug_scan_kernel      exclusive scan of the chunk counts (one workgroup) and the two totals
 //   aug_scatter_kernel   ordered compaction: each chunk again, AUG_CHUNK / 256 rounds of ballot + prefix, ascending ravel order
 // RandCropAugment.__call__ (per step: launches only, no host sync, no allocation):
-//   aug_sample_kernel    one workgroup: Philox4x64-10 draws, crop centres, the params table, counter and cursor advance
+//   aug_sample_kernel    one workgroup: Philox4x64-10 draws, crop centres, the params table, counter and cursor advance;
+//                        <true> also draws the rotation / zoom of each sample and writes the affine table
 //   aug_gather_kernel    every output voxel back through rot90^k, the flips and the corner to its source voxel; C image
-//                        channels (+ shift) and L label bytes; with normalize also fp64 partial sums per workgroup
+//                        channels (+ shift) and L label bytes; with normalize also fp64 partial sums per workgroup;
+//                        <., true> takes the samples its affine table flags through the matrix to a position between
+//                        voxels of the whole volume: trilinear image, nearest label, border padding (aug_affine_voxel)
 //   aug_norm_kernel      fixed-order reduction of the partials and (x - mean) / std over the nonzero voxels
 #include <algorithm>
 #include <math.h>
@@ -29,6 +32,10 @@ constexpr int AUG_MAXS = 512;         // crop extent per axis
 constexpr int AUG_NORM_WG = 64;       // workgroups per (sample, channel) of the normalize pass
 constexpr int AUG_ROW = 8;            // ints per params row: vol, z0, y0, x0, flip mask, k, shift flag, offset (float bits)
 constexpr int AUG_VCOLS = 12;         // int64 per volume table row: img, lbl, fg, nfg, bg, nbg, C, L, D, H, W, 0
+constexpr int AUG_AROW = 16;          // floats per affine row: flag, angle about axis 0, 1, 2, zoom of axis 0, 1, 2, M [3][3] row-major
+constexpr int AUG_BR0 = 8, AUG_BR1 = 16, AUG_BR2 = 16;   // output brick of one workgroup on a flagged sample (= AUG_TILE voxels)
+constexpr int AUG_MAXDIM_AFFINE = 1 << 24;               // extent up to which a float32 coordinate names every voxel
+static_assert(AUG_BR0 == AUG_VPT && AUG_BR1 * AUG_BR2 == 256, "one brick plane per round of the workgroup");
 
 // ---------------------------------------------------------------- Philox4x64-10 (Salmon et al. 2011; numpy.random.Philox)
 struct Ph4 { unsigned long long v[4]; };
@@ -218,9 +225,14 @@ aug_scatter_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lb
 
 // ---------------------------------------------------------------- per call: sampler
 // state (int64): [call counter, cursor, len(order), 0]
+// AFFINE: block 3 word 0 flags the sample, words 1..3 are the angles about axes 0..2, block 4 words 0..2 the zooms (word 0
+// for all three unless zoom_per_axis); blocks 0..2 are drawn as without it.  Angles and zooms are lo + (hi - lo) * u in
+// double, stored as float32; M = (R0 . R1) . R2 . diag(1 / z) in double from the STORED values, rounded once.
+template <bool AFFINE>
 __global__ void __launch_bounds__(256)
-aug_sample_kernel(UnetrAugDesc d, const long long* __restrict__ vols, int nvol, const int* __restrict__ order,
-                  long long* __restrict__ state, int* __restrict__ params) {
+aug_sample_kernel(UnetrAugDesc d, UnetrAugAffineDesc af, const long long* __restrict__ vols, int nvol,
+                  const int* __restrict__ order, long long* __restrict__ state, int* __restrict__ params,
+                  float* __restrict__ affine) {
 #pragma clang fp contract(off)
     const unsigned long long n = (unsigned long long)state[0];
     const long long cursor = state[1];
@@ -254,6 +266,33 @@ aug_sample_kernel(UnetrAugDesc d, const long long* __restrict__ vols, int nvol, 
         int* row = params + (long)s * AUG_ROW;
         row[0] = vol; row[1] = (int)corner[0]; row[2] = (int)corner[1]; row[3] = (int)corner[2];
         row[4] = flips; row[5] = k; row[6] = shift; row[7] = __float_as_int(off);
+        if (AFFINE) {
+            const Ph4 w3 = aug_block(d.seed, n, s, 3), w4 = aug_block(d.seed, n, s, 4);
+            float* arow = affine + (long)s * AUG_AROW;
+            const bool on = u01(w3.v[0]) < af.prob;
+            float ang[3] = {0.f, 0.f, 0.f}, zm[3] = {1.f, 1.f, 1.f};
+            float m[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+            if (on) {
+                double c[3], sn[3], inv[3];
+                for (int a = 0; a < 3; ++a) {
+                    ang[a] = (float)(-af.rotate[a] + (af.rotate[a] - -af.rotate[a]) * u01(w3.v[1 + a]));
+                    zm[a] = (float)(af.zoom_lo + (af.zoom_hi - af.zoom_lo) * u01(w4.v[af.zoom_per_axis ? a : 0]));
+                    c[a] = cos((double)ang[a]); sn[a] = sin((double)ang[a]); inv[a] = 1.0 / (double)zm[a];
+                }
+                const double r0[3][3] = {{1.0, 0.0, 0.0}, {0.0, c[0], -sn[0]}, {0.0, sn[0], c[0]}};
+                const double r1[3][3] = {{c[1], 0.0, sn[1]}, {0.0, 1.0, 0.0}, {-sn[1], 0.0, c[1]}};
+                const double r2[3][3] = {{c[2], -sn[2], 0.0}, {sn[2], c[2], 0.0}, {0.0, 0.0, 1.0}};
+                double t[3][3];
+                for (int i = 0; i < 3; ++i)
+                    for (int j = 0; j < 3; ++j) t[i][j] = (r0[i][0] * r1[0][j] + r0[i][1] * r1[1][j]) + r0[i][2] * r1[2][j];
+                for (int i = 0; i < 3; ++i)
+                    for (int j = 0; j < 3; ++j)
+                        m[i * 3 + j] = (float)(((t[i][0] * r2[0][j] + t[i][1] * r2[1][j]) + t[i][2] * r2[2][j]) * inv[j]);
+            }
+            arow[0] = on ? 1.f : 0.f;
+            for (int a = 0; a < 3; ++a) { arow[1 + a] = ang[a]; arow[4 + a] = zm[a]; }
+            for (int j = 0; j < 9; ++j) arow[7 + j] = m[j];
+        }
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -269,11 +308,77 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
+// crop position p of output voxel o: back through np.rot90(k, axes=(ra, rb)) (n = S[ra] = S[rb]), then the flips
+__device__ __forceinline__ void aug_crop_pos(const int o[3], const int S[3], int k, int ra, int rb, int n, int flips, int p[3]) {
+    p[0] = o[0]; p[1] = o[1]; p[2] = o[2];
+    if (k == 1) { p[ra] = o[rb]; p[rb] = n - 1 - o[ra]; }
+    else if (k == 2) { p[ra] = n - 1 - o[ra]; p[rb] = n - 1 - o[rb]; }
+    else if (k == 3) { p[ra] = n - 1 - o[rb]; p[rb] = o[ra]; }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) if (flips >> a & 1) p[a] = S[a] - 1 - p[a];
+}
+
+// The arithmetic of a flagged sample, float32 with no contraction, in the one order tests/augment_affine_ref.py restates:
+//   q_a   = (float)p_a - half_a,  half_a = (float)(S_a - 1) * 0.5f,  centre_a = (float)c0_a + half_a
+//   src_a = centre_a + ((M[a][0] * q0 + M[a][1] * q1) + M[a][2] * q2),  then clamped to [-1, dim_a]: whatever the matrix, the
+//           conversion to int below stays in range, and with border padding a position that far outside reads the border voxel
+//   f = floorf(src), t = src - f, i0 = clamp(f, 0, dim - 1), i1 = clamp(f + 1, 0, dim - 1)
+//   image: lerp a + t * (b - a) along axis 2, then 1, then 0;  label: voxel clamp(floorf(src + 0.5f), 0, dim - 1)
+struct AugTaps { long base[4]; int dx; float t[3]; long near; };     // base: (i0|i1 of axis 0, i0|i1 of axis 1) at i0 of axis 2
+
+__device__ __forceinline__ AugTaps aug_affine_taps(const int p[3], const float* m, const float half[3], const float centre[3],
+                                                   const int dims[3]) {
+#pragma clang fp contract(off)
+    const float q[3] = {(float)p[0] - half[0], (float)p[1] - half[1], (float)p[2] - half[2]};
+    int i0[3], i1[3], nr[3];
+    AugTaps tp;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float src = centre[a] + ((m[a * 3] * q[0] + m[a * 3 + 1] * q[1]) + m[a * 3 + 2] * q[2]);
+        src = fminf(fmaxf(src, -1.f), (float)dims[a]);
+        const float f = floorf(src);
+        tp.t[a] = src - f;
+        i0[a] = min(max((int)f, 0), dims[a] - 1);
+        i1[a] = min(max((int)f + 1, 0), dims[a] - 1);
+        nr[a] = min(max((int)floorf(src + 0.5f), 0), dims[a] - 1);
+    }
+    const long H = dims[1], W = dims[2];
+    tp.base[0] = ((long)i0[0] * H + i0[1]) * W + i0[2];
+    tp.base[1] = ((long)i0[0] * H + i1[1]) * W + i0[2];
+    tp.base[2] = ((long)i1[0] * H + i0[1]) * W + i0[2];
+    tp.base[3] = ((long)i1[0] * H + i1[1]) * W + i0[2];
+    tp.dx = i1[2] - i0[2];
+    tp.near = ((long)nr[0] * H + nr[1]) * W + nr[2];
+    return tp;
+}
+
+__device__ __forceinline__ float aug_trilinear(const float* __restrict__ img, const AugTaps& tp) {
+#pragma clang fp contract(off)
+    float r[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float a = img[tp.base[j]], b = img[tp.base[j] + tp.dx];
+        r[j] = a + tp.t[2] * (b - a);
+    }
+    const float u0 = r[0] + tp.t[1] * (r[1] - r[0]), u1 = r[2] + tp.t[1] * (r[3] - r[2]);
+    return u0 + tp.t[0] * (u1 - u0);
+}
+
+// workgroups per sample of the affine gather: enough for the ravel tiles of an unflagged sample and the bricks of a flagged one
+inline int aug_affine_blocks(const UnetrAugDesc* d) {
+    const long V = (long)d->S0 * d->S1 * d->S2;
+    return std::max(cdiv(V, AUG_TILE), cdiv(d->S0, AUG_BR0) * cdiv(d->S1, AUG_BR1) * cdiv(d->S2, AUG_BR2));
+}
+
 // grid (ceil(V / AUG_TILE), B); part: [B][C][gridDim.x][3] (count, sum, sum of squares over x != 0)
-template <bool NORM>
+// AFFINE: grid (aug_affine_blocks, B).  A sample whose affine row is flagged is cut into bricks of AUG_BR0 x AUG_BR1 x AUG_BR2
+// output voxels, one per workgroup, a 16 x 16 plane per round: the eight taps of neighbouring threads then share cache lines
+// whatever the rotation.  An unflagged sample takes the integer path below, tile for tile as without AFFINE (uniform per
+// workgroup), so it is written bit for bit as aug_gather_kernel<NORM, false> writes it.
+template <bool NORM, bool AFFINE>
 __global__ void __launch_bounds__(256)
 aug_gather_kernel(UnetrAugDesc d, const long long* __restrict__ vols, int nvol, const int* __restrict__ params,
-                  float* __restrict__ x, float* __restrict__ y, double* __restrict__ part) {
+                  const float* __restrict__ affine, float* __restrict__ x, float* __restrict__ y, double* __restrict__ part) {
 #pragma clang fp contract(off)
     const int s = blockIdx.y;
     const int* row = params + (long)s * AUG_ROW;
@@ -296,6 +401,44 @@ aug_gather_kernel(UnetrAugDesc d, const long long* __restrict__ vols, int nvol, 
     double cnt[AUG_MAXC], sum[AUG_MAXC], sq[AUG_MAXC];
 #pragma unroll
     for (int c = 0; c < AUG_MAXC; ++c) { cnt[c] = 0.0; sum[c] = 0.0; sq[c] = 0.0; }
+    const bool warped = AFFINE && affine[(long)s * AUG_AROW] != 0.f;
+    if (warped) {
+        float m[9], half[3], centre[3];
+#pragma unroll
+        for (int j = 0; j < 9; ++j) m[j] = affine[(long)s * AUG_AROW + 7 + j];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            half[a] = (float)(S[a] - 1) * 0.5f;
+            centre[a] = (float)c0[a] + half[a];
+            ok = ok && dims[a] <= AUG_MAXDIM_AFFINE;
+        }
+        const int nb1 = (S[1] + AUG_BR1 - 1) / AUG_BR1, nb2 = (S[2] + AUG_BR2 - 1) / AUG_BR2;
+        const int brick01 = blockIdx.x / nb2;
+        int o[3];
+        o[1] = (brick01 % nb1) * AUG_BR1 + (threadIdx.x >> 4);
+        o[2] = (blockIdx.x % nb2) * AUG_BR2 + (threadIdx.x & 15);
+#pragma unroll 2
+        for (int i = 0; i < AUG_BR0; ++i) {
+            o[0] = (brick01 / nb1) * AUG_BR0 + i;
+            if (o[0] >= S[0] || o[1] >= S[1] || o[2] >= S[2]) continue;
+            const long v = ((long)o[0] * S[1] + o[1]) * S[2] + o[2];
+            int p[3];
+            aug_crop_pos(o, S, k, ra, rb, n, flips, p);
+            AugTaps tp;
+            if (ok) tp = aug_affine_taps(p, m, half, centre, dims);
+#pragma unroll
+            for (int c = 0; c < AUG_MAXC; ++c) {
+                if (c >= d.C) continue;
+                float val = ok ? aug_trilinear(img + c * Vs, tp) : 0.f;
+                if (shift) val = val + off;
+                x[((long)s * d.C + c) * V + v] = val;
+                if (NORM && val != 0.f) { cnt[c] += 1.0; sum[c] += (double)val; sq[c] += (double)val * (double)val; }
+            }
+#pragma unroll
+            for (int l = 0; l < AUG_MAXC; ++l)
+                if (l < d.L) y[((long)s * d.L + l) * V + v] = ok ? (float)lbl[l * Vs + tp.near] : 0.f;
+        }
+    } else
 #pragma unroll
     for (int i = 0; i < AUG_VPT; ++i) {                      // unrolled: the loads of all AUG_VPT voxels are in flight together
         const long v = ((long)blockIdx.x * AUG_VPT + i) * 256 + threadIdx.x;
@@ -305,12 +448,8 @@ aug_gather_kernel(UnetrAugDesc d, const long long* __restrict__ vols, int nvol, 
         const long r = v / S[2];
         o[1] = (int)(r % S[1]);
         o[0] = (int)(r / S[1]);
-        int p[3] = {o[0], o[1], o[2]};                       // position before np.rot90(k, axes=(ra, rb))
-        if (k == 1) { p[ra] = o[rb]; p[rb] = n - 1 - o[ra]; }
-        else if (k == 2) { p[ra] = n - 1 - o[ra]; p[rb] = n - 1 - o[rb]; }
-        else if (k == 3) { p[ra] = n - 1 - o[rb]; p[rb] = o[ra]; }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) if (flips >> a & 1) p[a] = S[a] - 1 - p[a];
+        int p[3];
+        aug_crop_pos(o, S, k, ra, rb, n, flips, p);
         const long src = ((long)(c0[0] + p[0]) * H + (c0[1] + p[1])) * W + (c0[2] + p[2]);
 #pragma unroll
         for (int c = 0; c < AUG_MAXC; ++c) {
@@ -383,6 +522,12 @@ bool aug_desc_ok(const UnetrAugDesc* d) {
     return d->sampling == 0 || d->sampling == 1;
 }
 
+bool aug_affine_desc_ok(const UnetrAugAffineDesc* a) {
+    if (!a || !(a->prob >= 0.0 && a->prob <= 1.0)) return false;
+    for (int i = 0; i < 3; ++i) if (!(a->rotate[i] >= 0.0 && isfinite(a->rotate[i]))) return false;
+    return a->zoom_lo > 0.0 && a->zoom_lo <= a->zoom_hi && isfinite(a->zoom_hi);
+}
+
 }  // namespace
 
 extern "C" long unetr_aug_index_ws_ints(long V) { return V <= 0 ? 0 : 4L * cdiv(V, AUG_CHUNK) + 2; }
@@ -433,7 +578,17 @@ extern "C" int unetr_aug_index_scatter(const float* img, const uint8_t* lbl, int
 extern "C" int unetr_aug_sample(const UnetrAugDesc* d, const long long* vols, int nvol, const int* order, long long* state,
                                 int* params, void* stream) {
     if (!aug_desc_ok(d) || !vols || nvol <= 0 || !order || !state || !params) return UNETR_ERR_ARG;
-    hipLaunchKernelGGL(aug_sample_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *d, vols, nvol, order, state, params);
+    hipLaunchKernelGGL(aug_sample_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, *d, UnetrAugAffineDesc{}, vols, nvol,
+                       order, state, params, (float*)nullptr);
+    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+}
+
+extern "C" int unetr_aug_sample_affine(const UnetrAugDesc* d, const UnetrAugAffineDesc* a, const long long* vols, int nvol,
+                                       const int* order, long long* state, int* params, float* affine, void* stream) {
+    if (!aug_desc_ok(d) || !aug_affine_desc_ok(a) || !vols || nvol <= 0 || !order || !state || !params || !affine)
+        return UNETR_ERR_ARG;
+    hipLaunchKernelGGL(aug_sample_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, *d, *a, vols, nvol, order, state,
+                       params, affine);
     return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
 }
 
@@ -451,12 +606,35 @@ extern "C" int unetr_aug_gather(const UnetrAugDesc* d, const long long* vols, in
     const int nblk = cdiv(V, AUG_TILE);
     hipStream_t st = (hipStream_t)stream;
     if (d->normalize) {
-        hipLaunchKernelGGL(aug_gather_kernel<true>, dim3(nblk, d->B), dim3(256), 0, st, *d, vols, nvol, params, x, y,
-                           (double*)ws);
+        hipLaunchKernelGGL((aug_gather_kernel<true, false>), dim3(nblk, d->B), dim3(256), 0, st, *d, vols, nvol, params,
+                           (const float*)nullptr, x, y, (double*)ws);
         hipLaunchKernelGGL(aug_norm_kernel, dim3(AUG_NORM_WG, d->B * d->C), dim3(256), 0, st, x, V, (const double*)ws, nblk);
     } else {
-        hipLaunchKernelGGL(aug_gather_kernel<false>, dim3(nblk, d->B), dim3(256), 0, st, *d, vols, nvol, params, x, y,
-                           (double*)nullptr);
+        hipLaunchKernelGGL((aug_gather_kernel<false, false>), dim3(nblk, d->B), dim3(256), 0, st, *d, vols, nvol, params,
+                           (const float*)nullptr, x, y, (double*)nullptr);
+    }
+    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+}
+
+extern "C" size_t unetr_aug_gather_affine_ws_bytes(const UnetrAugDesc* d) {
+    if (!aug_desc_ok(d) || !d->normalize) return 0;
+    return (size_t)d->B * d->C * aug_affine_blocks(d) * 3 * sizeof(double);
+}
+
+extern "C" int unetr_aug_gather_affine(const UnetrAugDesc* d, const long long* vols, int nvol, const int* params,
+                                       const float* affine, float* x, float* y, void* ws, size_t ws_bytes, void* stream) {
+    if (!aug_desc_ok(d) || !vols || nvol <= 0 || !params || !affine || !x || !y) return UNETR_ERR_ARG;
+    if (d->normalize && (!ws || ws_bytes < unetr_aug_gather_affine_ws_bytes(d))) return UNETR_ERR_WORKSPACE;
+    const long V = (long)d->S0 * d->S1 * d->S2;
+    const int nblk = aug_affine_blocks(d);
+    hipStream_t st = (hipStream_t)stream;
+    if (d->normalize) {
+        hipLaunchKernelGGL((aug_gather_kernel<true, true>), dim3(nblk, d->B), dim3(256), 0, st, *d, vols, nvol, params, affine, x,
+                           y, (double*)ws);
+        hipLaunchKernelGGL(aug_norm_kernel, dim3(AUG_NORM_WG, d->B * d->C), dim3(256), 0, st, x, V, (const double*)ws, nblk);
+    } else {
+        hipLaunchKernelGGL((aug_gather_kernel<false, true>), dim3(nblk, d->B), dim3(256), 0, st, *d, vols, nvol, params, affine, x,
+                           y, (double*)nullptr);
     }
     return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
 }

@@ -519,7 +519,15 @@ int unetr_ranking_loss_bwd(const float* feat, int C, int S1, int S2, int S3, int
  * state (DEVICE int64: call counter, cursor, len(order), 0) is advanced by unetr_aug_sample, which writes params [B][8] (int32:
  * volume, corner z, y, x, flip mask, k, shift flag, offset as float bits) from Philox4x64-10 draws.  unetr_aug_gather maps every
  * voxel of x [B,C,S0,S1,S2] and y [B,L,S0,S1,S2] (float32) back to the volume; normalize adds NormalizeIntensity(nonzero=True,
- * channel_wise=True) per sample with ws of unetr_aug_gather_ws_bytes.  No host synchronisation. */
+ * channel_wise=True) per sample with ws of unetr_aug_gather_ws_bytes.  No host synchronisation.
+ * Random rotation and zoom (this project's own semantics): unetr_aug_sample_affine draws what
+ * unetr_aug_sample draws, from the same Philox words, and from blocks 3 and 4 of each sample the DEVICE table affine [B][16]
+ * (float32: flag 0 / 1, angle about spatial axis 0, 1, 2, zoom of axis 0, 1, 2, M [3][3] row-major; M = R0 R1 R2 diag(1 / zoom)
+ * in double from the stored float32 angles and zooms; an unflagged row holds zero angles, unit zooms and the identity).
+ * unetr_aug_gather_affine is unetr_aug_gather for the unflagged rows, bit for bit; an output voxel of a flagged row, at crop
+ * position p behind rot90 and the flips, reads the whole volume at c0 + (S - 1) / 2 + M (p - (S - 1) / 2): image trilinear,
+ * label nearest (floor(src + 0.5)), taps outside the volume clamped to the border, float32 arithmetic in one fixed order with
+ * no contraction (csrc/augment.hip: aug_affine_taps).  Volume extents up to 2^24.  Its workspace has its own query. */
 typedef struct {
     int B, num_samples, C, L, S0, S1, S2;
     int sampling;                     /* 0 RandCropByPosNegLabeld, 1 RandSpatialCropSamplesd */
@@ -544,6 +552,17 @@ int unetr_aug_sample(const UnetrAugDesc* d, const long long* vols, int nvol, con
 size_t unetr_aug_gather_ws_bytes(const UnetrAugDesc* d);
 int unetr_aug_gather(const UnetrAugDesc* d, const long long* vols, int nvol, const int* params, float* x, float* y, void* ws,
                      size_t ws_bytes, void* stream);
+typedef struct {
+    double prob;                      /* per sample */
+    double rotate[3];                 /* the angle about spatial axis a is uniform in [-rotate[a], rotate[a]] (radians) */
+    double zoom_lo, zoom_hi;          /* 0 < zoom_lo <= zoom_hi; a zoom z > 1 makes structures z times larger */
+    int zoom_per_axis;                /* 0: one zoom for the three axes, 1: one draw per axis */
+} UnetrAugAffineDesc;
+int unetr_aug_sample_affine(const UnetrAugDesc* d, const UnetrAugAffineDesc* a, const long long* vols, int nvol, const int* order,
+                            long long* state, int* params, float* affine, void* stream);
+size_t unetr_aug_gather_affine_ws_bytes(const UnetrAugDesc* d);
+int unetr_aug_gather_affine(const UnetrAugDesc* d, const long long* vols, int nvol, const int* params, const float* affine,
+                            float* x, float* y, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- per-volume resampling and reorientation (csrc/preprocess.hip; unetr_segmentation_3d.py:326-331) ----
  * Spacingd(mode=("bilinear", "nearest")) -> Orientationd [-> ConvertToMultiChannelBasedOnBratsClassesd] as one gather: output voxel

@@ -4,7 +4,11 @@
 
 Prints ONE JSON line: per case the median of --iters warmed calls timed with HIP events, the same with every sample rotated
 (rot90_prob=1) and unrotated (rot90_prob=0), the bytes the call must move and the implied rate.  With --cpu also the wall time
-of the CPU restatement (tests/augment_ref.py::apply_ref) on the same params, run once.  Cases:
+of the CPU restatement (tests/augment_ref.py::apply_ref) on the same params, run once.  Each case is also timed with every
+sample rotated and zoomed (affine_prob=1, rotate_range 30 degrees about each axis, zoom_range (0.7, 1.4): "affine_us"), with
+the bytes that gather must move at the least -- the distinct source voxels under the warped footprints of its last call
+(image taps 4 B x C, label voxels 1 B x L) plus the bytes written -- its floor at 8 TB/s, the achieved rate, the ratio to the
+plain call and the share of the 4.3 ms training step.  Cases:
   ct: 1 item x 4 samples of 96^3 from a 1-channel 320x320x200 volume, 14 classes, scale + foreground crop, all transforms
   mr: 1 item x 4 samples of 128^3 from a 4-channel 240x240x155 volume, 3 label channels, all transforms + normalize
 """
@@ -55,6 +59,31 @@ def time_calls(fn, iters):
     return statistics.median(ts)
 
 
+def affine_floor_bytes(aug, cache, C, L, normalize):
+    """the least bytes the affine call just made must move: distinct source voxels of every sample's footprint + the output"""
+    import augment_affine_ref as A
+    dims = cache.shapes[0][2:]
+    S = aug.spatial_size
+    src = 0
+    for r, a in zip(aug.params.cpu().tolist(), aug.affine.cpu()):
+        if float(a[0]) == 0.0:
+            src += S[0] * S[1] * S[2] * (C * 4 + L)
+            continue
+        sc = A.source_coords(S, r[1:4], r[4], r[5], aug.spatial_axes, a[7:16].numpy(), dims)
+        i0, i1, _ = A._taps(sc, dims)
+        taps = torch.zeros(dims, dtype=torch.bool)
+        for z in (i0[0], i1[0]):
+            for y in (i0[1], i1[1]):
+                for x in (i0[2], i1[2]):
+                    taps[z, y, x] = True
+        near = torch.zeros(dims, dtype=torch.bool)
+        n = [torch.floor(sc[k] + 0.5).long().clamp(0, dims[k] - 1) for k in range(3)]
+        near[n[0], n[1], n[2]] = True
+        src += int(taps.sum()) * C * 4 + int(near.sum()) * L
+    nvox = aug.batch_size * S[0] * S[1] * S[2]
+    return src + nvox * (C + L) * 4 + (2 * nvox * C * 4 if normalize else 0)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
@@ -94,6 +123,15 @@ def main():
             moved += 2 * nvox * c["C"] * 4
         res["bytes_moved"] = moved
         res["GBps"] = round(moved / (res["us"] * 1e-6) / 1e9, 1)
+        aug = pkg.RandCropAugment(cache, pos=1, neg=1, flip_prob=(0.1, 0.1, 0.1), rot90_prob=0.1, max_k=3, shift_offsets=0.1,
+                                  shift_prob=0.5, seed=1, affine_prob=1.0, rotate_range=0.5236, zoom_range=(0.7, 1.4), **c["aug"])
+        res["affine_us"] = round(time_calls(lambda: aug(x, y), args.iters), 2)
+        floor = affine_floor_bytes(aug, cache, c["C"], c["L"], c["aug"]["normalize"])
+        res["affine_bytes_floor"] = floor
+        res["affine_floor_us_at_8TBps"] = round(floor / 8e12 * 1e6, 2)
+        res["affine_GBps"] = round(floor / (res["affine_us"] * 1e-6) / 1e9, 1)
+        res["affine_over_plain"] = round(res["affine_us"] / res["us"], 2)
+        res["affine_share_of_4.3ms_step"] = round(res["affine_us"] / 4300.0, 4)
         if args.cpu:
             import augment_ref as R
             p = aug.params.cpu()
