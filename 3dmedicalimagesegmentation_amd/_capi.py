@@ -97,7 +97,7 @@ class SwVolume(ctypes.Structure):
     _fields_ = [("in_", c_void_p), ("out", c_void_p), ("count", c_void_p), ("table", c_void_p),
                 ("B", c_int), ("Cin", c_int), ("C", c_int), ("Di", c_int), ("Hi", c_int), ("Wi", c_int),
                 ("D", c_int), ("H", c_int), ("W", c_int), ("pz", c_int), ("py", c_int), ("px", c_int),
-                ("cval", c_float), ("rows", c_int), ("cursor", c_int)]
+                ("cval", c_float), ("rows", c_int), ("cursor", c_int), ("activation", c_int)]
 
 
 class RestoreGeom(ctypes.Structure):      # unetr_restore_geom, passed by value
@@ -195,6 +195,8 @@ _SIGNATURES = {
     "unetr_sw_gather_batch": [P, P, c_int, c_int, c_int, c_int, c_int, P],
     "unetr_sw_accumulate_batch": [P, P, P, c_int, c_int, c_int, c_int, c_int, P],
     "unetr_sw_finalize_post": [P, P, P, c_int, c_int, c_long, c_int, P],
+    "unetr_sw_rewind": [P, P],
+    "unetr_sw_finalize_post_thr": [P, P, P, c_int, c_int, c_long, c_int, c_float, P],
     "unetr_hausdorff": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, P, P, c_size_t, c_int, P],
     "unetr_surface_metrics": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_double), ctypes.POINTER(c_double), c_int,
                               ctypes.POINTER(c_double), P, P, c_size_t, c_int, P],

@@ -159,7 +159,23 @@ __device__ __forceinline__ void sw_st(float* p, const float (&r)[NV]) {
     }
 }
 
+// r[0..NV) in reverse order (the x-mirrored run of a window: load the mirrored aligned quad, reverse it in registers)
+template <int NV>
+__device__ __forceinline__ void sw_rev(float (&r)[NV]) {
+#pragma unroll
+    for (int k = 0; k < NV / 2; ++k) { const float t = r[k]; r[k] = r[NV - 1 - k]; r[NV - 1 - k] = t; }
+}
+
+// Window-local voxel (z, y, x .. x+NV-1) under flip mask f (bit 0 = z, 1 = y, 2 = x): the mirrored position.  With the x bit the
+// result is the START of the mirrored run, which holds the NV voxels in reverse order.
+__device__ __forceinline__ void sw_mirror(int f, int nv, int rz, int ry, int rx, int& z, int& y, int& x) {
+    if (f & 1) z = rz - 1 - z;
+    if (f & 2) y = ry - 1 - y;
+    if (f & 4) x = rx - nv - x;
+}
+
 __global__ void sw_advance_kernel(unetr_sw_volume* vol) { vol->cursor = vol->cursor + 1; }
+__global__ void sw_rewind_kernel(unetr_sw_volume* vol) { vol->cursor = -1; }
 
 // the row in flight, or nullptr-like failure (uniform per launch): loads the row into LDS
 __device__ __forceinline__ bool sw_load_row(const unetr_sw_volume* vol, int* row) {
@@ -176,7 +192,8 @@ __device__ __forceinline__ bool sw_slot_ok(const unetr_sw_volume* vol, const int
     return b >= 0 && b < vol->B && z >= 0 && y >= 0 && x >= 0 && z + rz <= vol->D && y + ry <= vol->H && x + rx <= vol->W;
 }
 
-// dst[j, c, z, y, x] = in[b_j, c, z_j + z - pz, y_j + y - py, x_j + x - px], cval outside the stored volume (and in unused slots)
+// dst[j, c, z, y, x] = in[b_j, c, z_j + z' - pz, y_j + y' - py, x_j + x' - px], cval outside the stored volume (and in unused slots);
+// (z', y', x') = (z, y, x) mirrored inside the window along the axes of the row's flip mask (header int 1; 0: as they are).
 template <int NV>
 __global__ void __launch_bounds__(256)
 sw_gather_batch_kernel(const unetr_sw_volume* __restrict__ vol, float* __restrict__ dst, int n, int Cin, int rz, int ry, int rx) {
@@ -194,7 +211,10 @@ sw_gather_batch_kernel(const unetr_sw_volume* __restrict__ vol, float* __restric
     for (int k = 0; k < NV; ++k) r[k] = cval;
     if (j < row[0] && sw_slot_ok(vol, row, j, rz, ry, rx)) {
         const int Di = vol->Di, Hi = vol->Hi, Wi = vol->Wi;
-        const int Z = row[5 + 4 * j] + z - vol->pz, Y = row[6 + 4 * j] + y - vol->py, X = row[7 + 4 * j] + x - vol->px;
+        const int f = row[1] & 7;
+        int zs = z, ys = y, xs = x;
+        sw_mirror(f, NV, rz, ry, rx, zs, ys, xs);
+        const int Z = row[5 + 4 * j] + zs - vol->pz, Y = row[6 + 4 * j] + ys - vol->py, X = row[7 + 4 * j] + xs - vol->px;
         if (Z >= 0 && Z < Di && Y >= 0 && Y < Hi) {
             const float* src = vol->in + (((long)row[4 + 4 * j] * Cin + c) * Di + Z) * (long)Hi * Wi + (long)Y * Wi;
             if (X >= 0 && X + NV <= Wi) {
@@ -205,6 +225,7 @@ sw_gather_batch_kernel(const unetr_sw_volume* __restrict__ vol, float* __restric
                     if (X + k >= 0 && X + k < Wi) r[k] = src[X + k];
             }
         }
+        if (f & 4) sw_rev<NV>(r);
     }
     sw_st<NV>(dst + ((long)j * Cin + c) * rv + ((long)z * ry + y) * rx + x, r);
 }
@@ -212,10 +233,13 @@ sw_gather_batch_kernel(const unetr_sw_volume* __restrict__ vol, float* __restric
 // NV x-neighbours at (Z, Y, X..) of one batch item, covered by exactly the windows in `mask`: add those windows in slot order.
 // The per-window update is the one sw_accumulate_kernel performs (out = fma(w, seg, out); count = count + w), so a voxel
 // receives the same fp32 operations in the same order as from one unetr_sw_accumulate launch per window.
+// f: the row's flip mask -- the windows were forwarded mirrored, so seg is read at the mirrored position (the weight is not: it
+// follows the position in the volume).  act: 0 seg as it is, 2 sigmoid(seg) per element, 1 softmax over the C channels of each
+// covering window: one pass for max and sum (rescaled when the max moves), one that blends exp(s - max) / sum.
 template <int NV>
 __device__ __forceinline__ void sw_blend(const int* row, unsigned mask, int Z, int Y, int X, const float* __restrict__ seg,
                                          const float* __restrict__ imp, float* __restrict__ out, float* __restrict__ count,
-                                         int C, int ry, int rx, long rv, int H, int W, long V) {
+                                         int C, int rz, int ry, int rx, long rv, int H, int W, long V, int f, int act) {
     const long o = ((long)Z * H + Y) * W + X;
     float cnt[NV], w[NV], s[NV], acc[NV];
     sw_ld<NV>(cnt, count + o);
@@ -227,14 +251,53 @@ __device__ __forceinline__ void sw_blend(const int* row, unsigned mask, int Z, i
         for (int k = 0; k < NV; ++k) cnt[k] += imp ? w[k] : 1.f;
     }
     sw_st<NV>(count + o, cnt);
+    if (act == 1) {
+        for (unsigned m = mask; m; m &= m - 1) {
+            const int i = __ffs(m) - 1;
+            int lz = Z - row[5 + 4 * i], ly = Y - row[6 + 4 * i], lx = X - row[7 + 4 * i];
+            const long li = ((long)lz * ry + ly) * rx + lx;
+            sw_mirror(f, NV, rz, ry, rx, lz, ly, lx);
+            const float* ps = seg + (long)i * C * rv + ((long)lz * ry + ly) * rx + lx;
+            if (imp) sw_ld<NV>(w, imp + li);
+            float mx[NV], sum[NV];
+            for (int c = 0; c < C; ++c) {
+                sw_ld<NV>(s, ps + (long)c * rv);
+#pragma unroll
+                for (int k = 0; k < NV; ++k) {
+                    if (c == 0) { mx[k] = s[k]; sum[k] = 1.f; }
+                    else if (s[k] > mx[k]) { sum[k] = fmaf(sum[k], expf(mx[k] - s[k]), 1.f); mx[k] = s[k]; }
+                    else sum[k] += expf(s[k] - mx[k]);
+                }
+            }
+            for (int c = 0; c < C; ++c) {
+                float* po = out + (long)c * V + o;
+                sw_ld<NV>(s, ps + (long)c * rv);
+#pragma unroll
+                for (int k = 0; k < NV; ++k) s[k] = expf(s[k] - mx[k]) / sum[k];
+                if (f & 4) sw_rev<NV>(s);
+                sw_ld<NV>(acc, po);
+#pragma unroll
+                for (int k = 0; k < NV; ++k) acc[k] = fmaf(imp ? w[k] : 1.f, s[k], acc[k]);
+                sw_st<NV>(po, acc);
+            }
+        }
+        return;
+    }
     for (int c = 0; c < C; ++c) {
         float* po = out + (long)c * V + o;
         sw_ld<NV>(acc, po);
         for (unsigned m = mask; m; m &= m - 1) {
             const int i = __ffs(m) - 1;
-            const long li = ((long)(Z - row[5 + 4 * i]) * ry + (Y - row[6 + 4 * i])) * rx + (X - row[7 + 4 * i]);
+            int lz = Z - row[5 + 4 * i], ly = Y - row[6 + 4 * i], lx = X - row[7 + 4 * i];
+            const long li = ((long)lz * ry + ly) * rx + lx;
+            sw_mirror(f, NV, rz, ry, rx, lz, ly, lx);
             if (imp) sw_ld<NV>(w, imp + li);
-            sw_ld<NV>(s, seg + ((long)i * C + c) * rv + li);
+            sw_ld<NV>(s, seg + ((long)i * C + c) * rv + ((long)lz * ry + ly) * rx + lx);
+            if (f & 4) sw_rev<NV>(s);
+            if (act == 2) {
+#pragma unroll
+                for (int k = 0; k < NV; ++k) s[k] = 1.f / (1.f + expf(-s[k]));
+            }
 #pragma unroll
             for (int k = 0; k < NV; ++k) acc[k] = fmaf(imp ? w[k] : 1.f, s[k], acc[k]);
         }
@@ -272,23 +335,26 @@ sw_accumulate_batch_kernel(const unetr_sw_volume* __restrict__ vol, const float*
     const long V = (long)vol->D * H * W;
     float* out = vol->out + (long)b * C * V;
     float* count = vol->count + (long)b * V;
+    const int f = row[1] & 7, act = vol->activation;
     bool same = true;
 #pragma unroll
     for (int k = 1; k < NV; ++k) same = same && mk[k] == mk[0];
     if (NV > 1 && same) {
-        if (__ffs(mk[0]) - 1 == j) sw_blend<NV>(row, mk[0], Z, Y, X, seg, imp, out, count, C, ry, rx, rv, H, W, V);
+        if (__ffs(mk[0]) - 1 == j) sw_blend<NV>(row, mk[0], Z, Y, X, seg, imp, out, count, C, rz, ry, rx, rv, H, W, V, f, act);
         return;
     }
 #pragma unroll
     for (int k = 0; k < NV; ++k)
-        if (__ffs(mk[k]) - 1 == j) sw_blend<1>(row, mk[k], Z, Y, X + k, seg, imp, out, count, C, ry, rx, rv, H, W, V);
+        if (__ffs(mk[k]) - 1 == j) sw_blend<1>(row, mk[k], Z, Y, X + k, seg, imp, out, count, C, rz, ry, rx, rv, H, W, V, f, act);
 }
 
 // v = out / count, then per voxel: post 0 stores v; 1 stores one_hot(argmax_c v) over out; 2 stores argmax_c v (as float) into
-// dst [B, V]; 3 stores (v >= 0) -- sigmoid(v) >= 0.5 -- over out.  argmax takes the first maximal channel (torch.argmax).
+// dst [B, V]; 3 stores (v >= thr) over out -- thr 0: sigmoid(v) >= 0.5 for blended logits; 0.5: for blended probabilities.  argmax
+// takes the first maximal channel (torch.argmax).
 template <int NV>
 __global__ void __launch_bounds__(256)
-sw_finalize_post_kernel(float* __restrict__ out, const float* __restrict__ count, float* __restrict__ dst, int C, long V, int post) {
+sw_finalize_post_kernel(float* __restrict__ out, const float* __restrict__ count, float* __restrict__ dst, int C, long V, int post,
+                        float thr) {
     const long v = ((long)blockIdx.x * 256 + threadIdx.x) * NV;
     if (v >= V) return;
     const int b = blockIdx.y;
@@ -302,7 +368,7 @@ sw_finalize_post_kernel(float* __restrict__ out, const float* __restrict__ count
         for (int k = 0; k < NV; ++k) {
             a[k] = a[k] / cn[k];
             if (c == 0 || a[k] > mx[k]) { mx[k] = a[k]; am[k] = c; }
-            if (post == 3) a[k] = a[k] >= 0.f ? 1.f : 0.f;
+            if (post == 3) a[k] = a[k] >= thr ? 1.f : 0.f;
         }
         if (post == 0 || post == 3) sw_st<NV>(ob + (long)c * V, a);
     }
@@ -324,6 +390,12 @@ sw_finalize_post_kernel(float* __restrict__ out, const float* __restrict__ count
 extern "C" int unetr_sw_advance(unetr_sw_volume* vol, void* stream) {
     if (!vol) return UNETR_ERR_ARG;
     hipLaunchKernelGGL(sw_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, vol);
+    return unetr_check_launch();
+}
+
+extern "C" int unetr_sw_rewind(unetr_sw_volume* vol, void* stream) {
+    if (!vol) return UNETR_ERR_ARG;
+    hipLaunchKernelGGL(sw_rewind_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, vol);
     return unetr_check_launch();
 }
 
@@ -351,13 +423,18 @@ extern "C" int unetr_sw_accumulate_batch(const unetr_sw_volume* vol, const float
     return unetr_check_launch();
 }
 
-extern "C" int unetr_sw_finalize_post(float* out, const float* count, float* dst, int B, int C, long V, int post, void* stream) {
+extern "C" int unetr_sw_finalize_post_thr(float* out, const float* count, float* dst, int B, int C, long V, int post, float threshold,
+                                          void* stream) {
     if (!out || !count || B <= 0 || B > 65535 || C <= 0 || V <= 0 || post < 0 || post > 3 || (post == 2 && !dst)) return UNETR_ERR_ARG;
     if ((post == 1 || post == 2) && C > DMAXC) return UNETR_ERR_UNSUPPORTED;
     const bool v4 = V % 4 == 0 && ((size_t)out & 15) == 0 && ((size_t)count & 15) == 0 && ((size_t)dst & 15) == 0;
     const dim3 grid(cdiv(cdiv(V, v4 ? 4 : 1), 256), B);
     hipStream_t st = (hipStream_t)stream;
-    if (v4) hipLaunchKernelGGL(sw_finalize_post_kernel<4>, grid, dim3(256), 0, st, out, count, dst, C, V, post);
-    else hipLaunchKernelGGL(sw_finalize_post_kernel<1>, grid, dim3(256), 0, st, out, count, dst, C, V, post);
+    if (v4) hipLaunchKernelGGL(sw_finalize_post_kernel<4>, grid, dim3(256), 0, st, out, count, dst, C, V, post, threshold);
+    else hipLaunchKernelGGL(sw_finalize_post_kernel<1>, grid, dim3(256), 0, st, out, count, dst, C, V, post, threshold);
     return unetr_check_launch();
+}
+
+extern "C" int unetr_sw_finalize_post(float* out, const float* count, float* dst, int B, int C, long V, int post, void* stream) {
+    return unetr_sw_finalize_post_thr(out, count, dst, B, C, V, post, 0.f, stream);
 }

@@ -239,12 +239,54 @@ class DiceMetric:
 
 # ---- SlidingWindowInferer: table-driven rows, captured forward, fused post-processing ------------------------------------------
 _POST = {None: 0, "onehot": 1, "argmax": 2, "sigmoid": 3}
+_ACTIVATION = {None: 0, "softmax": 1, "sigmoid": 2}      # unetr_sw_volume.activation
+_SOFTMAX_MAX_CHANNELS = 16
 
 
-def plan_window_table(batch, image_size, roi, overlap, n):
+def flip_masks(tta_flips):
+    """``tta_flips`` of SlidingWindowInferer as a list of flip masks (bit a = spatial axis a, the convention of
+    augment.PARAM_COLS), or None: "all" is masks 0..7; otherwise a non-empty sequence without repeats of axis tuples or masks."""
+    if tta_flips is None:
+        return None
+    if isinstance(tta_flips, str):
+        if tta_flips != "all":
+            raise ValueError(f"tta_flips must be None, 'all' or a sequence of axis tuples / masks, got {tta_flips!r}")
+        return list(range(8))
+    if not isinstance(tta_flips, (list, tuple)) or len(tta_flips) == 0:
+        raise ValueError(f"tta_flips must be None, 'all' or a non-empty sequence of axis tuples / masks, got {tta_flips!r}")
+    masks = []
+    for f in tta_flips:
+        if isinstance(f, bool):
+            raise ValueError(f"tta_flips: {f!r} is neither an axis tuple nor a mask")
+        if isinstance(f, int):
+            if not 0 <= f <= 7:
+                raise ValueError(f"tta_flips: mask {f} is outside 0..7")
+            m = f
+        elif isinstance(f, (list, tuple)):
+            if any(isinstance(a, bool) or not isinstance(a, int) or not 0 <= a <= 2 for a in f) or len(set(f)) != len(f):
+                raise ValueError(f"tta_flips: {f!r} is not a tuple of distinct spatial axes 0..2")
+            m = sum(1 << a for a in f)
+        else:
+            raise ValueError(f"tta_flips: {f!r} is neither an axis tuple nor a mask")
+        if m in masks:
+            raise ValueError(f"tta_flips: flip {f!r} is listed twice")
+        masks.append(m)
+    return masks
+
+
+def _finalize_threshold(post, activation):
+    """the threshold of post="sigmoid" on the averaged result: logits at 0, sigmoid probabilities at 0.5"""
+    if post == "sigmoid" and activation == "softmax":
+        raise ValueError("post='sigmoid' thresholds one channel at a time: it cannot follow activation='softmax'")
+    return 0.5 if activation == "sigmoid" else 0.0
+
+
+def plan_window_table(batch, image_size, roi, overlap, n, flips=None):
     """The windows of one call as rows of ``n`` slots, in the order sliding_window_inference visits them (batch item major, then
     _dense_patch_starts).  Returns (int32 CPU tensor [rows, SW_ROW_INTS] in the layout of include/unetr_hip.h: [active, 0, 0, 0,
-    (b, z, y, x) per slot], list of active counts per row); only the last row may hold fewer than ``n`` windows."""
+    (b, z, y, x) per slot], list of active counts per row); only the last row may hold fewer than ``n`` windows.
+    ``flips`` (a list of flip masks): every row becomes ``len(flips)`` consecutive rows with the same slots, one per flip in
+    order, the mask in header int 1; the counts are repeated with them."""
     if not 1 <= n <= _capi.SW_MAX_BATCH:
         raise ValueError(f"sw_batch_size must be in [1, {_capi.SW_MAX_BATCH}], got {n}")
     starts = _dense_patch_starts(image_size, roi, _scan_interval(image_size, roi, overlap))
@@ -259,6 +301,11 @@ def plan_window_table(batch, image_size, roi, overlap, n):
         counts.append(len(slots))
         table[r, 0] = len(slots)
         table[r, 4:4 + 4 * len(slots)] = torch.tensor(slots, dtype=torch.int32).flatten()
+    if flips is not None:
+        nf = len(flips)
+        table = table.repeat_interleave(nf, dim=0)
+        table[:, 1] = torch.tensor(list(flips), dtype=torch.int32).repeat(rows)
+        counts = [c for c in counts for _ in range(nf)]
     return table, counts
 
 
@@ -283,11 +330,29 @@ class SlidingWindowInferer:
     forwards the batch compositions the function forwards.  Anything else runs the same kernels eagerly.
     ``stats``: captures / recaptures / replays / eager_rows, counted over the inferer's life.
 
+    Mirror test-time augmentation and ensembling (this project's semantics, per window as nnU-Net does):
+    ``tta_flips`` -- None, "all" (flip masks 0..7) or a sequence of axis tuples ``()``, ``(0,)``, ``(1, 2)`` / masks 0..7 -- makes
+    every window be forwarded once per flip, mirrored inside the gather, and blended un-mirrored inside the accumulate;
+    ``activation`` -- None, "softmax" (at most 16 channels) or "sigmoid" -- is applied to each window prediction before it is
+    blended; ``network`` may be a list or tuple of networks whose predictions are blended into the same sums, model after model:
+
+        out[b, c, p] = sum_m sum_{windows k covering p} sum_{f in flips} w(p - k) * unflip_f(act(net_m(flip_f(x_b[k : k + roi]))))[c, p - k]
+        count[b, p]  = the same sum of w(p - k);   result = out / count
+
+    The weight w follows the position in the volume.  ``post`` works on that average: "sigmoid" thresholds at 0.5 after
+    activation="sigmoid" and is an error after "softmax".  The rows of a call are the plan's rows times the flips (the flip mask is
+    data in the row header), so the same captured graphs serve every flip; an ensemble takes the captured route when every member
+    is this package's UNETR, and ``replays`` / ``eager_rows`` count rows x flips x models.
+
     Weight freshness of a captured forward: see functional.invalidate_weight_shadows (rule for captured inference graphs)."""
 
     def __init__(self, roi_size, sw_batch_size: int = 1, overlap: float = 0.25, mode: str = "constant", sigma_scale=0.125,
-                 padding_mode: str = "constant", cval: float = 0.0, use_graph: bool = True):
+                 padding_mode: str = "constant", cval: float = 0.0, use_graph: bool = True, tta_flips=None, activation=None):
         _check_mode(mode)
+        if activation not in _ACTIVATION:
+            raise ValueError(f"activation must be one of {list(_ACTIVATION)}, got {activation!r}")
+        self.tta_flips = flip_masks(tta_flips)
+        self.activation = activation
         if overlap < 0 or overlap >= 1:
             raise AssertionError("overlap must be >= 0 and < 1.")
         if not 1 <= int(sw_batch_size) <= _capi.SW_MAX_BATCH:
@@ -311,7 +376,7 @@ class SlidingWindowInferer:
         if plan is None:
             if len(self._plans) > 64:
                 self._plans.clear()
-            plan = self._plans[key] = plan_window_table(B, image_size, roi, self.overlap, self.sw_batch_size)
+            plan = self._plans[key] = plan_window_table(B, image_size, roi, self.overlap, self.sw_batch_size, self.tta_flips)
         return plan
 
     def _desc_of(self, device):
@@ -466,14 +531,22 @@ class SlidingWindowInferer:
         return {m: self._graphs[k] for m, k in keys.items()}
 
     # ------------------------------------------------------------------------------------------------ call
+    def _check_channels(self, C):
+        if self.activation == "softmax" and C > _SOFTMAX_MAX_CHANNELS:
+            raise NotImplementedError(f"activation='softmax' takes at most {_SOFTMAX_MAX_CHANNELS} channels, got {C}")
+
     @torch.no_grad()
-    def __call__(self, inputs: torch.Tensor, network: Callable[..., torch.Tensor], post=None, *args, **kwargs) -> torch.Tensor:
+    def __call__(self, inputs: torch.Tensor, network, post=None, *args, **kwargs) -> torch.Tensor:
         from .unetr import UNETR
+        if post not in _POST:
+            raise ValueError(f"post must be one of {list(_POST)}, got {post!r}")
+        threshold = _finalize_threshold(post, self.activation)
+        networks = list(network) if isinstance(network, (list, tuple)) else [network]
+        if not networks:
+            raise ValueError("network: an ensemble needs at least one member")
         Fn._require_gpu(inputs)
         if inputs.dim() != 5:
             raise ValueError("3-D volumes [B,C,D,H,W] expected")
-        if post not in _POST:
-            raise ValueError(f"post must be one of {list(_POST)}, got {post!r}")
         device = inputs.device
         B, Cin = inputs.shape[0], inputs.shape[1]
         image_size_ = list(inputs.shape[2:])
@@ -498,11 +571,17 @@ class SlidingWindowInferer:
         desc = self._desc_of(device)
         D, H, W = image_size
         V = D * H * W
-        captured = self.use_graph and isinstance(network, UNETR) and not args and not kwargs
+        captured = self.use_graph and all(isinstance(net, UNETR) for net in networks) and not args and not kwargs
+        known = {net.out_channels for net in networks if isinstance(net, UNETR)}
+        if len(known) > 1:
+            raise ValueError(f"the networks of an ensemble must return the same channel count, got {sorted(known)}")
+        C = known.pop() if known else None
+        if C is not None:
+            self._check_channels(C)
         graphs = None
         if captured:
-            graphs = self._rows_captured(network, sorted(set(counts)), Cin, roi, desc, imp)
-        C = network.out_channels if isinstance(network, UNETR) else None
+            # (every member's graphs exist, and are fresh, before the first replay: a capture synchronises the device)
+            graphs = [self._rows_captured(net, sorted(set(counts)), Cin, roi, desc, imp) for net in networks]
         table = table_cpu.pin_memory().to(device, non_blocking=True)
         vol = _capi.SwVolume()
         vol.in_, vol.table = inputs.data_ptr(), table.data_ptr()
@@ -511,6 +590,7 @@ class SlidingWindowInferer:
         vol.D, vol.H, vol.W = D, H, W
         vol.pz, vol.py, vol.px = offs
         vol.cval, vol.rows, vol.cursor = self.cval, len(counts), -1
+        vol.activation = _ACTIVATION[self.activation]
         out = count = None
 
         def allocate(C):
@@ -527,19 +607,24 @@ class SlidingWindowInferer:
             vol.C = 0
             self._upload_desc(desc, vol)
         self._keep = (table, inputs)
-        if captured:
-            for m in counts:
-                graphs[m].graph.replay()
-            self.stats["replays"] += len(counts)
-        else:
+        # models in list order, each over the whole table from row 0; out / count persist, the cursor is rewound in between
+        for k, net in enumerate(networks):
+            if k:
+                call("unetr_sw_rewind", desc.data_ptr(), Fn._stream())
+            if captured:
+                for m in counts:
+                    graphs[k][m].graph.replay()
+                self.stats["replays"] += len(counts)
+                continue
             for r, m in enumerate(counts):
                 key = (m, Cin, tuple(roi), device.index)
                 static_in = self._inputs.get(key)
                 if static_in is None:
                     static_in = self._inputs[key] = torch.empty(m, Cin, *roi, dtype=torch.float32, device=device)
                 self._gather(desc, static_in, roi)
-                seg = self._forward(network, static_in, args, kwargs)
+                seg = self._forward(net, static_in, args, kwargs)
                 if out is None:
+                    self._check_channels(seg.shape[1])
                     vol.cursor = r                    # (the cursor has been advanced to this row already)
                     allocate(seg.shape[1])
                 elif seg.shape[1] != out.shape[1]:
@@ -548,8 +633,8 @@ class SlidingWindowInferer:
             self.stats["eager_rows"] += len(counts)
         C = out.shape[1]
         dst = torch.empty(B, 1, D, H, W, dtype=torch.float32, device=device) if post == "argmax" else None
-        call("unetr_sw_finalize_post", out.data_ptr(), count.data_ptr(), dst.data_ptr() if dst is not None else None, B, C, V,
-             _POST[post], Fn._stream())
+        call("unetr_sw_finalize_post_thr", out.data_ptr(), count.data_ptr(), dst.data_ptr() if dst is not None else None, B, C, V,
+             _POST[post], threshold, Fn._stream())
         res = dst if dst is not None else out
         sl = [slice(None), slice(None)]
         for sp in range(3):                       # undo the padding of volumes smaller than the window

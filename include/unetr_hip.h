@@ -453,6 +453,17 @@ int unetr_dice_counts(const float* pred, const float* y, int B, int C, long V, i
  *                             1: out = one_hot(argmax_c v); 2: dst [B, V] = argmax_c v as float (out is left as sums);
  *                             3: out = (v >= 0), i.e. sigmoid(v) >= 0.5.  argmax takes the first maximal channel; post 1 / 2
  *                             need C <= 16.
+ * Mirror test-time augmentation and ensembling (per window, the project's own semantics -- DESIGN.md section 18):
+ *   row header int 1          the row's flip mask (bit 0 = z, bit 1 = y, bit 2 = x; 0 = none).  unetr_sw_gather_batch hands the
+ *                             forward every window of the row mirrored along those axes (the mirror acts on the gathered, padded
+ *                             window), and unetr_sw_accumulate_batch reads seg at the mirrored position, so the prediction is
+ *                             blended un-flipped.  The importance map is indexed by the position in the VOLUME, never mirrored.
+ *   activation                trailing descriptor field, read at run time by unetr_sw_accumulate_batch: 0 blends seg as it is,
+ *                             1 softmax over the C channels of each window voxel, 2 sigmoid per element.
+ *   unetr_sw_rewind           cursor = -1 (device-side): the next model of an ensemble walks the table again, out / count persist
+ *   unetr_sw_finalize_post_thr  unetr_sw_finalize_post whose post = 3 stores (v >= threshold): 0 for blended logits, 0.5 for
+ *                             blended sigmoid probabilities.  unetr_sw_finalize_post is threshold 0.
+ * An all-zero header and activation are the behaviour described above, bit for bit.
  * (Additions: no existing signature moved, UNETR_ABI_VERSION stays.) */
 #define UNETR_SW_MAX_BATCH 16
 #define UNETR_SW_ROW_INTS (4 + 4 * UNETR_SW_MAX_BATCH)
@@ -464,12 +475,17 @@ typedef struct {
     int pz, py, px;       /* low-side padding */
     float cval;
     int rows, cursor;
+    int activation;       /* 0 none, 1 softmax over channels, 2 sigmoid: applied to seg inside unetr_sw_accumulate_batch (a trailing
+                             addition: a zero-initialised struct keeps the plain blend) */
 } unetr_sw_volume;
 int unetr_sw_advance(unetr_sw_volume* vol, void* stream);
 int unetr_sw_gather_batch(const unetr_sw_volume* vol, float* dst, int n, int Cin, int rz, int ry, int rx, void* stream);
 int unetr_sw_accumulate_batch(const unetr_sw_volume* vol, const float* seg, const float* importance, int n, int C,
                               int rz, int ry, int rx, void* stream);
 int unetr_sw_finalize_post(float* out, const float* count, float* dst, int B, int C, long V, int post, void* stream);
+int unetr_sw_rewind(unetr_sw_volume* vol, void* stream);
+int unetr_sw_finalize_post_thr(float* out, const float* count, float* dst, int B, int C, long V, int post, float threshold,
+                               void* stream);
 /* unetr_hausdorff: monai.metrics.HausdorffDistanceMetric (MONAI 0.6.0, distance_metric="euclidean", :495-496) per item and
  * class: out[b][c - c0] (float64, [B][C-c0]) for the classes c0 <= c < C (c0 = 1: include_background=False).  pred / y as in
  * unetr_dice_counts (from_logits fuses argmax + one-hot; otherwise a voxel is in a mask where its value == 1).  use_percentile = 0
