@@ -8,12 +8,14 @@ Layouts: token matrices [B*L, H]; feature maps channels-last [B, D, H, W, C] (po
 """
 import ctypes
 import os
-import weakref
 
 import torch
 
-from . import _capi, grad_arena
+from . import _capi, derived_weights, grad_arena
 from ._capi import GemmDesc, GemmBf16Desc, call, call_rc
+from .derived_weights import (_split_words, after_step, conv_pack_get, drop_wt_shadow, invalidate_weight_shadows,  # noqa: F401
+                              records_of, refresh_conv_packs, refresh_derived_weights, register_weight_shadow, shadow_at,
+                              shadow_ptr_for_update, twin_at, weight_bf16, weight_bf16_t, weight_x3, wt_enabled)
 from .grad_arena import (ArenaState, _DEFAULT_STATE, _gout, _ret, clear_grad_sinks, flush_deferred,  # noqa: F401
                          register_grad_sinks)
 
@@ -206,385 +208,18 @@ def gemm_bf16(A, B, M, N, K, *, b_kn=False, C=None, Cb=None, lda=None, ldb=None,
          Cb.data_ptr() if Cb is not None else None, ws.data_ptr(), ws.numel() * 4, _stream())
 
 
-# ---- bf16 operand storage (bf16 precision mode) ---------------------------------------------------------------
-# The encoder's Linear layers read bf16-STORED operands through unetr_gemm_bf16: activations are emitted as bf16 by
-# the producing kernels (LayerNorm, attention, GELU epilogue), weights come from a bf16 shadow.  A shadow is fresh when
-# (a) the flat-arena AdamW maintains it (the optimizer kernel writes the bf16 copy next to the fp32 master) and torch
-# has not modified the parameter since (version counter), or (b) it was cast in this "weight epoch" -- every code path
-# of this package that changes weights behind torch's back (per-parameter AdamW, DDP broadcast) bumps the epoch.
-# Under hipGraph capture a non-maintained shadow is always re-cast, so the cast is part of the captured step.
-_SHADOW = {}
-_SHADOW_AT = {}       # the same entries by the parameter's storage address (_prefetch is handed detached aliases)
-_WEIGHT_EPOCH = [0]
-
-
-def mark_flat_maintained(params, state=None):
-    """flat-arena AdamW has just rewritten the whole bf16 shadow arena together with the masters: every registered shadow
-    of these parameters is in step again.  Only walks the table after something of THIS model had to be re-derived: the
-    count lives in the model's ArenaState (a process-wide one let model A's step clear what model B still had to redo)."""
-    if state is None and params:
-        state = grad_arena.owner(params[0])
-    if state is not None and not state.unmaintained:
-        return
-    for w in params:
-        ent = _SHADOW.get(id(w))
-        if ent is not None and ent[4]() is w and ent[5] == w.data_ptr():
-            ent[1], ent[3] = w._version, True
-    if state is not None:
-        state.unmaintained = 0
-
-
-def invalidate_weight_shadows():
-    """Declare every derived weight copy (bf16 shadows, packed conv weights) stale.  MANDATORY after writing a parameter
-    through ``.data`` in place (``p.data.copy_()``, ``p.data.mul_()``, an EMA swap, a hand-written broadcast) once the
-    copies are optimizer-maintained (this package's AdamW has stepped): such a write changes neither the version counter
-    nor the storage address, so nothing else can notice it.  Everything torch can see is handled automatically: in-place
-    ops on the parameter, torch optimizers, ``load_state_dict``, re-pointed ``.data``, and -- for copies no optimizer of
-    this package maintains -- any change at all between two forward passes (``begin_forward``).
-
-    Captured inference graphs (inference.SlidingWindowInferer) follow the same contract.  A forward captured under no_grad
-    reads derived copies in two ways: a copy that no optimizer of this package maintained at capture time is re-derived INSIDE
-    the graph (weight_bf16 / conv_pack_get never trust an epoch under capture), so every replay is current; a copy that was
-    optimizer-maintained at capture time -- and the bf16x3 word shadow -- is read as it is.  Before the first replay of every
-    call the inferer therefore starts a new weight epoch and walks the as-is copies through these same getters eagerly: nothing
-    happens to a copy that is still maintained and in step, a stale one (version counter, address, or this function) is
-    re-derived into the same buffer, which the graph then reads.  If a parameter, a derived buffer or the scratch workspace has
-    moved since capture, the graph is captured again.  A live TrainStep on the same model needs nothing extra: its optimizer
-    kernels rewrite the buffers the inference graph reads."""
-    _WEIGHT_EPOCH[0] += 1
-    for ent in _SHADOW.values():
-        ent[1] = -1
-    for ent in _SHADOW_X3.values():
-        ent[1] = -1
-    for ent in _SHADOW_T.values():
-        ent[1] = -1
-    for ent in _PACKS.values():
-        ent[1] = -1
-
-
-def refresh_derived_weights(model):
-    """Re-derive, eagerly and into the SAME buffers, every derived weight copy of ``model`` (bf16 shadows, bf16x3 words, transposed
-    twins, packed conv weights) that is out of step with its parameter.  A captured TrainStep reads the copies its optimizer kernels
-    maintain as they are -- a replay runs no Python that could notice a change -- so this is the call to make after
-    ``model.load_state_dict()`` (or any other write torch can see) on a model whose training step is ALREADY captured: resuming
-    from a checkpoint after capture.  Copies that are current are left alone; before capture nothing is needed (the first forward
-    re-derives on demand).  ``.data`` writes behind the version counter still need invalidate_weight_shadows() first."""
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("refresh_derived_weights launches derive kernels: not while a hipGraph is being captured")
-    params = {id(p): p for p in model.parameters()}
-    for p in params.values():
-        ent = _SHADOW.get(id(p))
-        if ent is not None and ent[4]() is p:
-            weight_bf16(p)
-        ent = _SHADOW_X3.get(id(p))
-        if ent is not None and ent[2]() is p:
-            weight_x3(p)
-    for key, ent in list(_PACKS.items()):
-        p = params.get(key[0])
-        if p is not None and ent[4]() is p:
-            conv_pack_get(p, key[1], key[2])
-    flat = getattr(model, "_flat", None)
-    if flat is not None and flat.get("shadow_t") is not None:       # the twins, from the bf16 shadow arena made current above
-        todo = []
-        for e in _SHADOW_T.values():
-            p = e[2]()
-            if e[5] is flat["shadow_t"] and p is not None and not _wt_current(e, p) and _arena_shadow_of(flat, p, e[4]) is not None:
-                todo.append(e)
-        if todo:
-            _wt_derive(flat, todo)
+# ---- derived weight copies: derived_weights.py owns the tables and the freshness rules; the ops read weights through its getters ----
+grad_arena._stream = derived_weights._stream = _stream
 
 
 def begin_forward(state=None):
-    """Called by UNETR.forward.  (1) A derived weight copy that no optimizer of this package keeps in step is trusted for
-    ONE forward/backward pass only: a new pass starts a new weight epoch, so the first use re-derives it (a ``.data``
-    write between two passes is then always seen; optimizer-maintained copies stay valid, see
-    invalidate_weight_shadows).  (2) Deferred weight-gradient work a failed backward left behind is dropped, and so is a fused
-    epilogue (AdamW.begin_fused_step / TrainStep's bf16 communication epilogue) that was armed for a step which never finished."""
-    if not torch.cuda.is_current_stream_capturing():
-        _WEIGHT_EPOCH[0] += 1
+    """Called by UNETR.forward: a new pass starts a new weight epoch, and what a failed step left behind is dropped -- deferred
+    weight-gradient work, and a fused epilogue (AdamW.begin_fused_step / TrainStep's bf16 communication form) armed for it."""
+    derived_weights.begin_forward()
     if state is not None:
         state.reset_deferred()
         state.fuse = None          # an optimizer / communication epilogue is armed AFTER the forward of the step it belongs to:
                                    # whatever a failed step left armed must not ride on the next backward
-
-
-# ---- bf16x3 mode: word shadow of the weights ---------------------------------------------------------------------------------
-# The bf16x3 Linear GEMMs split their fp32 operands into (hi, lo) bf16 pairs in registers; the weight operand of a step is constant,
-# so with flat arenas its split form is kept as a second arena of words [hi | lo << 16] (unetr_split_words: one streaming launch
-# over the parameter arena after every optimizer step, AdamW.* -> refresh_x3_shadow) and the GEMM kernel splits only the activation
-# operand.  Same freshness rule as the bf16 shadow: valid while torch has not modified the parameter (version counter, address);
-# ``.data`` writes behind torch's back need invalidate_weight_shadows().  Created on first use (an eager pass: never under capture).
-_SHADOW_X3 = {}
-
-
-def x3_words_enabled():
-    """UNETR_AMD_X3_WORDS=0 (A/B hook): the bf16x3 GEMMs split the fp32 weights in registers like the activations"""
-    return os.environ.get("UNETR_AMD_X3_WORDS", "1") != "0"
-
-
-def _split_words(src, dst, n):
-    call("unetr_split_words", src.data_ptr(), dst.data_ptr(), n, _stream())
-
-
-def weight_x3(w):
-    """the weight as split words (int32 view, same shape) when `w` lives in a flat arena; else None (the kernel splits the fp32 weight)"""
-    if not x3_words_enabled():
-        return None
-    st = grad_arena.owner(w)
-    flat = st.flat if st is not None else None
-    if flat is None:
-        return None
-    if flat.get("shadow_x3") is None:
-        if torch.cuda.is_current_stream_capturing():
-            return None                      # (the arena must not come out of a graph's private pool)
-        arena = torch.empty(flat["total"], dtype=torch.int32, device=w.device)
-        _split_words(flat["param"], arena, flat["total"])
-        flat["shadow_x3"] = arena
-        for p, o in zip(flat["params"], flat["offsets"]):
-            _SHADOW_X3[id(p)] = [arena[o:o + p.numel()].view_as(p), p._version, weakref.ref(p), p.data_ptr(), (p.numel() + 7) // 8 * 8]
-    ent = _SHADOW_X3.get(id(w))
-    if ent is None or ent[2]() is not w or ent[3] != w.data_ptr() or ent[0].device != w.device:
-        return None
-    if ent[1] != w._version:                 # torch modified the parameter since the last derive: redo this slice (whole padded slot)
-        _split_words(w, ent[0], ent[4])
-        ent[1] = w._version
-    return ent[0]
-
-
-def refresh_x3_shadow(flat, written=False):
-    """optimizer side (flat arenas): the parameter arena has just been updated by kernels of this package.  written: those kernels
-    wrote the word shadow themselves (AdamW arena launches take its pointer); otherwise one derive launch over the arena -- when the
-    bf16x3 GEMMs have asked for a word shadow at all"""
-    arena = flat.get("shadow_x3") if flat is not None else None
-    if arena is None:
-        return
-    if not written:
-        _split_words(flat["param"], arena, flat["total"])
-    for p in flat["params"]:
-        ent = _SHADOW_X3.get(id(p))
-        if ent is not None and ent[2]() is p and ent[3] == p.data_ptr():
-            ent[1] = p._version
-
-
-# ---- bf16 mode: transposed bf16 shadow of the ViT Linear weights -------------------------------------------------------------
-# The data gradients dx = dy . W read W [out, in] as the [K, N] operand (b_kn = 1: transposing LDS reads).  With flat arenas a second
-# bf16 arena holds every such weight transposed -- W [N, K] at arena offset o has its twin [K, N] at shadow_t + o -- and the data
-# gradient runs in the forward kernel form (b_kn = 0) on it.  The fused weight-gradient + AdamW launch writes the twin next to the
-# bf16 shadow (unetr_gemm_bf16_grouped_wgrad_adamw_t); every other optimizer step of this package re-derives the twins it has
-# invalidated in one grouped launch (refresh_wt_shadow).  Both forms give the same bits (DESIGN section 10 item 5), so the arena is
-# only created where it is written for free: by a backward pass with the fused AdamW epilogue armed, outside graph capture.
-# Freshness: the rule of the word shadow above -- valid while torch has not modified the parameter (version counter, address);
-# invalidate_weight_shadows() after ``.data`` writes.  A stale or absent twin never raises: the caller keeps the b_kn form.
-_SHADOW_T = {}        # id(p) -> [twin view [K, N], version, weakref(p), address, arena offset, the twin arena]
-_SHADOW_T_AT = {}     # the same entries by storage address (_prefetch)
-
-
-def drop_wt_shadow(flat):
-    """forget the twin arena of a model and every table entry that points into it (ArenaState.clear)"""
-    arena = flat.pop("shadow_t", None) if flat is not None else None
-    if arena is None:
-        return
-    for tab in (_SHADOW_T, _SHADOW_T_AT):
-        for k in [k for k, e in tab.items() if e[5] is arena]:
-            del tab[k]
-
-
-def wt_enabled():
-    """UNETR_AMD_WT=0 (A/B hook): no transposed shadow, the data gradients stay on the b_kn form"""
-    return os.environ.get("UNETR_AMD_WT", "1") != "0"
-
-
-def _epilogue_twin_arena(flat):
-    """the twin arena of a model for the fused weight-gradient + AdamW launch to write, or None"""
-    return flat.get("shadow_t") if wt_enabled() and flat is not None else None
-
-
-grad_arena._stream, grad_arena._drop_twins, grad_arena._twin_arena = _stream, drop_wt_shadow, _epilogue_twin_arena
-
-
-def _wt_current(ent, w):
-    return ent is not None and ent[2]() is not None and ent[1] == w._version and ent[3] == w.data_ptr()
-
-
-def _wt_derive(flat, ents):
-    """twins of `ents` from the bf16 shadow arena (which the caller knows to be current for them) in ONE grouped launch"""
-    arr = (_capi.TransposeProblem * len(ents))()
-    for i, ent in enumerate(ents):
-        arr[i].offset, arr[i].K, arr[i].N = ent[4], ent[0].shape[0], ent[0].shape[1]      # (the twin is [K, N]: the weight [N, K])
-    call("unetr_transpose_bf16_grouped", flat["shadow"].data_ptr(), flat["shadow_t"].data_ptr(), arr, len(ents), _stream())
-    for ent in ents:
-        p = ent[2]()
-        ent[1], ent[3] = p._version, p.data_ptr()
-
-
-def _arena_shadow_of(flat, p, off):
-    """the bf16 shadow of `p`, current, when it IS the slice of the shadow arena (the derive launch reads the arena); else None"""
-    sh = weight_bf16(p)
-    return sh if sh.data_ptr() == flat["shadow"].data_ptr() + 2 * off else None
-
-
-def _keeps_twin(st):
-    """this backward pass ends in the epilogue that writes the twins (the fused AdamW form, not the bf16 communication form)"""
-    fz = st.fuse if st is not None else None
-    return fz is not None and fz.get("kind") != "bf16out"
-
-
-def weight_bf16_t(w):
-    """The transposed bf16 twin [in, out] of Linear weight `w` [out, in], or None (the caller then reads weight_bf16(w) as the
-    [K, N] operand).  Never launches under graph capture; creates the arena only for a backward pass whose weight-gradient launch
-    will keep it current (the fused AdamW epilogue), and under capture hands a twin out only to such a pass: the optimizer part of
-    any other captured step would leave it behind from the second replay on."""
-    if not wt_enabled() or w.dim() != 2 or w.shape[0] % 8 or w.shape[1] % 8:
-        return None
-    st = grad_arena.owner(w)
-    flat = st.flat if st is not None else None
-    if flat is None or flat.get("shadow") is None:
-        return None
-    capturing = torch.cuda.is_current_stream_capturing()
-    keeps = _keeps_twin(st)
-    if capturing and not keeps:
-        return None        # a replay runs no Python: a graph may read the twin only if the graph itself rewrites it every step
-    if flat.get("shadow_t") is None:
-        if capturing or not keeps:
-            return None
-        flat["shadow_t"] = torch.zeros(flat["total"], dtype=torch.bfloat16, device=w.device)
-    ent = _SHADOW_T.get(id(w))
-    if ent is None or ent[2]() is not w or ent[5] is not flat["shadow_t"]:
-        index = flat.get("_index")
-        if index is None:
-            index = flat["_index"] = {id(p): o for p, o in zip(flat["params"], flat["offsets"])}
-        off = index.get(id(w))
-        if off is None or flat["shadow_t"].device != w.device:
-            return None
-        ent = [flat["shadow_t"][off:off + w.numel()].view(w.shape[1], w.shape[0]), -1, weakref.ref(w), w.data_ptr(), off, flat["shadow_t"]]
-        _SHADOW_T[id(w)] = ent
-        _SHADOW_T_AT[w.data_ptr()] = ent
-    if not _wt_current(ent, w):
-        if capturing:
-            return None
-        # this twin and every other registered one of the arena that is stale (after invalidate_weight_shadows: all of them) in one launch
-        todo = []
-        for e in _SHADOW_T.values():
-            p = e[2]()
-            if e[5] is flat["shadow_t"] and p is not None and (e is ent or not _wt_current(e, p)) and _arena_shadow_of(flat, p, e[4]) is not None:
-                todo.append(e)
-        if not any(e is ent for e in todo):          # (identity: the entries hold tensors)
-            return None
-        _wt_derive(flat, todo)
-    return ent[0]
-
-
-def refresh_wt_shadow(flat, stepped, written=()):
-    """optimizer side (flat arenas): kernels of this package have just updated the parameters `stepped` and their bf16 shadow slices.
-    written: those whose twin the same kernels wrote (the fused weight-gradient epilogue) -- such a twin keeps its stamp: current if it
-    was current before the step, stale if it was stale.  Every other registered twin of a parameter that stepped is re-derived from
-    the bf16 shadow arena, all of them in one grouped launch (a step being captured only marks them stale: weight_bf16_t gave its
-    backward pass no twin, so its graph does not read them, and the next eager or fused pass re-derives them)."""
-    if flat is None or flat.get("shadow_t") is None:
-        return
-    written = {id(p) for p in written}
-    todo = []
-    for p in stepped:
-        ent = _SHADOW_T.get(id(p))
-        if ent is None or ent[5] is not flat["shadow_t"] or ent[2]() is not p or id(p) in written:
-            continue
-        sh = _SHADOW.get(id(p))
-        if (sh is not None and sh[4]() is p and sh[1] == p._version and sh[5] == p.data_ptr()
-                and sh[0].data_ptr() == flat["shadow"].data_ptr() + 2 * ent[4] and not torch.cuda.is_current_stream_capturing()):
-            todo.append(ent)
-        else:
-            ent[1] = -1            # (weight_bf16_t re-derives it when a backward pass asks)
-    if todo:
-        _wt_derive(flat, todo)
-
-
-def register_weight_shadow(w, shadow):
-    """flat-arena mode: `shadow` is the bf16 view the optimizer kernel keeps in step with `w`"""
-    _SHADOW[id(w)] = [shadow, w._version, _WEIGHT_EPOCH[0], True, weakref.ref(w), w.data_ptr()]   # caller has just cast it
-    _SHADOW_AT[w.data_ptr()] = _SHADOW[id(w)]
-
-
-def weight_bf16(w):
-    ent = _SHADOW.get(id(w))
-    if ent is None or ent[4]() is not w or ent[0].shape != w.shape or ent[0].device != w.device:
-        ent = [torch.empty(w.shape, dtype=torch.bfloat16, device=w.device), -1, -1, False, weakref.ref(w), 0]
-        _SHADOW[id(w)] = ent
-        _SHADOW_AT[w.data_ptr()] = ent
-    # (a re-pointed parameter -- `p.data = other` -- keeps its version counter: the storage address is part of the key)
-    fresh = ent[1] == w._version and ent[5] == w.data_ptr() and (
-        ent[3] or (ent[2] == _WEIGHT_EPOCH[0] and not torch.cuda.is_current_stream_capturing()))
-    if not fresh:
-        cast_bf16(w.detach(), out=ent[0])
-        # re-derived here = somebody other than this package's optimizer changed the weight (or may have): the copy is no
-        # longer optimizer-maintained until that optimizer steps again (shadow_ptr_for_update / mark_flat_maintained)
-        ent[1], ent[2], ent[5], ent[3] = w._version, _WEIGHT_EPOCH[0], w.data_ptr(), False
-        st = grad_arena.owner(w)
-        if st is not None:
-            st.unmaintained += 1
-    return ent[0]
-
-
-# ---- packed conv weights (MFMA operand layouts of csrc/conv3.hip) ------------------------------------------------------
-# Same freshness rules as the bf16 shadows: a pack is fresh when the optimizer of this package maintains it (one grouped
-# re-pack launch right after the update, refresh_conv_packs) and torch has not modified the parameter since, or it was
-# packed in this weight epoch outside graph capture.  kind 0 / 1: 3x3x3 forward / data gradient, 2 / 3: 1x1x1 forward /
-# transposed.  Without this the step spent ~25 five-microsecond pack launches on its critical path.
-_PACKS = {}
-
-
-def conv_pack_get(w, kind, prec):
-    key = (id(w), kind, prec)
-    ent = _PACKS.get(key)
-    cout, cin = w.shape[0], w.shape[1]
-    if ent is None or ent[4]() is not w or ent[0].device != w.device:
-        lib = _capi.load()
-        if kind == 4:          # transposed conv [in, out, 2, 2, 2] -> bf16 [in][tap][out]
-            nbytes = w.numel() * 2
-        else:
-            nbytes = lib.unetr_conv3_packed_bytes(cin, cout, kind, prec) if kind <= 1 else (
-                lib.unetr_conv3_packed_1x1_bytes(cin, cout, prec) if kind == 2 else lib.unetr_conv3_packed_1x1_bytes(cout, cin, prec))
-        ent = [torch.empty(nbytes, dtype=torch.uint8, device=w.device), -1, -1, False, weakref.ref(w), 0]
-        _PACKS[key] = ent
-    fresh = ent[1] == w._version and ent[5] == w.data_ptr() and (
-        ent[3] or (ent[2] == _WEIGHT_EPOCH[0] and not torch.cuda.is_current_stream_capturing()))
-    if not fresh:
-        _pack_launch([(w, ent[0], cin, cout, kind)], prec)
-        ent[1], ent[2], ent[5], ent[3] = w._version, _WEIGHT_EPOCH[0], w.data_ptr(), False
-    return ent[0]
-
-
-def _pack_launch(items, prec):
-    arr = (_capi.PackProblem * len(items))()
-    for i, (w, buf, cin, cout, kind) in enumerate(items):
-        arr[i].w, arr[i].out, arr[i].Cin, arr[i].Cout, arr[i].kind = w.data_ptr(), buf.data_ptr(), cin, cout, kind
-    call("unetr_conv3_pack_grouped", arr, len(items), prec, _stream())
-
-
-def refresh_conv_packs():
-    """optimizer side: re-pack every registered conv weight in one launch per precision; the packs are optimizer-maintained
-    from here on"""
-    by_prec = {}
-    for key, ent in list(_PACKS.items()):
-        w = ent[4]()
-        if w is None:
-            del _PACKS[key]
-            continue
-        if not w.is_cuda or ent[1] != w._version or ent[5] != w.data_ptr():
-            continue                                  # torch touched the parameter: conv_pack_get re-packs on demand
-        by_prec.setdefault(key[2], []).append((w, ent[0], w.shape[1], w.shape[0], key[1]))
-        ent[3] = True
-    for prec, items in by_prec.items():
-        _pack_launch(items, prec)
-
-
-def shadow_ptr_for_update(w):
-    """optimizer side: where the bf16 copy of `w` lives, if the GEMMs have asked for one; the caller's kernel rewrites
-    it together with the fp32 master, which makes the shadow optimizer-maintained from here on"""
-    ent = _SHADOW.get(id(w))
-    if ent is None or ent[4]() is not w or ent[1] != w._version or ent[5] != w.data_ptr():
-        return None
-    ent[3] = True
-    return ent[0].data_ptr()
 
 
 # Prefetch riders: the launch just before a ViT Linear GEMM (a LayerNorm, the attention core) carries spare workgroups that read
@@ -603,21 +238,15 @@ def _prefetch(host, *weights, dgrad=0):
         return None
     pf, n = _capi.Prefetch(), 0
     for w in weights:
-        if dgrad and w is not None and wt_enabled() and dgrad <= WT_MAX_ROWS:
-            st = grad_arena.owner(w)
-            tw = _SHADOW_T_AT.get(w.data_ptr())
-            if (tw is not None and _wt_current(tw, w) and tw[0].device == w.device and tw[0].numel() == w.numel()
-                    and (_keeps_twin(st) or not torch.cuda.is_current_stream_capturing())):
-                pf.ptr[n], pf.bytes[n] = tw[0].data_ptr(), tw[0].numel() * 2
-                n += 1
-                continue
-        # (by storage address: callers hand detached aliases of the next / lower block's parameters)
-        ent = _SHADOW_AT.get(w.data_ptr()) if w is not None else None
-        owner = ent[4]() if ent is not None else None
-        if owner is None or owner.data_ptr() != w.data_ptr() or ent[0].shape != w.shape or ent[0].device != w.device:
+        if w is None:
             continue
-        pf.ptr[n], pf.bytes[n] = ent[0].data_ptr(), ent[0].numel() * 2
-        n += 1
+        # (by storage address: callers hand detached aliases of the next / lower block's parameters)
+        buf = twin_at(w) if dgrad and wt_enabled() and dgrad <= WT_MAX_ROWS else None
+        if buf is None:
+            buf = shadow_at(w)
+        if buf is not None:
+            pf.ptr[n], pf.bytes[n] = buf.data_ptr(), buf.numel() * 2
+            n += 1
     return pf if n else None
 
 

@@ -344,7 +344,7 @@ class SlidingWindowInferer:
     data in the row header), so the same captured graphs serve every flip; an ensemble takes the captured route when every member
     is this package's UNETR, and ``replays`` / ``eager_rows`` count rows x flips x models.
 
-    Weight freshness of a captured forward: see functional.invalidate_weight_shadows (rule for captured inference graphs)."""
+    Weight freshness of a captured forward: see derived_weights.invalidate_weight_shadows (rule for captured inference graphs)."""
 
     def __init__(self, roi_size, sw_batch_size: int = 1, overlap: float = 0.25, mode: str = "constant", sigma_scale=0.125,
                  padding_mode: str = "constant", cval: float = 0.0, use_graph: bool = True, tta_flips=None, activation=None):
@@ -415,49 +415,25 @@ class SlidingWindowInferer:
     # ------------------------------------------------------------------------------------------------ capture
     @staticmethod
     def _derived_entries(model):
-        """(kind, parameter, table entry, getter arguments) of every derived weight copy registered for the model's parameters"""
-        params = {id(p): p for p in model.parameters()}
-        out = []
-        for pid, p in params.items():
-            ent = Fn._SHADOW.get(pid)
-            if ent is not None and ent[4]() is p:
-                out.append(("bf16", p, ent, ()))
-            ent = Fn._SHADOW_X3.get(pid)
-            if ent is not None and ent[2]() is p:
-                out.append(("x3", p, ent, ()))
-        for key, ent in Fn._PACKS.items():
-            p = params.get(key[0])
-            if p is not None and ent[4]() is p:
-                out.append(("pack", p, ent, (key[1], key[2])))
-        return out
+        """the record of every derived weight copy a forward reads that is registered for the model's parameters"""
+        return Fn.records_of(model.parameters())
 
     @staticmethod
     def _signature(model, device, derived):
         """every address a captured forward may have baked in: the parameters, the scratch workspace, and the buffers of the
-        derived copies that existed when it was captured (`derived`: (kind, weak parameter, getter arguments), looked up again)"""
+        derived copies that existed when it was captured (`derived`: their records then, looked up again)"""
         sig = [p.data_ptr() for p in model.parameters()]
         sig.append(Fn.workspace(device).data_ptr())
-        for kind, ref, extra in derived:
-            p = ref()
-            ent = None
-            if p is not None:
-                ent = (Fn._SHADOW.get(id(p)) if kind == "bf16" else Fn._SHADOW_X3.get(id(p)) if kind == "x3"
-                       else Fn._PACKS.get((id(p),) + tuple(extra)))
-            sig.append(ent[0].data_ptr() if ent is not None else 0)
+        for rec in derived:
+            cur = rec.current()
+            sig.append(cur.buf.data_ptr() if cur is not None else 0)
         return tuple(sig)
 
     @classmethod
     def _as_is(cls, model):
         """the derived copies a capture starting now would READ AS THEY ARE (optimizer-maintained, or the word shadow in step with
         its parameter) instead of re-deriving them inside the graph"""
-        out = []
-        for kind, p, ent, extra in cls._derived_entries(model):
-            if kind == "x3":
-                if ent[1] == p._version and ent[3] == p.data_ptr():
-                    out.append((kind, weakref.ref(p), extra))
-            elif ent[3] and ent[1] == p._version and ent[5] == p.data_ptr():
-                out.append((kind, weakref.ref(p), extra))
-        return out
+        return [rec for rec in cls._derived_entries(model) if rec.read_as_is()]
 
     def _capture(self, model, key, m, Cin, roi, desc, imp):
         from .train_step import side_stream
@@ -481,7 +457,7 @@ class SlidingWindowInferer:
             ent.seg = self._forward(model, ent.static_in, (), {})
             self._accumulate(desc, ent.seg, imp, roi)
         cur.wait_stream(side)
-        ent.derived = [(kind, weakref.ref(p), extra) for kind, p, _, extra in self._derived_entries(model)]
+        ent.derived = self._derived_entries(model)
         ent.signature = self._signature(model, device, ent.derived)
         self._graphs[key] = ent
         self.stats["captures"] += 1
@@ -494,19 +470,14 @@ class SlidingWindowInferer:
         Fn.begin_forward(None)
         seen = set()
         for ent in ents:
-            for kind, ref, extra in ent.as_is:
-                p = ref()
+            for rec in ent.as_is:
+                p = rec.param()
                 if p is None:
                     return False
-                if (kind, id(p), extra) in seen:
-                    continue
-                seen.add((kind, id(p), extra))
-                if kind == "bf16":
-                    Fn.weight_bf16(p)
-                elif kind == "x3":
-                    Fn.weight_x3(p)
-                else:
-                    Fn.conv_pack_get(p, *extra)
+                slot = (rec.kind, id(p), rec.pack)
+                if slot not in seen:
+                    seen.add(slot)
+                    rec.get()
         device = ents[0].static_in.device
         return all(ent.signature == self._signature(model, device, ent.derived) for ent in ents)
 

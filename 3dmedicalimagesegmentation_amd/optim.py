@@ -327,9 +327,8 @@ class AdamW(torch.optim.Optimizer):
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                 call("unetr_adamw_hyper", p.data_ptr(), g.data_ptr(), 0, 1.0, st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(),
                      self._hyper_ptr(gi), b1, b2, group["eps"], steps.data_ptr() + 4 * i, Fn.shadow_ptr_for_update(p), None, stream)
-        if self._flat is not None and per_tensor:
-            Fn.refresh_x3_shadow(self._flat)      # (per-tensor launches do not write the bf16x3 word shadow: one derive launch)
-            Fn.refresh_wt_shadow(self._flat, [p for g in self.param_groups for p in g["params"] if p.grad is not None])
+        if self._flat is not None and per_tensor:      # (per-tensor launches write neither the bf16x3 words nor the transposed twins)
+            Fn.after_step(self._flat, [p for g in self.param_groups for p in g["params"] if p.grad is not None], arena=False, repack=False)
         Fn.refresh_conv_packs()          # one grouped launch: packed conv weights follow the update
         return loss
 
@@ -359,7 +358,7 @@ class AdamW(torch.optim.Optimizer):
         b1, b2 = group["betas"]
         shadow = flat.get("shadow")            # bf16 copy of the arena read by the bf16-storage GEMMs, refreshed in the same kernel
         sptr = shadow.data_ptr() + lo * 2 if shadow is not None else None
-        words = flat.get("shadow_x3")          # bf16x3 mode: the word shadow (functional.weight_x3), written by the same kernel
+        words = flat.get("shadow_x3")          # bf16x3 mode: the word shadow (derived_weights.weight_x3), written by the same kernel
         wptr = words.data_ptr() + lo * 4 if words is not None else None
         call("unetr_adamw_hyper", flat["param"].data_ptr() + lo * 4, gptr + lo * (2 if g_bf16 else 4), int(g_bf16), gscale,
              m.data_ptr() + lo * 4, v.data_ptr() + lo * 4, hi - lo, self._hyper_ptr(0), b1, b2, group["eps"],
@@ -381,10 +380,7 @@ class AdamW(torch.optim.Optimizer):
         steps = self._advance_steps(0, params, pattern, dev)
         for run in self._flat_runs(params, pattern):
             self._launch_run(group, run, steps, gbase, False, 1.0, stream)
-        if flat.get("shadow") is not None:           # the kernel rewrote the bf16 shadow slices of every parameter that stepped
-            Fn.mark_flat_maintained([p for p, has in zip(params, pattern) if has], flat.get("state"))
-        Fn.refresh_x3_shadow(flat, written=True)     # (bf16x3 mode: the optimizer kernels wrote the word shadow)
-        Fn.refresh_wt_shadow(flat, [p for p, has in zip(params, pattern) if has])      # (bf16 mode: they did not write the transposed twins)
+        Fn.after_step(flat, [p for p, has in zip(params, pattern) if has], arena=True, repack=False)      # (step() re-packs once, at its end)
         return True
 
     # ---- single-GPU fused step: AdamW of the ViT Linear weights rides on the grouped weight-gradient launch ----------------
@@ -470,11 +466,7 @@ class AdamW(torch.optim.Optimizer):
         for k, has in enumerate(pattern):
             if has:
                 self._host_steps[k] += 1
-        Fn.refresh_x3_shadow(flat, written=True)
-        if flat.get("shadow") is not None:
-            Fn.mark_flat_maintained([p for p, has in zip(params, pattern) if has], flat.get("state"))
-        Fn.refresh_wt_shadow(flat, [p for p, has in zip(params, pattern) if has], written=[params[i] for i in fz["wt_done"]])
-        Fn.refresh_conv_packs()
+        Fn.after_step(flat, [p for p, has in zip(params, pattern) if has], arena=True, twins_written=[params[i] for i in fz["wt_done"]])
 
     # ---- data-parallel arena update: all-reduce pieces overlap the optimizer kernels of the pieces before them ----
     def plan_reduced(self, max_elems=None, cuts=(), pattern=None):
@@ -506,11 +498,7 @@ class AdamW(torch.optim.Optimizer):
 
     @torch.no_grad()
     def end_reduced_step(self, plan):
-        Fn.refresh_x3_shadow(self._flat, written=True)
-        if self._flat.get("shadow") is not None:
-            Fn.mark_flat_maintained([p for p, has in zip(self.param_groups[0]["params"], plan["pattern"]) if has], self._flat.get("state"))
-        Fn.refresh_wt_shadow(self._flat, [p for p, has in zip(self.param_groups[0]["params"], plan["pattern"]) if has])
-        Fn.refresh_conv_packs()
+        Fn.after_step(self._flat, [p for p, has in zip(self._flat["params"], plan["pattern"]) if has], arena=True)
 
     @torch.no_grad()
     def step_reduced(self, plan, gsrc, gscale, before_run=None, order=None):
@@ -518,12 +506,8 @@ class AdamW(torch.optim.Optimizer):
         the arena: the all-reduced communication buffer) times ``gscale``.  ``before_run(k, lo, hi)`` runs before range
         k's kernel is launched -- the caller makes the current stream wait for that range's all-reduce there."""
         group = self.param_groups[0]
-        params = group["params"]
-        dev = self._flat["param"].device
         stream = torch.cuda.current_stream().cuda_stream
-        if self._flat_state is None:
-            self._flat_state = (torch.zeros_like(self._flat["param"]), torch.zeros_like(self._flat["param"]))
-        steps = self._advance_steps(0, params, plan["pattern"], dev)
+        steps = self.begin_reduced_step(plan)
         g_bf16 = gsrc.dtype == torch.bfloat16
         if not g_bf16 and gsrc.dtype != torch.float32:
             raise RuntimeError("gradient source must be fp32 or bf16")
@@ -533,8 +517,4 @@ class AdamW(torch.optim.Optimizer):
             if before_run is not None:
                 before_run(k, run[2], run[3])
             self._launch_run(group, run, steps, gsrc.data_ptr(), g_bf16, gscale, stream)
-        Fn.refresh_x3_shadow(self._flat, written=True)
-        if self._flat.get("shadow") is not None:
-            Fn.mark_flat_maintained([p for p, has in zip(params, plan["pattern"]) if has], self._flat.get("state"))
-        Fn.refresh_wt_shadow(self._flat, [p for p, has in zip(params, plan["pattern"]) if has])
-        Fn.refresh_conv_packs()
+        self.end_reduced_step(plan)

@@ -263,13 +263,13 @@ class UNETR(nn.Module):
             old.clear()
         self._arena_state = Fn.register_grad_sinks(views, Fn.ArenaState())
         # bf16 shadow of the whole arena: the bf16-storage GEMMs read weights from it, AdamW(flat=...) rewrites it in
-        # the optimizer kernel (functional.weight_bf16 re-casts a slice if torch modifies the parameter itself)
+        # the optimizer kernel (derived_weights.weight_bf16 re-casts a slice if torch modifies the parameter itself)
         shadow = Fn.cast_bf16(flat_p)
         for p, o in zip(params, offs):
             Fn.register_weight_shadow(p, shadow[o:o + p.numel()].view_as(p))
         self._flat = dict(param=flat_p, grad=flat_g, offsets=offs, params=params, total=n, shadow=shadow,
                           state=self._arena_state)
-        self._arena_state.flat = self._flat        # (functional.weight_x3: the bf16x3 word shadow is an arena next to these)
+        self._arena_state.flat = self._flat        # (derived_weights.weight_x3: the bf16x3 word shadow is an arena next to these)
         return self._flat
 
     # first block of each ViT backward pass after the first, in execution order of backward (see forward_staged): passes run

@@ -173,7 +173,7 @@ def _twins_match(pkg, m, flat, stamped):
         assert torch.equal(_bits(flat["shadow_t"][o:o + N * K]).view(K, N), want), (N, K)
         assert torch.equal(flat["shadow"][o:o + N * K].view(N, K), w.detach().bfloat16())
         if stamped:
-            assert Fn._wt_current(Fn._SHADOW_T.get(id(w)), w)
+            assert Fn.twin_at(w) is not None
 
 
 def _takes_twin_route(pkg, m):
@@ -181,7 +181,7 @@ def _takes_twin_route(pkg, m):
     Fn = pkg.functional
     for w in _linear_weights(m):
         B, bkn = Fn._dgrad_operand(w, 16)
-        assert bkn is False and B.data_ptr() == Fn._SHADOW_T[id(w)][0].data_ptr() and B.shape == (w.shape[1], w.shape[0])
+        assert bkn is False and B.data_ptr() == Fn.twin_at(w).data_ptr() and B.shape == (w.shape[1], w.shape[0])
         assert Fn._dgrad_operand(w, Fn.WT_MAX_ROWS + 8)[1] is True          # (above the measured range: the b_kn form)
 
 

@@ -85,7 +85,7 @@ for cfg in ("6464", "3264", "64128"):
             lambda: Fn.gemm_bf16(dyb, w["w2"], M, MLP, H, b_kn=True, C=du, Cb=dub2, act=2, aux=u, ldaux=MLP))
         res[f"dgrad dy2  N=768  K=3072 cfg {cfg} {tag}"] = timeit(lambda: Fn.gemm_bf16(dub, w["w1"], M, H, MLP, b_kn=True, C=dx))
         res[f"dgrad datt N=768  K=768  cfg {cfg} {tag}"] = timeit(lambda: Fn.gemm_bf16(dyb, w["p"], M, H, H, b_kn=True, C=dx))
-# the same data gradients in the forward (b_kn = 0) form on the transposed weight twin [in, out] (functional.weight_bf16_t), and
+# the same data gradients in the forward (b_kn = 0) form on the transposed weight twin [in, out] (derived_weights.weight_bf16_t), and
 # dx of the qkv weight ([M x 768], K = 2304: a shape the forward form does not meet in the forward pass)
 wt = {n: t.t().contiguous() for n, t in w.items()}
 dqb_ = torch.randn(M, 3 * H, device=dev).bfloat16()

@@ -24,8 +24,8 @@ def main():
     # as in the bench run, where this package's AdamW keeps the bf16 weight shadows in step: one eager pass creates them, then they
     # count as optimizer-maintained (otherwise every captured forward re-casts its 49 weights)
     rl.encoder_forward_rate(pkg, model, x[:1], "bf16", iters=1)
-    for ent in pkg.functional._SHADOW.values():
-        ent[3] = True
+    for p in model.parameters():
+        pkg.functional.shadow_ptr_for_update(p)
     r = rl.encoder_forward_rate(pkg, model, x, "bf16", iters=int(os.environ.get("PROBE_ITERS", 10)))
     print(r, flush=True)
 
