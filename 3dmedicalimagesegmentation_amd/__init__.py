@@ -12,7 +12,7 @@ from .metrics import (ConfusionMatrixMetric, HausdorffDistanceMetric, SurfaceDic
                       surface_metrics)
 from .postprocess import KeepLargestConnectedComponent, connected_components, remove_small_components  # noqa: F401
 from .train_step import TrainStep  # noqa: F401
-from .augment import RandCropAugment, VolumeCache  # noqa: F401
+from .augment import IntensityAugment, RandCropAugment, VolumeCache  # noqa: F401
 from .preprocess import Geometry, resample_orient, restore_native  # noqa: F401
 from .functional import invalidate_weight_shadows, refresh_derived_weights  # noqa: F401
 from . import _capi, augment, ddp, functional, inference, metrics, postprocess, preprocess, train_step  # noqa: F401
@@ -20,5 +20,5 @@ from . import _capi, augment, ddp, functional, inference, metrics, postprocess, 
 __all__ = ["UNETR", "UNETRLogits", "DiceCELoss", "ranking_loss", "AdamW", "default_precision", "sliding_window_inference",
            "SlidingWindowInferer", "DiceMetric", "ConfusionMatrixMetric", "HausdorffDistanceMetric", "TrainStep", "invalidate_weight_shadows",
            "refresh_derived_weights",
-           "VolumeCache", "RandCropAugment", "resample_orient", "restore_native", "Geometry", "KeepLargestConnectedComponent", "connected_components",
+           "VolumeCache", "RandCropAugment", "IntensityAugment", "resample_orient", "restore_native", "Geometry", "KeepLargestConnectedComponent", "connected_components",
            "remove_small_components", "surface_metrics", "SurfaceDistanceMetric", "SurfaceDiceMetric"]

@@ -93,6 +93,10 @@ class AugAffineDesc(ctypes.Structure):
     _fields_ = [("prob", c_double), ("rotate", c_double * 3), ("zoom_lo", c_double), ("zoom_hi", c_double), ("zoom_per_axis", c_int)]
 
 
+class AugIntensityDesc(ctypes.Structure):      # index: noise std, blur sigma, brightness, contrast, gamma
+    _fields_ = [("prob", c_double * 5), ("lo", c_double * 5), ("hi", c_double * 5)]
+
+
 class SwVolume(ctypes.Structure):
     _fields_ = [("in_", c_void_p), ("out", c_void_p), ("count", c_void_p), ("table", c_void_p),
                 ("B", c_int), ("Cin", c_int), ("C", c_int), ("Di", c_int), ("Hi", c_int), ("Wi", c_int),
@@ -208,6 +212,8 @@ _SIGNATURES = {
     "unetr_aug_gather": [ctypes.POINTER(AugDesc), P, c_int, P, P, P, P, c_size_t, P],
     "unetr_aug_sample_affine": [ctypes.POINTER(AugDesc), ctypes.POINTER(AugAffineDesc), P, c_int, P, P, P, P, P],
     "unetr_aug_gather_affine": [ctypes.POINTER(AugDesc), P, c_int, P, P, P, P, P, c_size_t, P],
+    "unetr_aug_intensity_sample": [ctypes.POINTER(AugDesc), ctypes.POINTER(AugIntensityDesc), P, P, P],
+    "unetr_aug_intensity_apply": [ctypes.POINTER(AugDesc), P, P, P, c_size_t, P],
     "unetr_resample_orient": [P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_double), c_int, c_int, c_int, P, P, P],
     "unetr_restore_native": [P, c_int, c_int, RestoreGeom, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
     "unetr_ccl": [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint, c_int, c_int, c_int, c_int, P, c_size_t, c_int, P],
@@ -221,7 +227,7 @@ _SIGNATURES = {
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + ("unetr_conv3_packed_bytes", "unetr_conv3_packed_1x1_bytes", "unetr_ranking_workspace_floats",
                                             "unetr_conv3_wgrad_rows", "unetr_tconv2_wgrad_rows", "unetr_outconv_in_bwd_rows", "unetr_hausdorff_workspace_bytes",
                                             "unetr_aug_index_ws_ints", "unetr_aug_gather_ws_bytes", "unetr_aug_gather_affine_ws_bytes", "unetr_ccl_workspace_bytes",
-                                            "unetr_surface_metrics_workspace_bytes")
+                                            "unetr_surface_metrics_workspace_bytes", "unetr_aug_intensity_ws_bytes")
 
 _lib = None
 
@@ -269,6 +275,8 @@ def load():
     lib.unetr_aug_gather_ws_bytes.restype = c_size_t
     lib.unetr_aug_gather_affine_ws_bytes.argtypes = [ctypes.POINTER(AugDesc)]
     lib.unetr_aug_gather_affine_ws_bytes.restype = c_size_t
+    lib.unetr_aug_intensity_ws_bytes.argtypes = [ctypes.POINTER(AugDesc)]
+    lib.unetr_aug_intensity_ws_bytes.restype = c_size_t
     _lib = lib
     return lib
 

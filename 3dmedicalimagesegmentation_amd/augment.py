@@ -13,8 +13,13 @@ tests/augment_ref.py, which replays the params table of every call bit for bit o
 ``affine_prob > 0`` adds a random rotation and zoom per sample, taken at crop time from the whole cached volume in the same
 single gather (trilinear image, nearest label, border padding); its semantics are this project's own (RandCropAugment's
 docstring, DESIGN.md section 12, tests/augment_affine_ref.py).
+
+``intensity=IntensityAugment(...)`` adds nnU-Net's intensity family on x after all of that: Gaussian blur, Gaussian noise,
+brightness, contrast and gamma, flagged per sample, from the same Philox stream; again the project's own semantics
+(IntensityAugment's and RandCropAugment's docstrings, DESIGN.md section 12, tests/augment_intensity_ref.py).
 """
 import ctypes
+import dataclasses
 import math
 from typing import Optional, Sequence, Tuple, Union
 
@@ -22,9 +27,13 @@ import torch
 
 from . import functional as Fn
 from . import preprocess
-from ._capi import AugAffineDesc, AugDesc, call, load
+from ._capi import AugAffineDesc, AugDesc, AugIntensityDesc, call, load
 
 AFFINE_COLS = 16        # affine row (float32): flag, angle about spatial axis 0, 1, 2, zoom of axis 0, 1, 2, M [3][3] row-major
+INTENSITY_COLS = 16     # intensity row (int32, floats as bits): flag bits, noise std, blur sigma of axis 0, 1, 2, brightness factor,
+                        # contrast factor, gamma, low / high word of the call counter, six zeros
+INTENSITY_NOISE, INTENSITY_BLUR, INTENSITY_BRIGHTNESS, INTENSITY_CONTRAST, INTENSITY_GAMMA = 1, 2, 4, 8, 16
+MAX_BLUR_SIGMA = 2.0    # the blur's radius (int)(max(4 sigma, 0.5) + 0.5) stays within 8
 _MAXDIM_AFFINE = 1 << 24  # volume extent up to which a float32 coordinate still names every voxel
 PARAM_COLS = 8          # params row: volume, corner z, y, x, flip mask (bit a = spatial axis a), k, shift flag, offset (float bits)
 _VCOLS = 12             # device volume table row: img ptr, lbl ptr, fg ptr, nfg, bg ptr, nbg, C, L, D, H, W, 0
@@ -181,6 +190,69 @@ def _triple(v, name):
     return t
 
 
+def _bits_to_float(col: torch.Tensor) -> torch.Tensor:
+    return col.to(torch.int32).contiguous().view(torch.float32)
+
+
+@dataclasses.dataclass(frozen=True)
+class IntensityAugment:
+    """The intensity half of the augmentation, for ``RandCropAugment(..., intensity=...)``: per sample and with its own
+    probability each, Gaussian blur (one sigma per spatial axis), Gaussian noise (std), brightness (x * f), contrast
+    (clip((x - mean) * f + mean, min, max)) and gamma (((x - min) / (range + 1e-7)) ** gamma * range + min), applied in that
+    order to x after everything else the augment does (normalize included); y is not touched.  Values are uniform in their
+    ``(lo, hi)``; one set of draws serves all channels of a sample, statistics are per (sample, channel) over the crop.  These
+    semantics are this project's own: nnU-Net's choice of operations, MONAI's formulas, no bit parity with either
+    (tests/augment_intensity_ref.py).  Every probability defaults to 0: off."""
+    noise_prob: float = 0.0
+    noise_std: Tuple[float, float] = (0.0, 0.1)
+    blur_prob: float = 0.0
+    blur_sigma: Tuple[float, float] = (0.5, 1.0)
+    brightness_prob: float = 0.0
+    brightness_range: Tuple[float, float] = (0.75, 1.25)
+    contrast_prob: float = 0.0
+    contrast_range: Tuple[float, float] = (0.75, 1.25)
+    gamma_prob: float = 0.0
+    gamma_range: Tuple[float, float] = (0.7, 1.5)
+
+    _OPS = (("noise_prob", "noise_std"), ("blur_prob", "blur_sigma"), ("brightness_prob", "brightness_range"),
+            ("contrast_prob", "contrast_range"), ("gamma_prob", "gamma_range"))     # the order of the C descriptor
+
+    def __post_init__(self):
+        for pname, rname in self._OPS:
+            p = float(getattr(self, pname))
+            if not 0.0 <= p <= 1.0:
+                raise ValueError(f"{pname} must be in [0, 1], got {getattr(self, pname)}")
+            try:
+                lo, hi = (float(v) for v in getattr(self, rname))
+            except (TypeError, ValueError):
+                raise ValueError(f"{rname}: (low, high) expected, got {getattr(self, rname)!r}") from None
+            if not (math.isfinite(lo) and math.isfinite(hi)):
+                raise ValueError(f"{rname}: finite bounds expected, got {getattr(self, rname)!r}")
+            if lo > hi:
+                raise ValueError(f"{rname}: low > high ({lo} > {hi})")
+            if rname == "noise_std":
+                if lo < 0:
+                    raise ValueError(f"noise_std must be nonnegative, got {getattr(self, rname)!r}")
+            elif lo <= 0:
+                raise ValueError(f"{rname}: positive bounds expected, got {getattr(self, rname)!r}")
+            if rname == "blur_sigma" and hi > MAX_BLUR_SIGMA:
+                raise ValueError(f"blur_sigma must lie in (0, {MAX_BLUR_SIGMA}], got {getattr(self, rname)!r}")
+            object.__setattr__(self, pname, p)
+            object.__setattr__(self, rname, (lo, hi))
+
+    @classmethod
+    def nnunet(cls) -> "IntensityAugment":
+        """nnU-Net's probabilities (noise 0.1, blur 0.2, brightness 0.15, contrast 0.15, gamma 0.3) with the default ranges"""
+        return cls(noise_prob=0.1, blur_prob=0.2, brightness_prob=0.15, contrast_prob=0.15, gamma_prob=0.3)
+
+    def _desc(self) -> AugIntensityDesc:
+        d = AugIntensityDesc()
+        for j, (pname, rname) in enumerate(self._OPS):
+            d.prob[j] = getattr(self, pname)
+            d.lo[j], d.hi[j] = getattr(self, rname)
+        return d
+
+
 class RandCropAugment:
     """One training batch per call: B // num_samples volumes from the schedule, num_samples crops of each (item-major, MONAI's
     list collate order), each followed by RandFlipd per axis, RandRotate90d, RandShiftIntensityd and optionally
@@ -198,7 +270,16 @@ class RandCropAugment:
     affine at crop time, flips, rot90, shift, normalize.  The crop corner is drawn as without the affine: the crop box lies in
     the volume, its warped footprint need not.  This is NOT bit parity with MONAI's RandAffined: that one warps the already
     cropped patch (so it pads where this reads the neighbouring anatomy), pads by reflection by default and orders and
-    parametrises its matrix differently.  Unflagged samples are bit-identical to what ``affine_prob=0`` writes."""
+    parametrises its matrix differently.  Unflagged samples are bit-identical to what ``affine_prob=0`` writes.
+
+    ``intensity=IntensityAugment(...)`` adds, after all of the above and on x only, blur, noise, brightness, contrast and gamma
+    in that order, each flagged per sample, and records the draws in ``aug.intensity`` [B, 16] (int32, float values as their
+    bits: flag bits noise 1 / blur 2 / brightness 4 / contrast 8 / gamma 16, noise std, blur sigma of axis 0, 1, 2, brightness
+    factor, contrast factor, gamma, low and high word of the call counter that keyed the draws, six zeros; an unflagged operation
+    stores its neutral value).  The draws are Philox blocks 5..7 of the sample's stream, the noise of voxel group g of channel c
+    is block (n, s, 16 + c, 1 + g); ``params`` and ``affine`` do not move.  These semantics are this project's own (nnU-Net's
+    operations, MONAI's formulas, float32 in a fixed order: DESIGN.md section 12, tests/augment_intensity_ref.py), NOT bit
+    parity with either.  With ``intensity=None`` the augment calls exactly the entry points it called before."""
 
     def __init__(self, cache: VolumeCache, spatial_size: Union[int, Sequence[int]] = 96, num_samples: int = 4, pos: float = 1,
                  neg: float = 1, sampling: str = "pos_neg", flip_prob: Union[float, Sequence[float], None] = (0.1, 0.1, 0.1),
@@ -206,7 +287,10 @@ class RandCropAugment:
                  shift_offsets: Union[float, Sequence[float]] = 0.1, shift_prob: float = 0.5, normalize: Optional[str] = None,
                  seed: int = 0, batch_size: Optional[int] = None, order_capacity: Optional[int] = None,
                  affine_prob: float = 0.0, rotate_range: Union[float, Sequence[float], None] = None,
-                 zoom_range: Optional[Sequence[float]] = None, zoom_per_axis: bool = False):
+                 zoom_range: Optional[Sequence[float]] = None, zoom_per_axis: bool = False,
+                 intensity: Optional[IntensityAugment] = None):
+        if intensity is not None and not isinstance(intensity, IntensityAugment):
+            raise ValueError(f"intensity must be an IntensityAugment or None, got {type(intensity).__name__}")
         S = tuple(int(s) for s in _triple(spatial_size, "spatial_size"))
         if any(not 0 < s <= _MAXS for s in S):
             raise ValueError(f"spatial_size must be in 1..{_MAXS} per axis, got {S}")
@@ -306,6 +390,14 @@ class RandCropAugment:
             self.affine[:, [4, 5, 6, 7, 11, 15]] = 1.0
             ws = load().unetr_aug_gather_affine_ws_bytes(ctypes.byref(d))
         self._ws = torch.empty(max(ws, 8), dtype=torch.uint8, device=dev)
+        self.intensity_config = intensity
+        self.intensity = None                  # [B, 16] int32 once an IntensityAugment is given
+        self._idesc = self._iws = None
+        if intensity is not None:
+            self._idesc = intensity._desc()
+            self.intensity = torch.zeros(B, INTENSITY_COLS, dtype=torch.int32, device=dev)
+            self.intensity[:, 5:8] = 0x3F800000                                     # 1.0f: the neutral factors and gamma
+            self._iws = torch.empty(load().unetr_aug_intensity_ws_bytes(ctypes.byref(d)), dtype=torch.uint8, device=dev)
 
     # ---------------------------------------------------------------- schedule
     def set_order(self, ids) -> None:
@@ -349,6 +441,8 @@ class RandCropAugment:
         self._check_out(x, y)
         st = Fn._stream()
         d = ctypes.byref(self._desc)
+        if self.intensity is not None:         # before the sampler: it reads the call counter the sampler then advances
+            call("unetr_aug_intensity_sample", d, ctypes.byref(self._idesc), self._state.data_ptr(), self.intensity.data_ptr(), st)
         if self.affine is None:
             call("unetr_aug_sample", d, self._table.data_ptr(), self.num_volumes, self._order.data_ptr(), self._state.data_ptr(),
                  self.params.data_ptr(), st)
@@ -359,12 +453,41 @@ class RandCropAugment:
                  self._order.data_ptr(), self._state.data_ptr(), self.params.data_ptr(), self.affine.data_ptr(), st)
             call("unetr_aug_gather_affine", d, self._table.data_ptr(), self.num_volumes, self.params.data_ptr(),
                  self.affine.data_ptr(), x.data_ptr(), y.data_ptr(), self._ws.data_ptr(), self._ws.numel(), st)
+        if self.intensity is not None:
+            call("unetr_aug_intensity_apply", d, self.intensity.data_ptr(), x.data_ptr(), self._iws.data_ptr(), self._iws.numel(), st)
 
-    def apply(self, params: torch.Tensor, x: torch.Tensor, y: torch.Tensor, affine: Optional[torch.Tensor] = None) -> None:
+    def _check_intensity(self, table: torch.Tensor) -> None:
+        if self.intensity is None:
+            raise ValueError("an intensity table needs an augment built with intensity=IntensityAugment(...)")
+        if tuple(table.shape) != (self.batch_size, INTENSITY_COLS):
+            raise ValueError(f"intensity [{self.batch_size}, {INTENSITY_COLS}] expected, got {tuple(table.shape)}")
+        if table.is_cuda:
+            return
+        h = table.to(torch.int32)
+        flags = h[:, 0]
+        if not bool(((flags >= 0) & (flags <= 31)).all()):
+            raise ValueError("intensity: the flag bits (column 0) must be in 0..31")
+        v = _bits_to_float(h[:, 1:8])
+        if not bool(torch.isfinite(v).all()):
+            raise ValueError("intensity: every value must be finite")
+        if bool((v[:, 0] < 0).any()):
+            raise ValueError("intensity: the noise std (column 1) must be nonnegative")
+        blur = (flags & INTENSITY_BLUR) != 0
+        if bool((v[:, 1:4] > MAX_BLUR_SIGMA).any()) or bool((v[:, 1:4] < 0).any()) or bool((v[blur, 1:4] <= 0).any()):
+            raise ValueError(f"intensity: a blur sigma (columns 2..4) must lie in (0, {MAX_BLUR_SIGMA}] (0 on a row without blur)")
+        if bool((v[:, 4:7] <= 0).any()):
+            raise ValueError("intensity: brightness factor, contrast factor and gamma (columns 5..7) must be positive")
+
+    def apply(self, params: torch.Tensor, x: torch.Tensor, y: torch.Tensor, affine: Optional[torch.Tensor] = None,
+              intensity: Optional[torch.Tensor] = None) -> None:
         """the gather alone with an explicit [B, 8] table (int32) and, on an augment built with affine_prob > 0, an explicit
         [B, 16] affine table (float32; None: no sample is flagged); host tables are checked (crop inside the volume, affine
-        values finite, flag 0 or 1)"""
+        values finite, flag 0 or 1).  On an augment built with an IntensityAugment, an explicit [B, 16] intensity table (int32,
+        the layout of ``aug.intensity``; None: no operation is flagged) is followed by the intensity passes; a host table is
+        checked (flag bits 0..31, values finite, std >= 0, sigma <= 2 and > 0 where blur is flagged, factors and gamma > 0)."""
         self._check_out(x, y)
+        if intensity is not None:
+            self._check_intensity(intensity)
         if affine is not None:
             if self.affine is None:
                 raise ValueError("an affine table needs an augment built with affine_prob > 0")
@@ -393,3 +516,7 @@ class RandCropAugment:
             a = affine.to(device=self.device, dtype=torch.float32).contiguous()
             call("unetr_aug_gather_affine", ctypes.byref(self._desc), self._table.data_ptr(), self.num_volumes, p.data_ptr(),
                  a.data_ptr(), x.data_ptr(), y.data_ptr(), self._ws.data_ptr(), self._ws.numel(), Fn._stream())
+        if intensity is not None:
+            t = intensity.to(device=self.device, dtype=torch.int32).contiguous()
+            call("unetr_aug_intensity_apply", ctypes.byref(self._desc), t.data_ptr(), x.data_ptr(), self._iws.data_ptr(),
+                 self._iws.numel(), Fn._stream())

@@ -17,6 +17,11 @@
 //                        <., true> takes the samples its affine table flags through the matrix to a position between
 //                        voxels of the whole volume: trilinear image, nearest label, border padding (aug_affine_voxel)
 //   aug_norm_kernel      fixed-order reduction of the partials and (x - mean) / std over the nonzero voxels
+// with an IntensityAugment (this project's own semantics), per call five more launches on x alone:
+//   aug_intensity_sample_kernel   one workgroup, before aug_sample_kernel: Philox blocks 5..7, the intensity table
+//   aug_blur_strided_kernel x 2, aug_blur_rows_kernel   separable Gaussian blur: axis 0 x -> ws, axis 1 ws -> x, axis 2 in place
+//   aug_intensity_point_kernel    counter-based Gaussian noise, brightness, (min, max, fp64 sum) partials per channel
+//   aug_intensity_tone_kernel     contrast and gamma from those statistics
 #include <algorithm>
 #include <math.h>
 #include "common.hpp"
@@ -512,6 +517,286 @@ aug_norm_kernel(float* __restrict__ x, long V, const double* __restrict__ part, 
     }
 }
 
+// ---------------------------------------------------------------- per call: intensity augmentation (this project's semantics)
+// table (int32 [B][AUG_IROW], floats as their bits): flag bits (noise 1, blur 2, brightness 4, contrast 8, gamma 16), noise std,
+// blur sigma of axis 0, 1, 2, brightness factor, contrast factor, gamma, low / high word of the call counter n, six zeros.
+// Everything below runs on x only, after the gather (+ normalize): blur, noise, brightness, contrast, gamma.  float32, no
+// contraction, in the one order tests/augment_intensity_ref.py restates.  Flags are read from the table, so the workgroups of a
+// sample whose flag is clear return at once, uniformly; grids are fixed.
+constexpr int AUG_IROW = 16;
+constexpr int AUG_I_NOISE = 1, AUG_I_BLUR = 2, AUG_I_BRIGHT = 4, AUG_I_CONTRAST = 8, AUG_I_GAMMA = 16;
+constexpr int AUG_BLUR_MAXR = 8;      // R = (int)(max(4 sigma, 0.5) + 0.5) with sigma <= 2
+constexpr int AUG_BLUR_T = 16;        // outputs per thread along a strided axis
+constexpr int AUG_BLUR_LDS = 2048;    // floats of whole rows one workgroup stages for the pass along axis 2 (>= AUG_MAXS)
+constexpr int AUG_TONE_TILE = 4096;   // voxels per workgroup of the contrast / gamma pass (a multiple of 1024)
+constexpr int AUG_NOISE_BLOCK = 16;  // Philox block of channel 0's noise: counter (n, s, 16 + c, 1 + group of 8 voxels)
+static_assert(AUG_BLUR_LDS >= AUG_MAXS, "one row fits");
+
+// blocks 5..7 of the sample's stream; blocks 0..4 are aug_sample_kernel's and do not move.  Reads state[0], writes no state.
+__global__ void __launch_bounds__(256)
+aug_intensity_sample_kernel(UnetrAugDesc d, UnetrAugIntensityDesc it, const long long* __restrict__ state, int* __restrict__ table) {
+#pragma clang fp contract(off)
+    const unsigned long long n = (unsigned long long)state[0];
+    for (int s = threadIdx.x; s < d.B; s += 256) {
+        const Ph4 w5 = aug_block(d.seed, n, s, 5), w6 = aug_block(d.seed, n, s, 6), w7 = aug_block(d.seed, n, s, 7);
+        const unsigned long long fw[5] = {w5.v[0], w5.v[2], w5.v[3], w7.v[0], w7.v[2]};      // flag word of noise, blur, brightness, contrast, gamma
+        const unsigned long long vw[5] = {w5.v[1], 0ull, w6.v[3], w7.v[1], w7.v[3]};          // value word (the blur has three, below)
+        int flags = 0;
+        float val[5] = {0.f, 0.f, 1.f, 1.f, 1.f}, sg[3] = {0.f, 0.f, 0.f};
+        for (int j = 0; j < 5; ++j) {
+            if (!(u01(fw[j]) < it.prob[j])) continue;
+            flags |= 1 << j;
+            if (j == 1) for (int a = 0; a < 3; ++a) sg[a] = (float)(it.lo[1] + (it.hi[1] - it.lo[1]) * u01(w6.v[a]));
+            else val[j] = (float)(it.lo[j] + (it.hi[j] - it.lo[j]) * u01(vw[j]));
+        }
+        int* row = table + (long)s * AUG_IROW;
+        row[0] = flags; row[1] = __float_as_int(val[0]);
+        for (int a = 0; a < 3; ++a) row[2 + a] = __float_as_int(sg[a]);
+        row[5] = __float_as_int(val[2]); row[6] = __float_as_int(val[3]); row[7] = __float_as_int(val[4]);
+        row[8] = (int)(unsigned)(n & 0xffffffffull); row[9] = (int)(unsigned)(n >> 32);
+        for (int j = 10; j < AUG_IROW; ++j) row[j] = 0;
+    }
+}
+
+// normalised taps w[0 .. 2R] of one axis into LDS (g, w: 2 * AUG_BLUR_MAXR + 1 floats each); every thread of the workgroup calls
+// it.  g_k = expf(-(float)(k k) / (2 sigma sigma)), w_k = g_k / sum(g), the sum in order k = -R .. R.  A sigma that is not
+// positive (possible only in a device table nobody checked) gives the single tap 1.
+__device__ __forceinline__ int aug_blur_weights(float sigma, float* g, float* w) {
+#pragma clang fp contract(off)
+    int R = 0;
+    if (sigma > 0.f) R = (int)fminf(fmaxf(4.0f * sigma, 0.5f) + 0.5f, (float)AUG_BLUR_MAXR);
+    const int t = threadIdx.x;
+    if (t <= 2 * R) {
+        const int k = t - R;
+        g[t] = R ? expf(-(float)(k * k) / (2.0f * sigma * sigma)) : 1.f;
+    }
+    __syncthreads();
+    if (t <= 2 * R) {
+        float sum = 0.f;
+        for (int j = 0; j <= 2 * R; ++j) sum = sum + g[j];
+        w[t] = g[t] / sum;
+    }
+    __syncthreads();
+    return R;
+}
+
+// AUG_BLUR_T outputs a0 .. of one column: the window of AUG_BLUR_T + 2R inputs (indices clamped into the crop: border padding)
+// sits in registers, every index a compile-time constant
+template <int R>
+__device__ __forceinline__ void aug_blur_column(const float* __restrict__ src, float* __restrict__ dst, long base, long stride,
+                                                int A, int a0, const float* w) {
+#pragma clang fp contract(off)
+    float win[AUG_BLUR_T + 2 * R], wk[2 * R + 1];
+#pragma unroll
+    for (int j = 0; j < AUG_BLUR_T + 2 * R; ++j) win[j] = src[base + (long)min(max(a0 + j - R, 0), A - 1) * stride];
+#pragma unroll
+    for (int k = 0; k <= 2 * R; ++k) wk[k] = w[k];
+#pragma unroll
+    for (int i = 0; i < AUG_BLUR_T; ++i) {
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k <= 2 * R; ++k) acc = acc + wk[k] * win[i + k];
+        if (a0 + i < A) dst[base + (long)(a0 + i) * stride] = acc;
+    }
+}
+
+// the pass along axis 0 or 1: a sample's [C][S0][S1][S2] block seen as [outer][A][inner], one thread per (outer, inner) column,
+// neighbouring threads on neighbouring inner positions (coalesced as they stand).  grid (ceil(outer inner / 256), ceil(A / T), B)
+__global__ void __launch_bounds__(256)
+aug_blur_strided_kernel(const int* __restrict__ table, int axis, const float* __restrict__ src, float* __restrict__ dst, long sample_elems,
+                        long outer, int A, long inner) {
+    __shared__ float g[2 * AUG_BLUR_MAXR + 1], w[2 * AUG_BLUR_MAXR + 1];
+    const int s = blockIdx.z;
+    const int* row = table + (long)s * AUG_IROW;
+    if (!(row[0] & AUG_I_BLUR)) return;
+    const int R = aug_blur_weights(__int_as_float(row[2 + axis]), g, w);
+    const long col = (long)blockIdx.x * 256 + threadIdx.x;
+    if (col >= outer * inner) return;
+    const long base = (long)s * sample_elems + (col / inner) * A * inner + col % inner;
+    const int a0 = blockIdx.y * AUG_BLUR_T;
+    switch (R) {
+        case 0: aug_blur_column<0>(src, dst, base, inner, A, a0, w); break;
+        case 1: aug_blur_column<1>(src, dst, base, inner, A, a0, w); break;
+        case 2: aug_blur_column<2>(src, dst, base, inner, A, a0, w); break;
+        case 3: aug_blur_column<3>(src, dst, base, inner, A, a0, w); break;
+        case 4: aug_blur_column<4>(src, dst, base, inner, A, a0, w); break;
+        case 5: aug_blur_column<5>(src, dst, base, inner, A, a0, w); break;
+        case 6: aug_blur_column<6>(src, dst, base, inner, A, a0, w); break;
+        case 7: aug_blur_column<7>(src, dst, base, inner, A, a0, w); break;
+        default: aug_blur_column<8>(src, dst, base, inner, A, a0, w); break;
+    }
+}
+
+// the pass along axis 2: a workgroup stages nr whole rows (nr S2 <= AUG_BLUR_LDS contiguous floats) in LDS and writes them
+// back blurred, so src may be dst.  grid (ceil(rows / nr), B), rows = C S0 S1
+__global__ void __launch_bounds__(256)
+aug_blur_rows_kernel(const int* __restrict__ table, const float* src, float* dst, long rows, int S2, int nr) {
+#pragma clang fp contract(off)
+    __shared__ float g[2 * AUG_BLUR_MAXR + 1], w[2 * AUG_BLUR_MAXR + 1];
+    __shared__ float buf[AUG_BLUR_LDS];
+    const int s = blockIdx.y;
+    const int* row = table + (long)s * AUG_IROW;
+    if (!(row[0] & AUG_I_BLUR)) return;
+    const int R = aug_blur_weights(__int_as_float(row[4]), g, w);
+    const long r0 = (long)blockIdx.x * nr;
+    const int cnt = (int)(rows - r0 < nr ? rows - r0 : nr) * S2;
+    const long base = ((long)s * rows + r0) * S2;
+    for (int e = threadIdx.x; e < cnt; e += 256) buf[e] = src[base + e];
+    __syncthreads();
+    for (int e = threadIdx.x; e < cnt; e += 256) {
+        const int r = e / S2, i = e - r * S2;
+        float acc = 0.f;
+        for (int k = -R; k <= R; ++k) acc = acc + w[k + R] * buf[r * S2 + min(max(i + k, 0), S2 - 1)];
+        dst[base + e] = acc;
+    }
+}
+
+// noise and brightness in place, and the (min, max, fp64 sum) of what they leave, per workgroup, for contrast and gamma.
+// One thread per group of 8 consecutive voxels of a channel: one Philox block, four Box-Muller pairs.
+// grid (ceil(V / AUG_TILE), C, B); part_sum / part_min / part_max: [B][C][gridDim.x]
+__global__ void __launch_bounds__(256)
+aug_intensity_point_kernel(UnetrAugDesc d, const int* __restrict__ table, float* __restrict__ x, double* __restrict__ part_sum,
+                           float* __restrict__ part_min, float* __restrict__ part_max) {
+#pragma clang fp contract(off)
+    const int s = blockIdx.z, c = blockIdx.y;
+    const int* row = table + (long)s * AUG_IROW;
+    const int flags = row[0];
+    if (!(flags & (AUG_I_NOISE | AUG_I_BRIGHT | AUG_I_CONTRAST | AUG_I_GAMMA))) return;
+    const long V = (long)d.S0 * d.S1 * d.S2;
+    const long grp = (long)blockIdx.x * 256 + threadIdx.x;
+    const long v0 = grp * AUG_VPT;
+    const int cnt = V - v0 >= AUG_VPT ? AUG_VPT : (V > v0 ? (int)(V - v0) : 0);
+    float* xp = x + ((long)s * d.C + c) * V + v0;
+    const bool vec = cnt == AUG_VPT && ((size_t)xp & 15) == 0;
+    float val[AUG_VPT];
+    if (vec) {
+        const float4 lo = ((const float4*)xp)[0], hi = ((const float4*)xp)[1];
+        val[0] = lo.x; val[1] = lo.y; val[2] = lo.z; val[3] = lo.w; val[4] = hi.x; val[5] = hi.y; val[6] = hi.z; val[7] = hi.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < AUG_VPT; ++j) val[j] = j < cnt ? xp[j] : 0.f;
+    }
+    if ((flags & AUG_I_NOISE) && cnt > 0) {
+        const float sd = __int_as_float(row[1]);
+        Ph4 ctr;
+        ctr.v[0] = (unsigned long long)(unsigned)row[8] | (unsigned long long)(unsigned)row[9] << 32;
+        ctr.v[1] = (unsigned long long)s; ctr.v[2] = (unsigned long long)(AUG_NOISE_BLOCK + c); ctr.v[3] = 1ull + (unsigned long long)grp;
+        const Ph4 r4 = philox4x64(ctr, d.seed, 0ull);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const unsigned a = (unsigned)(r4.v[i] & 0xffffffffull), b = (unsigned)(r4.v[i] >> 32);
+            const float u1 = ((float)(a >> 8) + 0.5f) * 0x1p-24f, u2 = ((float)(b >> 8) + 0.5f) * 0x1p-24f;
+            const float r = sqrtf(-2.0f * logf(u1)), t = 6.283185307179586f * u2;
+            val[2 * i] = val[2 * i] + sd * (r * cosf(t));
+            val[2 * i + 1] = val[2 * i + 1] + sd * (r * sinf(t));
+        }
+    }
+    if (flags & AUG_I_BRIGHT) {
+        const float f = __int_as_float(row[5]);
+#pragma unroll
+        for (int j = 0; j < AUG_VPT; ++j) val[j] = val[j] * f;
+    }
+    if (flags & (AUG_I_NOISE | AUG_I_BRIGHT)) {
+        if (vec) {
+            ((float4*)xp)[0] = make_float4(val[0], val[1], val[2], val[3]);
+            ((float4*)xp)[1] = make_float4(val[4], val[5], val[6], val[7]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < AUG_VPT; ++j) if (j < cnt) xp[j] = val[j];
+        }
+    }
+    if (flags & (AUG_I_CONTRAST | AUG_I_GAMMA)) {
+        __shared__ double rs[4];
+        __shared__ float rmn[4], rmx[4];
+        double sum = 0.0;
+        float mn = INFINITY, mx = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < AUG_VPT; ++j)
+            if (j < cnt) { sum += (double)val[j]; mn = fminf(mn, val[j]); mx = fmaxf(mx, val[j]); }
+        sum = wave_sum_d(sum);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o, 64)); mx = fmaxf(mx, __shfl_xor(mx, o, 64)); }
+        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+        if (lane == 0) { rs[wv] = sum; rmn[wv] = mn; rmx[wv] = mx; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const long p = ((long)s * d.C + c) * gridDim.x + blockIdx.x;
+            part_sum[p] = ((rs[0] + rs[1]) + rs[2]) + rs[3];
+            part_min[p] = fminf(fminf(rmn[0], rmn[1]), fminf(rmn[2], rmn[3]));
+            part_max[p] = fmaxf(fmaxf(rmx[0], rmx[1]), fmaxf(rmx[2], rmx[3]));
+        }
+    }
+}
+
+// contrast about the channel mean, clamped to the channel's range, then gamma on the range contrast leaves: contrast is a
+// monotone map and a clamp, so that range is the map of (mn, mx) and needs no second reduction.  Every workgroup of a
+// (sample, channel) reduces the nblk partials in the same fixed order, then takes one tile of AUG_TONE_TILE voxels (the
+// normalize pass's 64 looping workgroups per channel are too few waves to hide powf behind the loads: DESIGN.md section 12).
+// grid (ceil(V / AUG_TONE_TILE), C, B)
+__device__ __forceinline__ float aug_contrast(float v, float mean, float f, float mn, float mx) {
+#pragma clang fp contract(off)
+    return fminf(fmaxf((v - mean) * f + mean, mn), mx);
+}
+
+__global__ void __launch_bounds__(256)
+aug_intensity_tone_kernel(UnetrAugDesc d, const int* __restrict__ table, float* __restrict__ x, const double* __restrict__ part_sum,
+                          const float* __restrict__ part_min, const float* __restrict__ part_max, int nblk) {
+#pragma clang fp contract(off)
+    __shared__ double rs[256];
+    __shared__ float rmn[256], rmx[256];
+    const int s = blockIdx.z, c = blockIdx.y;
+    const int* row = table + (long)s * AUG_IROW;
+    const int flags = row[0];
+    if (!(flags & (AUG_I_CONTRAST | AUG_I_GAMMA))) return;
+    const long V = (long)d.S0 * d.S1 * d.S2;
+    const long p0 = ((long)s * d.C + c) * nblk;
+    double sum = 0.0;
+    float mn = INFINITY, mx = -INFINITY;
+    for (int i = threadIdx.x; i < nblk; i += 256) {
+        sum += part_sum[p0 + i]; mn = fminf(mn, part_min[p0 + i]); mx = fmaxf(mx, part_max[p0 + i]);
+    }
+    rs[threadIdx.x] = sum; rmn[threadIdx.x] = mn; rmx[threadIdx.x] = mx;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (threadIdx.x < w) {
+            rs[threadIdx.x] += rs[threadIdx.x + w];
+            rmn[threadIdx.x] = fminf(rmn[threadIdx.x], rmn[threadIdx.x + w]);
+            rmx[threadIdx.x] = fmaxf(rmx[threadIdx.x], rmx[threadIdx.x + w]);
+        }
+        __syncthreads();
+    }
+    const float mean = (float)(rs[0] / (double)V);
+    mn = rmn[0]; mx = rmx[0];
+    const bool contrast = flags & AUG_I_CONTRAST, gam = flags & AUG_I_GAMMA;
+    const float f = __int_as_float(row[6]), gamma = __int_as_float(row[7]);
+    const float gmn = contrast ? aug_contrast(mn, mean, f, mn, mx) : mn, gmx = contrast ? aug_contrast(mx, mean, f, mn, mx) : mx;
+    const float rng = gmx - gmn, den = rng + 1e-7f;
+    float* xp = x + ((long)s * d.C + c) * V;
+    const bool aligned = ((size_t)xp & 15) == 0;
+    const long tile0 = (long)blockIdx.x * AUG_TONE_TILE;
+#pragma unroll
+    for (int i = 0; i < AUG_TONE_TILE / 1024; ++i) {          // 16 bytes per thread and round where the address allows
+        const long v = tile0 + ((long)i * 256 + threadIdx.x) * 4;
+        if (v >= V) continue;
+        float q[4];
+        const int cnt = V - v >= 4 ? 4 : (int)(V - v);
+        const bool vec = aligned && cnt == 4;
+        if (vec) { const float4 t = *(const float4*)(xp + v); q[0] = t.x; q[1] = t.y; q[2] = t.z; q[3] = t.w; }
+        else
+#pragma unroll
+            for (int j = 0; j < 4; ++j) q[j] = j < cnt ? xp[v + j] : 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (contrast) q[j] = aug_contrast(q[j], mean, f, mn, mx);
+            if (gam) q[j] = powf((q[j] - gmn) / den, gamma) * rng + gmn;
+        }
+        if (vec) *(float4*)(xp + v) = make_float4(q[0], q[1], q[2], q[3]);
+        else
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (j < cnt) xp[v + j] = q[j];
+    }
+}
+
 bool aug_desc_ok(const UnetrAugDesc* d) {
     if (!d || d->B <= 0 || d->num_samples <= 0 || d->B % d->num_samples) return false;
     if (d->C <= 0 || d->C > AUG_MAXC || d->L <= 0 || d->L > AUG_MAXC) return false;
@@ -526,6 +811,22 @@ bool aug_affine_desc_ok(const UnetrAugAffineDesc* a) {
     if (!a || !(a->prob >= 0.0 && a->prob <= 1.0)) return false;
     for (int i = 0; i < 3; ++i) if (!(a->rotate[i] >= 0.0 && isfinite(a->rotate[i]))) return false;
     return a->zoom_lo > 0.0 && a->zoom_lo <= a->zoom_hi && isfinite(a->zoom_hi);
+}
+
+bool aug_intensity_desc_ok(const UnetrAugIntensityDesc* it) {
+    if (!it) return false;
+    for (int j = 0; j < 5; ++j) {
+        if (!(it->prob[j] >= 0.0 && it->prob[j] <= 1.0)) return false;
+        if (!(isfinite(it->lo[j]) && isfinite(it->hi[j]) && it->lo[j] <= it->hi[j])) return false;
+        if (j == 0 ? it->lo[j] < 0.0 : it->lo[j] <= 0.0) return false;
+    }
+    return it->hi[1] <= 2.0;
+}
+
+// workspace of the intensity passes: [blur ping-pong, B C V floats][fp64 sums, B C nblk][mins][maxs]
+inline size_t aug_intensity_tmp_bytes(const UnetrAugDesc* d) {
+    const size_t n = (size_t)d->B * d->C * d->S0 * d->S1 * d->S2 * sizeof(float);
+    return (n + 15) / 16 * 16;
 }
 
 }  // namespace
@@ -636,5 +937,43 @@ extern "C" int unetr_aug_gather_affine(const UnetrAugDesc* d, const long long* v
         hipLaunchKernelGGL((aug_gather_kernel<false, true>), dim3(nblk, d->B), dim3(256), 0, st, *d, vols, nvol, params, affine, x,
                            y, (double*)nullptr);
     }
+    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+}
+
+extern "C" int unetr_aug_intensity_sample(const UnetrAugDesc* d, const UnetrAugIntensityDesc* it, const long long* state, int* table,
+                                          void* stream) {
+    if (!aug_desc_ok(d) || !aug_intensity_desc_ok(it) || !state || !table) return UNETR_ERR_ARG;
+    hipLaunchKernelGGL(aug_intensity_sample_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *d, *it, state, table);
+    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+}
+
+extern "C" size_t unetr_aug_intensity_ws_bytes(const UnetrAugDesc* d) {
+    if (!aug_desc_ok(d)) return 0;
+    const long V = (long)d->S0 * d->S1 * d->S2;
+    return aug_intensity_tmp_bytes(d) + (size_t)d->B * d->C * cdiv(V, AUG_TILE) * (sizeof(double) + 2 * sizeof(float));
+}
+
+extern "C" int unetr_aug_intensity_apply(const UnetrAugDesc* d, const int* table, float* x, void* ws, size_t ws_bytes, void* stream) {
+    if (!aug_desc_ok(d) || !table || !x) return UNETR_ERR_ARG;
+    if (!ws || ((size_t)ws & 15) || ws_bytes < unetr_aug_intensity_ws_bytes(d)) return UNETR_ERR_WORKSPACE;
+    const long V = (long)d->S0 * d->S1 * d->S2;
+    const int nblk = cdiv(V, AUG_TILE);
+    const size_t parts = (size_t)d->B * d->C * nblk;
+    float* tmp = (float*)ws;
+    double* psum = (double*)((char*)ws + aug_intensity_tmp_bytes(d));
+    float* pmin = (float*)(psum + parts);
+    float* pmax = pmin + parts;
+    hipStream_t st = (hipStream_t)stream;
+    const long plane = (long)d->S1 * d->S2, rows = (long)d->C * d->S0 * d->S1;
+    const int nr = std::max(1, AUG_BLUR_LDS / d->S2);
+    // blur: axis 0 x -> tmp, axis 1 tmp -> x, axis 2 in place through LDS; then the two elementwise passes
+    hipLaunchKernelGGL(aug_blur_strided_kernel, dim3(cdiv(d->C * plane, 256), cdiv(d->S0, AUG_BLUR_T), d->B), dim3(256), 0, st, table,
+                       0, (const float*)x, tmp, (long)d->C * V, (long)d->C, d->S0, plane);
+    hipLaunchKernelGGL(aug_blur_strided_kernel, dim3(cdiv((long)d->C * d->S0 * d->S2, 256), cdiv(d->S1, AUG_BLUR_T), d->B), dim3(256), 0,
+                       st, table, 1, (const float*)tmp, x, (long)d->C * V, (long)d->C * d->S0, d->S1, (long)d->S2);
+    hipLaunchKernelGGL(aug_blur_rows_kernel, dim3(cdiv(rows, nr), d->B), dim3(256), 0, st, table, (const float*)x, x, rows, d->S2, nr);
+    hipLaunchKernelGGL(aug_intensity_point_kernel, dim3(nblk, d->C, d->B), dim3(256), 0, st, *d, table, x, psum, pmin, pmax);
+    hipLaunchKernelGGL(aug_intensity_tone_kernel, dim3(cdiv(V, AUG_TONE_TILE), d->C, d->B), dim3(256), 0, st, *d, table, x, (const double*)psum,
+                       (const float*)pmin, (const float*)pmax, nblk);
     return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
 }

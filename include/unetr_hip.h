@@ -579,6 +579,22 @@ int unetr_aug_sample_affine(const UnetrAugDesc* d, const UnetrAugAffineDesc* a, 
 size_t unetr_aug_gather_affine_ws_bytes(const UnetrAugDesc* d);
 int unetr_aug_gather_affine(const UnetrAugDesc* d, const long long* vols, int nvol, const int* params, const float* affine,
                             float* x, float* y, void* ws, size_t ws_bytes, void* stream);
+/* Intensity augmentation on x after the gather (this project's own semantics, DESIGN.md section 12: nnU-Net's choice of
+ * operations, MONAI's formulas, no bit parity with either): Gaussian blur, Gaussian noise, brightness, contrast, gamma, in that
+ * order, each with its own probability per sample; y is not touched.  unetr_aug_intensity_sample, launched BEFORE
+ * unetr_aug_sample (it reads state[0] and writes no state), draws from Philox blocks 5..7 of each sample the DEVICE table
+ * [B][16] (int32, floats as their bits: flag bits noise 1 / blur 2 / brightness 4 / contrast 8 / gamma 16, noise std, blur sigma
+ * of axis 0, 1, 2, brightness factor, contrast factor, gamma, low and high word of the call counter, six zeros; an unflagged
+ * operation holds std 0, sigma 0, factor 1, gamma 1).  unetr_aug_intensity_apply runs the passes from such a table: launches
+ * only, fixed grids, ws of unetr_aug_intensity_ws_bytes (16-byte aligned), no float atomics.  Statistics are per (sample,
+ * channel) over the crop; sigma <= 2.  prob / lo / hi below are indexed noise std, blur sigma, brightness, contrast, gamma. */
+typedef struct {
+    double prob[5], lo[5], hi[5];
+} UnetrAugIntensityDesc;
+int unetr_aug_intensity_sample(const UnetrAugDesc* d, const UnetrAugIntensityDesc* it, const long long* state, int* table,
+                               void* stream);
+size_t unetr_aug_intensity_ws_bytes(const UnetrAugDesc* d);
+int unetr_aug_intensity_apply(const UnetrAugDesc* d, const int* table, float* x, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- per-volume resampling and reorientation (csrc/preprocess.hip; unetr_segmentation_3d.py:326-331) ----
  * Spacingd(mode=("bilinear", "nearest")) -> Orientationd [-> ConvertToMultiChannelBasedOnBratsClassesd] as one gather: output voxel

@@ -1,6 +1,6 @@
 """GPU time of one RandCropAugment call (sampler + gather [+ normalize]).
 
-    python tools/bench_augment.py [--iters 50] [--cpu]
+    python tools/bench_augment.py [--iters 50] [--cpu] [--no-intensity | --trace-intensity]
 
 Prints ONE JSON line: per case the median of --iters warmed calls timed with HIP events, the same with every sample rotated
 (rot90_prob=1) and unrotated (rot90_prob=0), the bytes the call must move and the implied rate.  With --cpu also the wall time
@@ -11,6 +11,11 @@ the bytes that gather must move at the least -- the distinct source voxels under
 plain call and the share of the 4.3 ms training step.  Cases:
   ct: 1 item x 4 samples of 96^3 from a 1-channel 320x320x200 volume, 14 classes, scale + foreground crop, all transforms
   mr: 1 item x 4 samples of 128^3 from a 4-channel 240x240x155 volume, 3 label channels, all transforms + normalize
+Intensity augmentation (unless --no-intensity): the same call with intensity=IntensityAugment.nnunet() ("intensity_nnunet_us")
+and with every probability 1 ("intensity_all_us"); for the latter the bytes its five passes must move on top of the plain call
+(intensity_pass_bytes), the floor of the whole call at 8 TB/s, and the time of an eager-torch restatement of the five
+operations alone on the same x (F.conv3d blur, torch.randn noise, amin / amax / mean, pow; applied to every sample, since eager
+code cannot branch per sample without a host sync), to be compared with intensity_all_us - us.
 """
 import argparse
 import importlib
@@ -84,9 +89,42 @@ def affine_floor_bytes(aug, cache, C, L, normalize):
     return src + nvox * (C + L) * 4 + (2 * nvox * C * 4 if normalize else 0)
 
 
+def intensity_pass_bytes(nvox_c):
+    """bytes the intensity passes move for nvox_c = B * C * V float32 voxels with every operation flagged: three blur passes,
+    noise / brightness / statistics, contrast / gamma, each one read and one write"""
+    return 4 * nvox_c * 2 * 5
+
+
+def torch_intensity(x, sigma=0.75, std=0.05, brightness=1.1, contrast=1.1, gamma=1.2):
+    """the five operations in eager torch on every sample of x [B, C, S, S, S] (mid-range values); returns the result"""
+    import torch.nn.functional as F
+    R = int(max(4.0 * sigma, 0.5) + 0.5)
+    k = torch.arange(-R, R + 1, device=x.device, dtype=torch.float32)
+    w = torch.exp(-(k * k) / (2.0 * sigma * sigma))
+    w = w / w.sum()
+    v = x.reshape(-1, 1, *x.shape[2:])
+    for a in range(3):
+        shape, pad = [1, 1, 1, 1, 1], [0] * 6
+        shape[2 + a] = 2 * R + 1
+        pad[2 * (2 - a)] = pad[2 * (2 - a) + 1] = R
+        v = F.conv3d(F.pad(v, pad, mode="replicate"), w.view(shape))
+    v = v.reshape(x.shape)
+    v = v + std * torch.randn_like(v)
+    v = v * brightness
+    dims = (2, 3, 4)
+    mn, mx, mean = v.amin(dims, keepdim=True), v.amax(dims, keepdim=True), v.mean(dims, keepdim=True)
+    v = torch.minimum(torch.maximum((v - mean) * contrast + mean, mn), mx)
+    mn, mx = v.amin(dims, keepdim=True), v.amax(dims, keepdim=True)
+    rng = mx - mn
+    return ((v - mn) / (rng + 1e-7)).pow(gamma) * rng + mn
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--no-intensity", action="store_true", help="skip the intensity cases (A/B runs of the plain call)")
+    ap.add_argument("--trace-intensity", action="store_true",
+                    help="only the every-probability-1 call of each case: the run to put under rocprofv3 --kernel-trace --stats")
     ap.add_argument("--cpu", action="store_true", help="also time the CPU restatement once per case")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -113,6 +151,12 @@ def main():
         B = c["aug"]["num_samples"]
         x = torch.empty(B, c["C"], S, S, S, device=dev)
         y = torch.empty(B, c["L"], S, S, S, device=dev)
+        if args.trace_intensity:
+            full = pkg.IntensityAugment(noise_prob=1.0, blur_prob=1.0, brightness_prob=1.0, contrast_prob=1.0, gamma_prob=1.0)
+            aug = pkg.RandCropAugment(cache, pos=1, neg=1, flip_prob=(0.1, 0.1, 0.1), rot90_prob=0.1, max_k=3, shift_offsets=0.1,
+                                      shift_prob=0.5, seed=1, intensity=full, **c["aug"])
+            out[name] = {"intensity_all_us": round(time_calls(lambda: aug(x, y), args.iters), 2)}
+            continue
         for label, rot in (("us", 0.1), ("us_rot0", 0.0), ("us_rot1", 1.0)):
             aug = pkg.RandCropAugment(cache, pos=1, neg=1, flip_prob=(0.1, 0.1, 0.1), rot90_prob=rot, max_k=3, shift_offsets=0.1,
                                       shift_prob=0.5, seed=1, **c["aug"])
@@ -132,6 +176,23 @@ def main():
         res["affine_GBps"] = round(floor / (res["affine_us"] * 1e-6) / 1e9, 1)
         res["affine_over_plain"] = round(res["affine_us"] / res["us"], 2)
         res["affine_share_of_4.3ms_step"] = round(res["affine_us"] / 4300.0, 4)
+        if not args.no_intensity:
+            full = pkg.IntensityAugment(noise_prob=1.0, blur_prob=1.0, brightness_prob=1.0, contrast_prob=1.0, gamma_prob=1.0)
+            for label, it in (("intensity_nnunet_us", pkg.IntensityAugment.nnunet()), ("intensity_all_us", full)):
+                aug = pkg.RandCropAugment(cache, pos=1, neg=1, flip_prob=(0.1, 0.1, 0.1), rot90_prob=0.1, max_k=3, shift_offsets=0.1,
+                                          shift_prob=0.5, seed=1, intensity=it, **c["aug"])
+                res[label] = round(time_calls(lambda: aug(x, y), args.iters), 2)
+            extra = intensity_pass_bytes(nvox * c["C"])
+            res["intensity_pass_bytes"] = extra
+            res["intensity_all_floor_us_at_8TBps"] = round((moved + extra) / 8e12 * 1e6, 2)
+            res["intensity_all_minus_plain_us"] = round(res["intensity_all_us"] - res["us"], 2)
+            res["intensity_passes_GBps"] = round(extra / (res["intensity_all_minus_plain_us"] * 1e-6) / 1e9, 1)
+            res["intensity_all_share_of_4.3ms_step"] = round(res["intensity_all_us"] / 4300.0, 4)
+            try:
+                res["torch_intensity_us"] = round(time_calls(lambda: torch_intensity(x), max(args.iters // 5, 5)), 2)
+                res["torch_over_hip_passes"] = round(res["torch_intensity_us"] / res["intensity_all_minus_plain_us"], 1)
+            except RuntimeError as e:                          # an eager comparison that cannot run is reported, not hidden
+                res["torch_intensity_error"] = str(e).splitlines()[0][:200]
         if args.cpu:
             import augment_ref as R
             p = aug.params.cpu()
