@@ -108,6 +108,14 @@ class RestoreGeom(ctypes.Structure):      # unetr_restore_geom, passed by value
     _fields_ = [("m", c_double * 12), ("full", c_int * 3), ("origin", c_int * 3), ("crop", c_int * 3)]
 
 
+class SegLossDesc(ctypes.Structure):      # unetr_segloss_desc
+    _fields_ = [("B", c_int), ("C", c_int), ("V", c_long), ("multilabel", c_int), ("region", c_int), ("voxel", c_int),
+                ("include_background", c_int), ("squared_pred", c_int), ("batch", c_int), ("w_type", c_int),
+                ("has_ignore", c_int), ("ignore_index", c_int),
+                ("smooth_nr", c_float), ("smooth_dr", c_float), ("alpha", c_float), ("beta", c_float), ("gamma", c_float),
+                ("lambda_region", c_float), ("lambda_voxel", c_float), ("class_weight", c_void_p)]
+
+
 SW_MAX_BATCH = 16                      # = UNETR_SW_MAX_BATCH
 SW_ROW_INTS = 4 + 4 * SW_MAX_BATCH     # = UNETR_SW_ROW_INTS
 
@@ -192,6 +200,8 @@ _SIGNATURES = {
     "unetr_outconv_in_bwd": [P, P, c_long, P, P, c_long, P, P, P, c_long, P, P, P, c_int, c_long, c_int, c_int, P, c_size_t, c_int, P],
     "unetr_dicece_fwd": [P, P, c_int, c_int, c_long, c_int, c_float, c_float, P, P, P, c_size_t, P],
     "unetr_dicece_bwd": [P, P, P, P, P, c_int, c_int, c_long, c_int, P],
+    "unetr_segloss_fwd": [ctypes.POINTER(SegLossDesc), P, P, P, P, P, c_size_t, P],
+    "unetr_segloss_bwd": [ctypes.POINTER(SegLossDesc), P, P, P, P, P, P],
     "unetr_sw_accumulate": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
     "unetr_sw_finalize": [P, P, c_int, c_int, c_long, P],
     "unetr_dice_counts": [P, P, c_int, c_int, c_long, c_int, P, P, c_size_t, P],
@@ -227,7 +237,7 @@ _SIGNATURES = {
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + ("unetr_conv3_packed_bytes", "unetr_conv3_packed_1x1_bytes", "unetr_ranking_workspace_floats",
                                             "unetr_conv3_wgrad_rows", "unetr_tconv2_wgrad_rows", "unetr_outconv_in_bwd_rows", "unetr_hausdorff_workspace_bytes",
                                             "unetr_aug_index_ws_ints", "unetr_aug_gather_ws_bytes", "unetr_aug_gather_affine_ws_bytes", "unetr_ccl_workspace_bytes",
-                                            "unetr_surface_metrics_workspace_bytes", "unetr_aug_intensity_ws_bytes")
+                                            "unetr_surface_metrics_workspace_bytes", "unetr_aug_intensity_ws_bytes", "unetr_segloss_workspace_bytes")
 
 _lib = None
 
@@ -277,6 +287,8 @@ def load():
     lib.unetr_aug_gather_affine_ws_bytes.restype = c_size_t
     lib.unetr_aug_intensity_ws_bytes.argtypes = [ctypes.POINTER(AugDesc)]
     lib.unetr_aug_intensity_ws_bytes.restype = c_size_t
+    lib.unetr_segloss_workspace_bytes.argtypes = [ctypes.POINTER(SegLossDesc)]
+    lib.unetr_segloss_workspace_bytes.restype = c_size_t
     _lib = lib
     return lib
 

@@ -1616,3 +1616,52 @@ class DiceCEFn(torch.autograd.Function):
         call("unetr_dicece_bwd", logits.data_ptr(), label.data_ptr(), coef.data_ptr(), dloss.data_ptr(), dlogits.data_ptr(), B, C, V,
              ml, _stream())
         return dlogits, None, None, None, None, None
+
+
+class SegLossFn(torch.autograd.Function):
+    """The segmentation loss family of csrc/seg_loss.hip -> (loss, region term, voxel term) as a 3-vector.  `cfg` holds the fields of
+    unetr_segloss_desc that do not depend on the input (seg_losses.SegLoss builds it); `class_weight` is a device tensor [C] or None."""
+
+    @staticmethod
+    def _desc(cfg, B, C, V, class_weight):
+        d = _capi.SegLossDesc(B=B, C=C, V=V, **cfg)
+        d.class_weight = class_weight.data_ptr() if class_weight is not None else None
+        return d
+
+    @staticmethod
+    def forward(ctx, logits, label, cfg, class_weight=None, scalar=False):
+        """scalar=True: returns the 0-dim loss itself, as DiceCEFn does"""
+        _require_gpu(logits)
+        logits = logits.contiguous()
+        label = label.contiguous().to(torch.float32)
+        B, C = logits.shape[0], logits.shape[1]
+        V = logits.numel() // (B * C)
+        if cfg["multilabel"] and label.numel() != B * C * V:
+            raise ValueError(f"multi-label target must be [B,C,*spatial] like the logits, got {tuple(label.shape)}")
+        if not cfg["multilabel"] and label.numel() != B * V:
+            raise ValueError(f"label must be [B,1,*spatial] class indices, got {tuple(label.shape)}")
+        if not cfg["include_background"] and C == 1:
+            raise ValueError("include_background=False needs more than one channel")
+        if class_weight is not None and class_weight.numel() != C:
+            raise ValueError(f"class_weight has {class_weight.numel()} entries for {C} channels")
+        d = SegLossFn._desc(cfg, B, C, V, class_weight)
+        out = torch.empty(3, dtype=torch.float32, device=logits.device)
+        coef = torch.empty(B * C * 3 + 1, dtype=torch.float32, device=logits.device)
+        ws = workspace(logits.device)
+        call("unetr_segloss_fwd", ctypes.byref(d), logits.data_ptr(), label.data_ptr(), out.data_ptr(), coef.data_ptr(), ws.data_ptr(),
+             ws.numel() * 4, _stream())
+        ctx.save_for_backward(logits, label, coef)
+        ctx.desc, ctx.class_weight = d, class_weight            # (the tensor is kept alive with the pointer the descriptor holds)
+        ctx.scalar = bool(scalar)
+        return out[0] if scalar else out
+
+    @staticmethod
+    def backward(ctx, dout):
+        logits, label, coef = ctx.saved_tensors
+        # only out[0] is differentiable; out[1], out[2] are reporting copies
+        dloss = dout.reshape(1) if ctx.scalar else dout[0:1]
+        dloss = dloss.contiguous()
+        dlogits = torch.empty_like(logits)
+        call("unetr_segloss_bwd", ctypes.byref(ctx.desc), logits.data_ptr(), label.data_ptr(), coef.data_ptr(), dloss.data_ptr(),
+             dlogits.data_ptr(), _stream())
+        return dlogits, None, None, None, None

@@ -422,6 +422,46 @@ int unetr_dicece_fwd(const float* logits, const float* label, int B, int C, long
 int unetr_dicece_bwd(const float* logits, const float* label, const float* coef, const float* dloss,
                      float* dlogits, int B, int C, long V, int sigmoid_multilabel, void* stream);
 
+/* ---- segmentation loss family: loss = lambda_region * R + lambda_voxel * X (csrc/seg_loss.hip) -------------
+ * logits [B,C,V] fp32, 1 <= C <= 16 (else UNETR_ERR_UNSUPPORTED).  multilabel = 0: label [B,V] float class ids, p = softmax over
+ * the channels, y = one_hot(label); multilabel = 1: label [B,C,V] float mask, p = sigmoid.  Per (b,c): I = sum p*y, P = sum p,
+ * G = sum y (p^2 / y^2 with squared_pred; dice and jaccard only).  The region term runs over all channels, or 1..C-1 with
+ * include_background = 0 (C >= 2), as a mean over (b, channel); batch = 1 pools I, P, G over b first.
+ *   DICE     f = 1 - (2I + nr) / (G + P + dr)
+ *   JACCARD  f = 1 - (2I + nr) / (2(G + P - I) + dr)
+ *   TVERSKY  f = 1 - (I + nr) / (I + alpha (P - I) + beta (G - I) + dr)
+ *   GDL      per item f = 1 - (2 sum_c w_c I_c + nr) / (sum_c w_c (G_c + P_c) + dr), w_c = 1/G_c^2, 1/G_c or 1 (w_type); a channel
+ *            with G_c = 0 takes the item's largest finite weight (0 when there is none); w is a constant of the gradient
+ * The voxel term: CE = softmax cross entropy over all channels against the label (multilabel: against argmax_c(mask), first
+ * maximum), with class_weight[C] (device pointer or NULL; one-hot mode only) by torch's rule sum w_y (-log p_y) / sum w_y.  FOCAL =
+ * sigmoid focal loss of the raw logits z against the target t, exp(gamma * logsigmoid(-z (2t - 1))) * bce(z, t) * class_weight[c],
+ * as the plain mean over (b, included channels, v).  has_ignore (one-hot mode only): a voxel whose label equals ignore_index adds
+ * to no sum, the voxel means divide by the count of the others (at least one per call), and its gradient is zero.
+ * unetr_segloss_fwd: out[0] = loss, out[1] = R, out[2] = X; coef [B*C*3 + 1] floats kept for backward: per (b,c) the numbers
+ *   (a, b, k) of d(lambda_region R)/dp_c(v) = a y + b p + k, then the factor of the voxel term's gradient.  ws: 16-byte aligned,
+ *   unetr_segloss_workspace_bytes (0 for a descriptor that is refused).  Fixed-order partial sums, finalized by one block in
+ *   double: reproducible run to run, no float atomics.
+ * unetr_segloss_bwd: dlogits = *dloss (device scalar; NULL = 1) * dloss/dlogits, every element written.
+ * Launches only: no allocation, no host synchronisation.  (Additions: no existing signature moved, UNETR_ABI_VERSION stays.) */
+enum { UNETR_SEGLOSS_REGION_NONE = 0, UNETR_SEGLOSS_REGION_DICE = 1, UNETR_SEGLOSS_REGION_JACCARD = 2, UNETR_SEGLOSS_REGION_TVERSKY = 3,
+       UNETR_SEGLOSS_REGION_GDL = 4 };
+enum { UNETR_SEGLOSS_VOXEL_NONE = 0, UNETR_SEGLOSS_VOXEL_CE = 1, UNETR_SEGLOSS_VOXEL_FOCAL = 2 };
+enum { UNETR_SEGLOSS_W_SQUARE = 0, UNETR_SEGLOSS_W_SIMPLE = 1, UNETR_SEGLOSS_W_UNIFORM = 2 };
+typedef struct unetr_segloss_desc {
+    int B, C;
+    long V;
+    int multilabel, region, voxel;
+    int include_background, squared_pred, batch, w_type;
+    int has_ignore, ignore_index;
+    float smooth_nr, smooth_dr, alpha, beta, gamma, lambda_region, lambda_voxel;
+    const float* class_weight;
+} unetr_segloss_desc;
+size_t unetr_segloss_workspace_bytes(const unetr_segloss_desc* d);
+int unetr_segloss_fwd(const unetr_segloss_desc* d, const float* logits, const float* label, float* out, float* coef,
+                      void* ws, size_t ws_bytes, void* stream);
+int unetr_segloss_bwd(const unetr_segloss_desc* d, const float* logits, const float* label, const float* coef,
+                      const float* dloss, float* dlogits, void* stream);
+
 /* ---- validation side (unetr_segmentation_3d.py:103-132) -------------------------------------------------
  * unetr_sw_accumulate / unetr_sw_finalize: the blending step of monai.inferers.sliding_window_inference (MONAI 0.6.0,
  * called at :110): out[c, z0+z, y0+y, x0+x] += w * seg[c,z,y,x], count[...] += w for ONE window of ONE volume
