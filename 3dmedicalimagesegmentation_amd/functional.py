@@ -6,6 +6,7 @@ these functions must live on a ROCm device -- there is no CPU or eager-PyTorch f
 
 Layouts: token matrices [B*L, H]; feature maps channels-last [B, D, H, W, C] (possibly row-pitched views).
 """
+import collections
 import ctypes
 import os
 
@@ -114,6 +115,26 @@ def _as_act(t, prec):
     """tensor in the activation storage type of `prec` (a torch cast: only on the rare generic-fallback boundaries)"""
     dt = act_dtype(prec)
     return t if t.dtype == dt else t.to(dt)
+
+
+# The generic GEMM families (im2col conv, transposed conv, unetr_gemm) read and write fp32 storage only.  Where a bf16-stored tensor
+# meets them -- shapes the dedicated kernels decline -- these two casts are the boundary: exact on the way in, the activation
+# storage's own rounding on the way back.
+def _f32_rows(t, ld, c):
+    """(fp32 rows, their pitch) of the first `c` channels of a tensor with row pitch `ld`: the tensor itself when it is fp32"""
+    if t.dtype == torch.float32:
+        return t, ld
+    if ld != c:
+        t = t[..., :c]
+    return t.float().contiguous(), c
+
+
+def _act_rows(t32, prec, out=None):
+    """the way back: fp32 rows into the activation storage of `prec` -- a new tensor, or `out` (any row pitch)"""
+    if out is None:
+        return _as_act(t32, prec)
+    out.copy_(t32)
+    return out
 
 
 def _require_gpu(t, act=False, ids=False):
@@ -541,23 +562,23 @@ def conv3_fused(x, ldx, w, w3, dims, prec):
     cout, cin = w.shape[0], w.shape[1]
     if cout % 16 != 0:
         return None
-    dev = x.device
-    wp = conv_pack_get(w, 0, prec)
-    adt = act_dtype(prec)
-    x_f32 = int(prec == _capi.PREC_BF16 and x.dtype == torch.float32)      # the image in front of encoder1
-    c = torch.empty(B, D, H, W, cout, dtype=adt, device=dev)
-    st = torch.empty(B, cout, 2, dtype=torch.float32, device=dev)
-    wp3 = c3 = st3 = None
-    if w3 is not None:
-        wp3 = conv_pack_get(w3, 2, prec)
-        c3 = torch.empty(B, D, H, W, cout, dtype=adt, device=dev)
-        st3 = torch.empty(B, cout, 2, dtype=torch.float32, device=dev)
-    ws = workspace(dev)
+    wp, c, st, wp3, c3, st3, x_f32 = _conv3_front(x, w, w3, dims, prec, (cout, 2))
+    ws = workspace(x.device)
     rc = call_rc("unetr_conv3_fwd_fused", x.data_ptr(), ldx, wp.data_ptr(), c.data_ptr(), cout, st.data_ptr(), _p(wp3), _p(c3), cout,
                  _p(st3), IN_EPS, B, D, H, W, cin, cout, prec, x_f32, ws.data_ptr(), ws.numel() * 4, _stream())
-    if rc != 0:
-        return None
-    return c, st, c3, st3
+    return (c, st, c3, st3) if rc == 0 else None
+
+
+def _conv3_front(x, w, w3, dims, prec, stat_shape, store3=True):
+    """what conv3_fused and conv3_parts set up alike: (packed w, c, its statistics buffer [B, *stat_shape], the same three for the
+    1x1x1 conv w3 or None each, x_f32).  store3=False: the 1x1x1 output is not allocated."""
+    B, D, H, W = dims
+
+    def conv(wk, kind, store):
+        return (conv_pack_get(wk, kind, prec), torch.empty(B, D, H, W, w.shape[0], dtype=act_dtype(prec), device=x.device) if store else None,
+                torch.empty(B, *stat_shape, dtype=torch.float32, device=x.device))
+    x_f32 = int(prec == _capi.PREC_BF16 and x.dtype == torch.float32)      # the image in front of encoder1
+    return conv(w, 0, True) + (conv(w3, 2, store3) if w3 is not None else (None, None, None)) + (x_f32,)
 
 
 CONV3_MAX_ROWS = 1024        # = UNETR_CONV3_MAX_ROWS (include/unetr_hip.h)
@@ -578,35 +599,26 @@ def conv3_parts(x, ldx, w, w3, dims, prec, store3=True):
     cout, cin = w.shape[0], w.shape[1]
     if cout % 16 != 0 or cout > 128:
         return None
-    dev = x.device
-    wp = conv_pack_get(w, 0, prec)
-    adt = act_dtype(prec)
-    x_f32 = int(prec == _capi.PREC_BF16 and x.dtype == torch.float32)
-    c = torch.empty(B, D, H, W, cout, dtype=adt, device=dev)
-    part = torch.empty(B, CONV3_MAX_ROWS, 2, cout, dtype=torch.float32, device=dev)
-    wp3 = c3 = part3 = None
-    if w3 is not None:
-        wp3 = conv_pack_get(w3, 2, prec)
-        c3 = torch.empty(B, D, H, W, cout, dtype=adt, device=dev) if store3 else None
-        part3 = torch.empty(B, CONV3_MAX_ROWS, 2, cout, dtype=torch.float32, device=dev)
+    wp, c, part, wp3, c3, part3, x_f32 = _conv3_front(x, w, w3, dims, prec, (CONV3_MAX_ROWS, 2, cout), store3)
     rows = ctypes.c_int(0)
     rc = call_rc("unetr_conv3_fwd_parts", x.data_ptr(), ldx, wp.data_ptr(), c.data_ptr(), cout, part.data_ptr(), _p(wp3), _p(c3), cout,
                  _p(part3), ctypes.byref(rows), B, D, H, W, cin, cout, prec, x_f32, _stream())
-    if rc != 0:
-        return None
-    return c, part, c3, part3, rows.value
+    return (c, part, c3, part3, rows.value) if rc == 0 else None
 
 
 def instnorm_apply_fin(x, part, rows, B, V, C, lrelu, x2=None, part_b=None, rows_b=0, out=None, ldo=None):
     """instnorm_apply with the statistics formed in the kernel's prologue from partial rows; returns (y, stats, stats_b) or None"""
+    y, ldy, sa, sb = _apply_fin_outputs(x, B, C, out, ldo, x2 is not None)
+    rc = call_rc("unetr_instnorm_apply_fin", x.data_ptr(), C, part.data_ptr(), rows, _p(x2), C, _p(part_b), rows_b, sa.data_ptr(), _p(sb),
+                 IN_EPS, y.data_ptr(), ldy, B, V, C, int(lrelu), _a16(x), _stream())
+    return (y, sa, sb) if rc == 0 else None
+
+
+def _apply_fin_outputs(x, B, C, out, ldo, dual):
+    """(y, its row pitch, statistics of x, statistics of the second branch or None) of the two instnorm_apply_fin forms"""
     y = torch.empty_like(x) if out is None else out
     sa = torch.empty(B, C, 2, dtype=torch.float32, device=x.device)
-    sb = torch.empty(B, C, 2, dtype=torch.float32, device=x.device) if x2 is not None else None
-    rc = call_rc("unetr_instnorm_apply_fin", x.data_ptr(), C, part.data_ptr(), rows, _p(x2), C, _p(part_b), rows_b, sa.data_ptr(), _p(sb),
-                 IN_EPS, y.data_ptr(), C if out is None else ldo, B, V, C, int(lrelu), _a16(x), _stream())
-    if rc != 0:
-        return None
-    return y, sa, sb
+    return y, (C if out is None else ldo), sa, (torch.empty(B, C, 2, dtype=torch.float32, device=x.device) if dual else None)
 
 
 IN_IMG_MAX_ROWS = 512       # = UNETR_IN_IMG_MAX_ROWS
@@ -615,11 +627,9 @@ IN_IMG_MAX_ROWS = 512       # = UNETR_IN_IMG_MAX_ROWS
 def instnorm_apply_fin_img(x, part, rows, img, cin, w3, part_b, rows_b, B, V, C, out=None, ldo=None):
     """block end of the residual block on the image: lrelu(norm(x) + norm(conv1x1x1(img; w3))) with the 1x1x1 branch formed from the
     image in the kernel; returns (y, stats, stats_b) or None"""
-    y = torch.empty_like(x) if out is None else out
-    sa = torch.empty(B, C, 2, dtype=torch.float32, device=x.device)
-    sb = torch.empty(B, C, 2, dtype=torch.float32, device=x.device)
+    y, ldy, sa, sb = _apply_fin_outputs(x, B, C, out, ldo, True)
     rc = call_rc("unetr_instnorm_apply_fin_img", x.data_ptr(), C, part.data_ptr(), rows, img.data_ptr(), cin, w3.data_ptr(), part_b.data_ptr(), rows_b,
-                 sa.data_ptr(), sb.data_ptr(), IN_EPS, y.data_ptr(), C if out is None else ldo, B, V, C, 1, _a16(x), _stream())
+                 sa.data_ptr(), sb.data_ptr(), IN_EPS, y.data_ptr(), ldy, B, V, C, 1, _a16(x), _stream())
     return (y, sa, sb) if rc == 0 else None
 
 
@@ -656,10 +666,18 @@ def conv3_dgrad_stats(dy, w, xn, stats, dims, prec):
 
 def instnorm_bwd_apply_fin(dy, lddy, x, sa, part, rows, nsp, B, V, C, lrelu):
     """dx of y = lrelu?(norm(x)) from dy and the partial sums `part` [B, rows, nsp, C]; None when unsupported"""
+    r = _bwd_apply_fin(dy, lddy, x, sa, None, None, part, rows, nsp, B, V, C, lrelu)
+    return r[0] if r is not None else None
+
+
+def _bwd_apply_fin(dy, lddy, x, sa, x2, sb, part, rows, nsp, B, V, C, lrelu):
+    """the one call behind instnorm_bwd_apply_fin and its dual form (x2, sb: the second normalised branch): (dx, dx2 or None) or None"""
     dx = torch.empty_like(x)
-    rc = call_rc("unetr_instnorm_bwd_apply_fin", dy.data_ptr(), lddy, x.data_ptr(), C, sa.data_ptr(), None, 0, None, part.data_ptr(), rows, nsp,
-                 dx.data_ptr(), C, None, 0, B, V, C, int(lrelu), _a16(x), _stream())
-    return dx if rc == 0 else None
+    dx2 = torch.empty_like(x2) if x2 is not None else None
+    ld2 = C if x2 is not None else 0
+    rc = call_rc("unetr_instnorm_bwd_apply_fin", dy.data_ptr(), lddy, x.data_ptr(), C, sa.data_ptr(), _p(x2), ld2, _p(sb), part.data_ptr(), rows, nsp,
+                 dx.data_ptr(), C, _p(dx2), ld2, B, V, C, int(lrelu), _a16(x), _stream())
+    return (dx, dx2) if rc == 0 else None
 
 
 def out_fuse_enabled():
@@ -702,10 +720,7 @@ def outconv_in_bwd(dl, c2, s2, c3, s3, wo, bo, B, V, C):
 
 def instnorm_bwd_apply_fin_dual(dy, lddy, x, sa, x2, sb, part, rows, B, V, C):
     """(dx, dx2) of y = lrelu(norm(x) + norm(x2)) from dy and the partial sums `part` [B, rows, 3, C]; None when unsupported"""
-    dx, dx2 = torch.empty_like(x), torch.empty_like(x2)
-    rc = call_rc("unetr_instnorm_bwd_apply_fin", dy.data_ptr(), lddy, x.data_ptr(), C, sa.data_ptr(), x2.data_ptr(), C, sb.data_ptr(), part.data_ptr(), rows, 3,
-                 dx.data_ptr(), C, dx2.data_ptr(), C, B, V, C, 1, _a16(x), _stream())
-    return (dx, dx2) if rc == 0 else None
+    return _bwd_apply_fin(dy, lddy, x, sa, x2, sb, part, rows, 3, B, V, C, True)
 
 
 def conv3_dgrad_fused(dc1, dc3, w1, w3, dx, dims, prec):
@@ -766,37 +781,26 @@ def conv_pack(w, mode):
 def conv_fwd(x, ldx, wpack, dims, cin, cout, ks, prec, out=None, ldo=None, accumulate=False):
     """x: rows [B*D*H*W, cin] pitch ldx -> y rows [.., cout]"""
     B, D, H, W = dims
-    if prec == _capi.PREC_BF16:
-        # generic im2col-loader GEMM family: fp32 storage only -- cast at the boundary (shapes the dedicated kernels decline)
-        x32 = x.float().contiguous() if x.dtype != torch.float32 else x
-        l32 = x32.stride(-2) if x32.dim() >= 2 else ldx
-        o32 = torch.empty(B, D, H, W, cout, dtype=torch.float32, device=x.device)
+    boundary = prec == _capi.PREC_BF16       # generic im2col-loader GEMM family, fp32 storage only (shapes the dedicated kernels decline)
+    y, ldy = out, ldo
+    if boundary:
+        x, ldx = _f32_rows(x, ldx, cin)
+    if boundary or out is None:
+        y, ldy = torch.empty(B, D, H, W, cout, dtype=torch.float32, device=x.device), cout
         if accumulate and out is not None:
-            o32.copy_(out)
-        ws = workspace(x.device)
-        call("unetr_conv_gemm_fwd", x32.data_ptr(), l32, wpack.data_ptr(), o32.data_ptr(), cout, int(accumulate), B, D, H, W, cin, cout, ks,
-             prec, ws.data_ptr(), ws.numel() * 4, _stream())
-        if out is None:
-            return o32.to(act_dtype(prec))
-        out.copy_(o32)
-        return out
-    if out is None:
-        out = torch.empty(B, D, H, W, cout, dtype=torch.float32, device=x.device)
-        ldo = cout
+            y.copy_(out)
     ws = workspace(x.device)
-    call("unetr_conv_gemm_fwd", x.data_ptr(), ldx, wpack.data_ptr(), out.data_ptr(), ldo, int(accumulate), B, D, H, W, cin, cout, ks,
+    call("unetr_conv_gemm_fwd", x.data_ptr(), ldx, wpack.data_ptr(), y.data_ptr(), ldy, int(accumulate), B, D, H, W, cin, cout, ks,
          prec, ws.data_ptr(), ws.numel() * 4, _stream())
-    return out
+    return _act_rows(y, prec, out) if boundary else y
 
 
 def conv_wgrad(x, ldx, dy, lddy, dims, cin, cout, ks, prec, out=None):
     B, D, H, W = dims
     dw = out if out is not None else torch.empty(cout, cin, ks, ks, ks, dtype=torch.float32, device=x.device)
     ws = workspace(x.device)
-    if x.dtype != torch.float32:
-        x = x.float().contiguous(); ldx = x.stride(-2)
-    if dy.dtype != torch.float32:
-        dy = dy.float().contiguous(); lddy = dy.stride(-2)
+    x, ldx = _f32_rows(x, ldx, cin)
+    dy, lddy = _f32_rows(dy, lddy, cout)
     call("unetr_conv_gemm_wgrad", x.data_ptr(), ldx, dy.data_ptr(), lddy, dw.data_ptr(), B, D, H, W, cin, cout, ks, prec,
          ws.data_ptr(), ws.numel() * 4, _stream())
     return dw
@@ -855,23 +859,38 @@ def tconv_fwd(x, ldx, w, dims, cin, cout, prec, out=None, ldo=None):
         gemm_bf16(xb, weight_bf16(w).view(cin, 8 * cout), M, 8 * cout, cin, b_kn=True, C=tmp)
         call("unetr_pixel_shuffle2", tmp.data_ptr(), out.data_ptr(), ldo, B, D, H, W, cout, _a16(out), _stream())
         return out, xb
-    ws = workspace(x.device)
     if prec == _capi.PREC_BF16 and x.dtype != adt:
         x = x.to(adt).contiguous(); ldx = cin      # (fp32 tokens in front of a shape the GEMM form does not take)
-    args = (x.data_ptr(), ldx, w.data_ptr(), out.data_ptr(), ldo, B, D, H, W, cin, cout, prec, ws.data_ptr(), ws.numel() * 4, _stream())
-    if call_rc("unetr_tconv2_fwd", *args) != 0:       # dedicated kernel declines the shape -> generic GEMM family (fp32 storage)
-        if prec == _capi.PREC_BF16:
-            x32 = x.float().contiguous()
-            o32 = torch.empty(B, 2 * D, 2 * H, 2 * W, cout, dtype=torch.float32, device=x.device)
-            call("unetr_tconv_fwd", x32.data_ptr(), cin, w.data_ptr(), o32.data_ptr(), cout, B, D, H, W, cin, cout, prec,
-                 ws.data_ptr(), ws.numel() * 4, _stream())
-            # (through the row-copy kernel, not Tensor.copy_: `out` may be a view handed out by TconvFn.forward -- the skip half of
-            # a concatenation buffer -- and a torch in-place op on it inside a custom Function invalidates the view's grad_fn)
-            o16 = o32.to(adt)
-            call("unetr_copy_rows", out.data_ptr(), ldo, o16.data_ptr(), cout, B * 8 * D * H * W, cout, 0, _a16(out), _stream())
-        else:
-            call("unetr_tconv_fwd", *args)
+    tail = _tconv_tail(dims, cin, cout, prec, x.device)
+
+    def boundary():
+        x32, l32 = _f32_rows(x, ldx, cin)
+        o32 = torch.empty(B, 2 * D, 2 * H, 2 * W, cout, dtype=torch.float32, device=x.device)
+        call("unetr_tconv_fwd", x32.data_ptr(), l32, w.data_ptr(), o32.data_ptr(), cout, *tail)
+        # (through the row-copy kernel, not Tensor.copy_: `out` may be a view handed out by TconvFn.forward -- the skip half of
+        # a concatenation buffer -- and a torch in-place op on it inside a custom Function invalidates the view's grad_fn)
+        o16 = _act_rows(o32, prec)
+        call("unetr_copy_rows", out.data_ptr(), ldo, o16.data_ptr(), cout, B * 8 * D * H * W, cout, 0, _a16(out), _stream())
+    _tconv_ladder("fwd", (x.data_ptr(), ldx, w.data_ptr(), out.data_ptr(), ldo) + tail, prec, boundary)
     return out, None
+
+
+def _tconv_tail(dims, cin, cout, prec, device):
+    """the arguments every transposed-conv kernel ends with"""
+    ws = workspace(device)
+    return (*dims, cin, cout, prec, ws.data_ptr(), ws.numel() * 4, _stream())
+
+
+def _tconv_ladder(which, args, prec, boundary):
+    """The ladder of tconv_fwd / tconv_dgrad / tconv_wgrad: the dedicated kernel unetr_tconv2_<which>; where it declines the shape,
+    the generic GEMM family's unetr_tconv_<which> -- on the same arguments in the fp32-storage modes, through `boundary()` (which
+    casts to fp32 and back) in bf16 mode."""
+    if call_rc("unetr_tconv2_" + which, *args) == 0:
+        return
+    if prec == _capi.PREC_BF16:
+        boundary()
+    else:
+        call("unetr_tconv_" + which, *args)
 
 
 def tconv_bwd(x, ldx, xb, dy, lddy, w, dims, cin, cout, prec, need_dx):
@@ -919,33 +938,26 @@ def tconv_bwd(x, ldx, xb, dy, lddy, w, dims, cin, cout, prec, need_dx):
 def tconv_dgrad(dy, lddy, w, dims, cin, cout, prec):
     B, D, H, W = dims
     dx = torch.empty(B, D, H, W, cin, dtype=act_dtype(prec), device=dy.device)
-    ws = workspace(dy.device)
-    args = (dy.data_ptr(), lddy, w.data_ptr(), dx.data_ptr(), cin, 0, B, D, H, W, cin, cout, prec, ws.data_ptr(), ws.numel() * 4, _stream())
-    if call_rc("unetr_tconv2_dgrad", *args) != 0:
-        if prec == _capi.PREC_BF16:                   # generic GEMM family: fp32 storage
-            d32 = dy.float().contiguous() if lddy == cout else dy[..., :cout].float().contiguous()
-            x32 = torch.empty(B, D, H, W, cin, dtype=torch.float32, device=dy.device)
-            call("unetr_tconv_dgrad", d32.data_ptr(), cout, w.data_ptr(), x32.data_ptr(), cin, 0, B, D, H, W, cin, cout, prec,
-                 ws.data_ptr(), ws.numel() * 4, _stream())
-            dx.copy_(x32)
-        else:
-            call("unetr_tconv_dgrad", *args)
+    tail = _tconv_tail(dims, cin, cout, prec, dy.device)
+
+    def boundary():
+        d32, l32 = _f32_rows(dy, lddy, cout)
+        x32 = torch.empty(B, D, H, W, cin, dtype=torch.float32, device=dy.device)
+        call("unetr_tconv_dgrad", d32.data_ptr(), l32, w.data_ptr(), x32.data_ptr(), cin, 0, *tail)
+        _act_rows(x32, prec, out=dx)
+    _tconv_ladder("dgrad", (dy.data_ptr(), lddy, w.data_ptr(), dx.data_ptr(), cin, 0) + tail, prec, boundary)
     return dx
 
 
 def tconv_wgrad(x, ldx, dy, lddy, dims, cin, cout, prec, out=None):
-    B, D, H, W = dims
     dw = out if out is not None else torch.empty(cin, cout, 2, 2, 2, dtype=torch.float32, device=x.device)
-    ws = workspace(x.device)
-    args = (x.data_ptr(), ldx, dy.data_ptr(), lddy, dw.data_ptr(), B, D, H, W, cin, cout, prec, ws.data_ptr(), ws.numel() * 4, _stream())
-    if call_rc("unetr_tconv2_wgrad", *args) != 0:
-        if prec == _capi.PREC_BF16:
-            x32 = x.float().contiguous() if ldx == cin else x[..., :cin].float().contiguous()
-            d32 = dy.float().contiguous() if lddy == cout else dy[..., :cout].float().contiguous()
-            call("unetr_tconv_wgrad", x32.data_ptr(), cin, d32.data_ptr(), cout, dw.data_ptr(), B, D, H, W, cin, cout, prec,
-                 ws.data_ptr(), ws.numel() * 4, _stream())
-        else:
-            call("unetr_tconv_wgrad", *args)
+    tail = _tconv_tail(dims, cin, cout, prec, x.device)
+
+    def boundary():
+        x32, lx = _f32_rows(x, ldx, cin)
+        d32, ld = _f32_rows(dy, lddy, cout)
+        call("unetr_tconv_wgrad", x32.data_ptr(), lx, d32.data_ptr(), ld, dw.data_ptr(), *tail)
+    _tconv_ladder("wgrad", (x.data_ptr(), ldx, dy.data_ptr(), lddy, dw.data_ptr()) + tail, prec, boundary)
     return dw
 
 
@@ -1230,62 +1242,59 @@ def cat_of_skip(skip, C):
     return skip.as_strided((B, D, H, W, 2 * C), want, 0)
 
 
+# One record per direction, whatever the route (tests/test_conv_routes_cpu.py pins the launches of every route):
+# out: the block's result -- the LOGITS [B, Cout, D, H, W] when `folded`, i.e. the block end went into the out conv's kernel and was
+# never stored (otherwise the caller applies the out conv itself); saved = (c1, s1, a1, c2, s2, c3 or None, s3).
+BlockFwd = collections.namedtuple("BlockFwd", "out saved folded")
+# q1 / q2: the reductions of (dw1, dw3) / dw2 were queued on the arena; dwo, dbo: None unless the head was folded in.
+BlockBwd = collections.namedtuple("BlockBwd", "dx dw1 dw2 dw3 q1 q2 dwo dbo")
+
+
+def _conv3_stats(x, ldx, w, dims, cout, prec):
+    """(c, stats) of the 3x3x3 conv with its InstanceNorm statistics: one launch, or conv + statistics pass where that declines"""
+    f = conv3_fused(x, ldx, w, None, dims, prec)
+    if f is not None:
+        return f[0], f[1]
+    c = conv3(x, ldx, w, dims, prec)
+    return c, instnorm_stats(c, cout, dims[0], dims[1] * dims[2] * dims[3], cout)
+
+
+def _conv1_generic(x, ldx, w3, dims, cin, cout, prec):
+    """the 1x1x1 branch as a stored tensor on the generic GEMM family (fallback of conv3_fused and of the image form)"""
+    B, D, H, W = dims
+    x32, l32 = _f32_rows(x, ldx, cin)
+    c3 = torch.empty(B, D, H, W, cout, dtype=torch.float32, device=x.device)
+    gemm(x32, w3, c3, B * D * H * W, cout, cin, lda=l32, ldb=cin, ldc=cout, prec=prec)
+    return _act_rows(c3, prec)
+
+
 def _resblock_fwd(x, ldx, dims, cin, cout, w1, w2, w3, prec, to_cat=False, head=None):
-    """MONAI UnetResBlock (instance norm, in != out): lrelu(IN(conv2(lrelu(IN(conv1 x)))) + IN(conv3 x)).
-    head = (wo, bo) of the out conv that is the block's only consumer: returns (logits [B, Cout, V] or out, saved, fused) -- fused:
-    the block end was folded into the out conv and never stored (the caller applies the out conv itself otherwise)."""
+    """MONAI UnetResBlock (instance norm, in != out): lrelu(IN(conv2(lrelu(IN(conv1 x)))) + IN(conv3 x)) -> BlockFwd.
+    head = (wo, bo) of the out conv that is the block's only consumer."""
     B, D, H, W = dims
     V = D * H * W
     if in_fuse_level() & 1:
         r = _resblock_fwd_fin(x, ldx, dims, cout, w1, w2, w3, prec, to_cat, head if out_fuse_enabled() else None)
         if r is not None:
-            return r if head is not None else r[:2]
+            return r
     f1 = conv3_fused(x, ldx, w1, w3, dims, prec)
     if f1 is not None:
         c1, s1, c3, s3 = f1
     else:
-        f1 = conv3_fused(x, ldx, w1, None, dims, prec)
-        if f1 is not None:
-            c1, s1 = f1[0], f1[1]
-        else:
-            c1 = conv3(x, ldx, w1, dims, prec)
-            s1 = instnorm_stats(c1, cout, B, V, cout)
-        # 1x1x1 conv on the generic GEMM family (fp32 storage: cast at the boundary in bf16 mode)
-        x32 = x if x.dtype == torch.float32 else x.float()
-        c3 = torch.empty(B, D, H, W, cout, dtype=torch.float32, device=x.device)
-        gemm(x32, w3, c3, B * V, cout, cin, lda=x32.stride(-2), ldb=cin, ldc=cout, prec=prec)
-        c3 = _as_act(c3, prec)
+        c1, s1 = _conv3_stats(x, ldx, w1, dims, cout, prec)
+        c3 = _conv1_generic(x, ldx, w3, dims, cin, cout, prec)
         s3 = instnorm_stats(c3, cout, B, V, cout)
     a1 = instnorm_apply(c1, s1, B, V, cout, True)
-    f2 = conv3_fused(a1, cout, w2, None, dims, prec)
-    if f2 is not None:
-        c2, s2 = f2[0], f2[1]
-    else:
-        c2 = conv3(a1, cout, w2, dims, prec)
-        s2 = instnorm_stats(c2, cout, B, V, cout)
-    if to_cat:
-        _, half = skip_half(dims, cout, prec, x.device)
-        out = instnorm_apply(c2, s2, B, V, cout, True, x2=c3, sb=s3, out=half, ldo=2 * cout)
-    else:
-        out = instnorm_apply(c2, s2, B, V, cout, True, x2=c3, sb=s3)
-    if head is not None:
-        return out, (c1, s1, a1, c2, s2, c3, s3), False
-    return out, (c1, s1, a1, c2, s2, c3, s3)
-
-
-def _materialize_c3(x, w3, dims, cin, cout, prec):
-    """the 1x1x1 branch of the block on the image as a stored tensor (fallback of the image form: generic GEMM family)"""
-    B, D, H, W = dims
-    V = D * H * W
-    c3f = torch.empty(B * V, cout, dtype=torch.float32, device=x.device)
-    gemm(x.reshape(B * V, cin), w3, c3f, B * V, cout, cin, lda=cin, ldb=cin, ldc=cout, prec=prec)
-    return _as_act(c3f.view(B, D, H, W, cout), prec)
+    c2, s2 = _conv3_stats(a1, cout, w2, dims, cout, prec)
+    half = skip_half(dims, cout, prec, x.device)[1] if to_cat else None
+    out = instnorm_apply(c2, s2, B, V, cout, True, x2=c3, sb=s3, out=half, ldo=2 * cout if to_cat else None)
+    return BlockFwd(out, (c1, s1, a1, c2, s2, c3, s3), False)
 
 
 def _resblock_fwd_fin(x, ldx, dims, cout, w1, w2, w3, prec, to_cat, head=None):
     """the same block in FOUR launches: both convs leave their InstanceNorm sums as partial rows and the two apply kernels form
     the statistics in their prologues (no finalize launches); None when a shape declines (the caller takes the route above).
-    Returns (out, saved, fused); head = (wo, bo): the block end goes into the out conv's kernel when that accepts the shape."""
+    head = (wo, bo): the block end goes into the out conv's kernel when that accepts the shape."""
     B, D, H, W = dims
     V = D * H * W
     cin = w1.shape[1]
@@ -1308,52 +1317,51 @@ def _resblock_fwd_fin(x, ldx, dims, cout, w1, w2, w3, prec, to_cat, head=None):
     if f2 is None:
         return None
     c2, p2, _, _, rows2 = f2
-    if head is not None and not img and c3 is not None and not to_cat:
+    if head is not None and not img and not to_cat:
         r = outconv_in_fwd(c2, p2, rows2, c3, p3, rows1, head[0], head[1], B, V, cout)
         if r is not None:
-            return r[0].view(B, head[0].shape[0], D, H, W), (c1, s1, a1, c2, r[1], c3, r[2]), True
+            return BlockFwd(r[0].view(B, head[0].shape[0], D, H, W), (c1, s1, a1, c2, r[1], c3, r[2]), True)
     half = skip_half(dims, cout, prec, x.device)[1] if to_cat else None
-    if img:
-        r2 = instnorm_apply_fin_img(c2, p2, rows2, x, cin, w3, p3, rows1, B, V, cout, out=half, ldo=2 * cout if to_cat else None)
-        if r2 is None:                         # (a shape the image form declines: materialise the branch after all)
-            c3 = _materialize_c3(x, w3, dims, cin, cout, prec)
-            r2 = instnorm_apply_fin(c2, p2, rows2, B, V, cout, True, x2=c3, part_b=p3, rows_b=rows1, out=half, ldo=2 * cout if to_cat else None)
-    else:
+    r2 = instnorm_apply_fin_img(c2, p2, rows2, x, cin, w3, p3, rows1, B, V, cout, out=half, ldo=2 * cout if to_cat else None) if img else None
+    if r2 is None:
+        if img:                                # (a shape the image form declines: materialise the branch after all)
+            c3 = _conv1_generic(x, ldx, w3, dims, cin, cout, prec)
         r2 = instnorm_apply_fin(c2, p2, rows2, B, V, cout, True, x2=c3, part_b=p3, rows_b=rows1, out=half, ldo=2 * cout if to_cat else None)
     if r2 is None:
         return None
     out, s2, s3 = r2
-    return out, (c1, s1, a1, c2, s2, c3, s3), False
+    return BlockFwd(out, (c1, s1, a1, c2, s2, c3, s3), False)
 
 
 def _resblock_bwd(dout, x, ldx, dims, cin, cout, w1, w2, w3, saved, prec, need_dx, head=None):
-    """head = (wo, bo): the block end was folded into the out conv (``_resblock_fwd(..., head=)`` returned fused): ``dout`` is the
-    gradient of the LOGITS; the result then ends with (dwo, dbo)"""
+    """-> BlockBwd.  head = (wo, bo): the block end was folded into the out conv (the forward's record says `folded`): ``dout`` is
+    the gradient of the LOGITS."""
     B, D, H, W = dims
     V = D * H * W
     c1, s1, a1, c2, s2, c3, s3 = saved
-    head_grads = ()
-    dc23 = None
+    dwo = dbo = img_rows = None
+
+    def stored(dout, lddo, c3):
+        return instnorm_bwd(dout, lddo, c2, s2, B, V, cout, True, x2=c3, sb=s3)
+    # the gradient at the block end: dc2, dc3 -- or, from the image form, partial rows of dw3 in the place of dc3
     if head is not None:
+        # folded head: the out conv's backward leaves the InstanceNorm backward sums as partial rows
         dout, hpart, hrows, dwo, dbo = outconv_in_bwd(dout, c2, s2, c3, s3, head[0], head[1], B, V, cout)
-        head_grads = (dwo, dbo)
-        dc23 = instnorm_bwd_apply_fin_dual(dout, cout, c2, s2, c3, s3, hpart, hrows, B, V, cout)
-    dout, lddo = _rows(dout)
-    img3 = None
-    if dc23 is not None:
-        pass
+        ends = instnorm_bwd_apply_fin_dual(dout, cout, c2, s2, c3, s3, hpart, hrows, B, V, cout)
+        if ends is None:                       # fallback: the stored form's reduction pass over the out conv's data gradient
+            ends = stored(*_rows(dout), c3)
+        dc2, dc3 = ends
     elif c3 is None:
         # the block on the image: the 1x1x1 branch was never stored -- its gradient is formed per voxel inside the backward apply and
         # leaves only as partial rows of dw3
-        img3 = instnorm_bwd_img(dout, lddo, c2, s2, x, cin, w3, s3, B, V, cout)
-        if img3 is None:
-            c3 = _materialize_c3(x, w3, dims, cin, cout, prec)
-    if dc23 is not None:
-        dc2, dc3 = dc23
-    elif img3 is not None:
-        dc2, dc3 = img3[0], None
+        dout, lddo = _rows(dout)
+        img = instnorm_bwd_img(dout, lddo, c2, s2, x, cin, w3, s3, B, V, cout)
+        if img is None:                        # fallback: materialise the branch and take the stored form
+            dc2, dc3 = stored(dout, lddo, _conv1_generic(x, ldx, w3, dims, cin, cout, prec))
+        else:
+            dc2, dc3, img_rows = img[0], None, img[1:]
     else:
-        dc2, dc3 = instnorm_bwd(dout, lddo, c2, s2, B, V, cout, True, x2=c3, sb=s3)
+        dc2, dc3 = stored(*_rows(dout), c3)
     # arena mode: the three weight gradients' partial-sum reductions join the grouped launch at the end of the backward pass
     st, (g1, g2, g3) = grad_arena.dests(w1, w2, w3)
     # conv3 (1x1x1)
@@ -1371,8 +1379,8 @@ def _resblock_bwd(dout, x, ldx, dims, cin, cout, w1, w2, w3, saved, prec, need_d
         da1 = conv3(dc2, cout, w2, dims, prec, mode=1)
         dc1, _ = instnorm_bwd(da1, cout, c1, s1, B, V, cout, True)
     dw1, q1 = _conv3_wgrad_queued(st, x, ldx, dc1, cout, dims, cin, cout, prec, out=g1, dy3=dc3, out3=dw3 if dc3 is not None else None)
-    if img3 is not None:
-        rq = (img3[1], dw3, cout * cin, img3[2])
+    if img_rows is not None:
+        rq = (img_rows[0], dw3, cout * cin, img_rows[1])
         if q1:
             st.queue_reduce(*rq)           # joins the grouped reduce at the end of the backward pass
         else:
@@ -1381,13 +1389,13 @@ def _resblock_bwd(dout, x, ldx, dims, cin, cout, w1, w2, w3, saved, prec, need_d
     if need_dx:
         dx = torch.empty(B, D, H, W, cin, dtype=act_dtype(prec), device=x.device)
         if not conv3_dgrad_fused(dc1, dc3, w1, w3, dx, dims, prec):
+            # two kernels: the 1x1x1 data gradient on the generic GEMM family, and the 3x3x3 one accumulates onto it
             d32 = torch.empty(B, D, H, W, cin, dtype=torch.float32, device=x.device)
-            gemm(dc3.float() if dc3.dtype != torch.float32 else dc3, w3, d32, B * V, cin, cout, lda=cout, ldb=cin, ldc=cin, prec=prec, b_trans=True)
-            dx.copy_(d32)
+            dc3_32, ld3 = _f32_rows(dc3, cout, cout)
+            gemm(dc3_32, w3, d32, B * V, cin, cout, lda=ld3, ldb=cin, ldc=cin, prec=prec, b_trans=True)
+            _act_rows(d32, prec, out=dx)
             conv3(dc1, cout, w1, dims, prec, mode=1, out=dx, ldo=cin, accumulate=True)
-    if head is not None:
-        return dx, dw1, dw2, dw3, (q1, q2), head_grads
-    return dx, dw1, dw2, dw3, (q1, q2)
+    return BlockBwd(dx, dw1, dw2, dw3, q1, q2, dwo, dbo)
 
 
 class ResBlockFn(torch.autograd.Function):
@@ -1400,17 +1408,17 @@ class ResBlockFn(torch.autograd.Function):
         x, ldx = _rows(x)
         B, D, H, W, cin = x.shape
         cout = w1.shape[0]
-        out, saved = _resblock_fwd(x, ldx, (B, D, H, W), cin, cout, w1, w2, w3, prec, to_cat)
-        ctx.save_for_backward(x, w1, w2, w3, *saved)
+        r = _resblock_fwd(x, ldx, (B, D, H, W), cin, cout, w1, w2, w3, prec, to_cat)
+        ctx.save_for_backward(x, w1, w2, w3, *r.saved)
         ctx.meta = (ldx, (B, D, H, W), cin, cout, prec)
-        return out
+        return r.out
 
     @staticmethod
     def backward(ctx, dout):
         x, w1, w2, w3, *saved = ctx.saved_tensors
         ldx, dims, cin, cout, prec = ctx.meta
-        dx, dw1, dw2, dw3, (q1, q2) = _resblock_bwd(dout, x, ldx, dims, cin, cout, w1, w2, w3, saved, prec, ctx.needs_input_grad[0])
-        return dx, _ret(w1, dw1, deferred=q1), _ret(w2, dw2, deferred=q2), _ret(w3, dw3, deferred=q1), None, None
+        g = _resblock_bwd(dout, x, ldx, dims, cin, cout, w1, w2, w3, saved, prec, ctx.needs_input_grad[0])
+        return g.dx, _ret(w1, g.dw1, deferred=g.q1), _ret(w2, g.dw2, deferred=g.q2), _ret(w3, g.dw3, deferred=g.q1), None, None
 
 
 class TconvFn(torch.autograd.Function):
@@ -1423,11 +1431,8 @@ class TconvFn(torch.autograd.Function):
         x, ldx = _rows(x)
         B, D, H, W, cin = x.shape
         cout = w.shape[1]
-        if to_cat:
-            _, y = skip_half((B, 2 * D, 2 * H, 2 * W), cout, prec, x.device)
-            _, xb = tconv_fwd(x, ldx, w, (B, D, H, W), cin, cout, prec, out=y, ldo=2 * cout)
-        else:
-            y, xb = tconv_fwd(x, ldx, w, (B, D, H, W), cin, cout, prec)
+        half = skip_half((B, 2 * D, 2 * H, 2 * W), cout, prec, x.device)[1] if to_cat else None
+        y, xb = tconv_fwd(x, ldx, w, (B, D, H, W), cin, cout, prec, out=half, ldo=2 * cout if to_cat else None)
         ctx.save_for_backward(x, w)
         ctx.xb = xb
         ctx.meta = (ldx, (B, D, H, W), cin, cout, prec)
@@ -1480,50 +1485,35 @@ class UpBlockFn(torch.autograd.Function):
         B, D, H, W, cin = inp.shape
         C = wt.shape[1]
         dims2 = (B, 2 * D, 2 * H, 2 * W)
-        rows2 = B * 8 * D * H * W
-        if skip_in_cat and skip.dtype == act_dtype(prec):
-            cat = cat_of_skip(skip, C)
-            _, ctx.xb = tconv_fwd(inp, ldi, wt, (B, D, H, W), cin, C, prec, out=cat, ldo=2 * C)
-        else:
-            cat = torch.empty(*dims2, 2 * C, dtype=act_dtype(prec), device=inp.device)
+        in_cat = skip_in_cat and skip.dtype == act_dtype(prec)
+        cat = cat_of_skip(skip, C) if in_cat else torch.empty(*dims2, 2 * C, dtype=act_dtype(prec), device=inp.device)
+        _, ctx.xb = tconv_fwd(inp, ldi, wt, (B, D, H, W), cin, C, prec, out=cat, ldo=2 * C)
+        if not in_cat:
             skip, lds = _rows(_as_act(skip, prec))
-            _, ctx.xb = tconv_fwd(inp, ldi, wt, (B, D, H, W), cin, C, prec, out=cat, ldo=2 * C)
-            call("unetr_copy_rows", cat.data_ptr() + cat.element_size() * C, 2 * C, skip.data_ptr(), lds, rows2, C, 0, _a16(cat), _stream())
+            call("unetr_copy_rows", cat.data_ptr() + cat.element_size() * C, 2 * C, skip.data_ptr(), lds, B * 8 * D * H * W, C, 0, _a16(cat), _stream())
         ctx.meta = (ldi, (B, D, H, W), cin, C, prec)
-        if wo is None:
-            out, saved = _resblock_fwd(cat, 2 * C, dims2, 2 * C, C, w1, w2, w3, prec)
-            ctx.head = None
-            ctx.save_for_backward(inp, wt, w1, w2, w3, cat, *saved)
-            return out
-        res, saved, fused = _resblock_fwd(cat, 2 * C, dims2, 2 * C, C, w1, w2, w3, prec, head=(wo, bo))
-        ctx.head = fused
-        if fused:
-            ctx.save_for_backward(inp, wt, w1, w2, w3, cat, wo, bo, *saved)
-            return res
-        ctx.save_for_backward(inp, wt, w1, w2, w3, cat, wo, bo, res, *saved)
-        return _outconv_fwd(res, C, wo, bo)
+        r = _resblock_fwd(cat, 2 * C, dims2, 2 * C, C, w1, w2, w3, prec, head=(wo, bo) if wo is not None else None)
+        ctx.head_folded = r.folded          # (a head exists where wo is saved; where it was not folded in, the out conv runs on its own)
+        stored_end = r.out if wo is not None and not r.folded else None
+        ctx.save_for_backward(inp, wt, w1, w2, w3, cat, wo, bo, stored_end, *r.saved)
+        return r.out if stored_end is None else _outconv_fwd(stored_end, C, wo, bo)
 
     @staticmethod
     def backward(ctx, dout):
         ldi, dims, cin, C, prec = ctx.meta
         B, D, H, W = dims
         dims2 = (B, 2 * D, 2 * H, 2 * W)
-        head_ret = (None, None)
-        if ctx.head is None:
-            inp, wt, w1, w2, w3, cat, *saved = ctx.saved_tensors
-            dcat, dw1, dw2, dw3, (q1, q2) = _resblock_bwd(dout, cat, 2 * C, dims2, 2 * C, C, w1, w2, w3, saved, prec, True)
-        elif ctx.head:
-            inp, wt, w1, w2, w3, cat, wo, bo, *saved = ctx.saved_tensors
-            dcat, dw1, dw2, dw3, (q1, q2), (dwo, dbo) = _resblock_bwd(dout, cat, 2 * C, dims2, 2 * C, C, w1, w2, w3, saved, prec, True, head=(wo, bo))
-            head_ret = (_ret(wo, dwo), _ret(bo, dbo))
-        else:
-            inp, wt, w1, w2, w3, cat, wo, bo, out, *saved = ctx.saved_tensors
-            dblk, dwo, dbo = _outconv_bwd(dout, out, C, wo, bo)
-            dcat, dw1, dw2, dw3, (q1, q2) = _resblock_bwd(dblk, cat, 2 * C, dims2, 2 * C, C, w1, w2, w3, saved, prec, True)
-            head_ret = (_ret(wo, dwo), _ret(bo, dbo))
+        inp, wt, w1, w2, w3, cat, wo, bo, stored_end, *saved = ctx.saved_tensors
+        if stored_end is not None:
+            dout, dwo, dbo = _outconv_bwd(dout, stored_end, C, wo, bo)
+        g = _resblock_bwd(dout, cat, 2 * C, dims2, 2 * C, C, w1, w2, w3, saved, prec, True, head=(wo, bo) if ctx.head_folded else None)
+        if stored_end is None:
+            dwo, dbo = g.dwo, g.dbo         # (None without a head)
+        head_ret = (_ret(wo, dwo), _ret(bo, dbo)) if wo is not None else (None, None)
+        dcat = g.dx
         dinp, dwt = tconv_bwd(inp, ldi, ctx.xb, dcat, 2 * C, wt, dims, cin, C, prec, ctx.needs_input_grad[0])
         dskip = dcat[..., C:] if ctx.needs_input_grad[1] else None
-        return (dinp, dskip, dwt, _ret(w1, dw1, deferred=q1), _ret(w2, dw2, deferred=q2), _ret(w3, dw3, deferred=q1), None, None) + head_ret
+        return (dinp, dskip, dwt, _ret(w1, g.dw1, deferred=g.q1), _ret(w2, g.dw2, deferred=g.q2), _ret(w3, g.dw3, deferred=g.q1), None, None) + head_ret
 
 
 class OutConvFn(torch.autograd.Function):
