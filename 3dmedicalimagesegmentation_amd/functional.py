@@ -170,11 +170,23 @@ def _rows(t):
 
 
 # ------------------------------------------------------------------------------------------------ wrappers
+def _p(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _epilogue(d, bias=None, res=None, ldr=0, res_mod=0, pre=None, aux=None, ldaux=0, act=0, accumulate=False, alpha=1.0):
+    """the epilogue fields that GemmDesc and GemmBf16Desc share"""
+    d.bias, d.res, d.ldr, d.res_mod = _p(bias), _p(res), ldr, res_mod
+    d.pre, d.aux, d.ldaux = _p(pre), _p(aux), ldaux
+    d.act, d.accumulate, d.alpha = act, int(accumulate), alpha
+    return d
+
+
 def gemm(A, B, C, M, N, K, *, lda, ldb, ldc, prec, a_trans=False, b_trans=False, bias=None, res=None, ldr=0,
          res_mod=0, pre=None, aux=None, ldaux=0, act=0, accumulate=False, alpha=1.0, b_words=None):
     """b_words (bf16x3 mode): the pre-split word shadow of the weight B (weight_x3) -- read instead of B where the LDS-DMA kernel takes
     the shape (M >= 32, K % 32 == 0, N % 4 == 0, plain row pitches)"""
-    d = GemmDesc()
+    d = _epilogue(GemmDesc(), bias, res, ldr, res_mod, pre, aux, ldaux, act, accumulate, alpha)
     d.b_x3words = 0
     if (b_words is not None and prec == _capi.PREC_BF16X3 and not a_trans and M >= 32 and K % 32 == 0 and N % 4 == 0 and lda % 4 == 0
             and ldb % 4 == 0 and ldc % 4 == 0 and (not b_trans or N >= 64)):
@@ -184,13 +196,7 @@ def gemm(A, B, C, M, N, K, *, lda, ldb, ldc, prec, a_trans=False, b_trans=False,
     d.a_trans, d.b_trans = int(a_trans), int(b_trans)
     d.lda, d.ldb, d.ldc = lda, ldb, ldc
     d.strideA = d.strideB = d.strideC = d.strideR = 0
-    d.bias = bias.data_ptr() if bias is not None else None
-    d.res = res.data_ptr() if res is not None else None
-    d.ldr, d.res_mod = ldr, res_mod
-    d.pre = pre.data_ptr() if pre is not None else None
-    d.aux = aux.data_ptr() if aux is not None else None
-    d.ldaux = ldaux
-    d.act, d.accumulate, d.alpha, d.prec = act, int(accumulate), alpha, prec
+    d.prec = prec
     ws = workspace(C.device)
     call("unetr_gemm", ctypes.byref(d), A.data_ptr(), B.data_ptr(), C.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream())
 
@@ -208,7 +214,7 @@ def gemm_bf16(A, B, M, N, K, *, b_kn=False, C=None, Cb=None, lda=None, ldb=None,
               pre=None, aux=None, ldaux=0, act=0, accumulate=False, alpha=1.0, ldcb=None, tc=None):
     """C / Cb [M,N] = epilogue(A[M,K] @ (B[N,K]^T | B[K,N])) with bf16-stored operands (csrc/gemm_bf16.hip)"""
     assert A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16
-    d = GemmBf16Desc()
+    d = _epilogue(GemmBf16Desc(), bias, res, ldr, res_mod, pre, aux, ldaux, act, accumulate, alpha)
     d.M, d.N, d.K, d.b_kn = M, N, K, int(b_kn)
     d.lda = lda if lda is not None else K
     d.ldb = ldb if ldb is not None else (N if b_kn else K)
@@ -217,16 +223,8 @@ def gemm_bf16(A, B, M, N, K, *, b_kn=False, C=None, Cb=None, lda=None, ldb=None,
         d.ldcb = ldcb
     if tc is not None:              # (D, H, W, Cout): scatter the bf16 output as a 2x2x2 transposed conv (tap-major columns)
         d.tc_d, d.tc_h, d.tc_w, d.tc_cout = tc
-    d.bias = bias.data_ptr() if bias is not None else None
-    d.res = res.data_ptr() if res is not None else None
-    d.ldr, d.res_mod = ldr, res_mod
-    d.pre = pre.data_ptr() if pre is not None else None
-    d.aux = aux.data_ptr() if aux is not None else None
-    d.ldaux = ldaux
-    d.act, d.accumulate, d.alpha = act, int(accumulate), alpha
     ws = workspace(A.device)
-    call("unetr_gemm_bf16", ctypes.byref(d), A.data_ptr(), B.data_ptr(), C.data_ptr() if C is not None else None,
-         Cb.data_ptr() if Cb is not None else None, ws.data_ptr(), ws.numel() * 4, _stream())
+    call("unetr_gemm_bf16", ctypes.byref(d), A.data_ptr(), B.data_ptr(), _p(C), _p(Cb), ws.data_ptr(), ws.numel() * 4, _stream())
 
 
 # ---- derived weight copies: derived_weights.py owns the tables and the freshness rules; the ops read weights through its getters ----
@@ -295,7 +293,12 @@ def carry_twin(src, dst):
     tw = getattr(src, "_unetr_bf16", None)
     if tw is not None and tw[1] == src._version:
         dst._unetr_bf16 = (tw[0], dst._version)
-    if hasattr(src, "_unetr_ln"):
+    return _carry_ln(src, dst)
+
+
+def _carry_ln(src, dst):
+    """the stashed LayerNorm alone (TransformerBlockFn.forward's contiguous copy of its input: nothing reads a bf16 twin of it)"""
+    if dst is not src and hasattr(src, "_unetr_ln"):
         dst._unetr_ln = src._unetr_ln
     return dst
 
@@ -372,10 +375,6 @@ def colsum(x, M, N, ld, out=None):
     return out
 
 
-def _p(t):
-    return t.data_ptr() if t is not None else None
-
-
 def bf16_like(t):
     return torch.empty(t.shape, dtype=torch.bfloat16, device=t.device)
 
@@ -441,15 +440,12 @@ def gemm_bf16_ln_fwd(A, B, M, N, K, C, gamma, beta, y_bf16, bias=None, res=None,
     bf16x3 mode: A / B fp32 (B optionally as its word shadow b_words), the normalised rows go to the fp32 tensor ``y``."""
     x3 = A.dtype == torch.float32
     assert x3 or (A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16)
-    d = GemmBf16Desc()
+    d = _epilogue(GemmBf16Desc(), bias, res, ldr)
     d.x3 = (2 if b_words is not None else 1) if x3 else 0
     if b_words is not None:
         B = b_words
     d.M, d.N, d.K, d.b_kn = M, N, K, 0
     d.lda, d.ldb, d.ldc, d.ldcb = K, K, N, N
-    d.bias = bias.data_ptr() if bias is not None else None
-    d.res = res.data_ptr() if res is not None else None
-    d.ldr, d.alpha = ldr, 1.0
     mean = torch.empty(M, dtype=torch.float32, device=C.device)
     rstd = torch.empty(M, dtype=torch.float32, device=C.device)
     ws = workspace(C.device)
@@ -488,13 +484,12 @@ def gemm_ln_bwd_params(A, Bw, M, N, K, x, w, b, mean, rstd, dres=None, dx_bf16=N
     b_kn=False: Bw is the transposed twin [N, K] of the weight (weight_bf16_t), read in the forward kernel form."""
     x3 = A.dtype == torch.float32              # bf16x3 mode: fp32 operands (Bw optionally as its word shadow b_words)
     assert x3 or (A.dtype == torch.bfloat16 and Bw.dtype == torch.bfloat16)
-    d = GemmBf16Desc()
+    d = _epilogue(GemmBf16Desc())
     d.x3 = (2 if b_words is not None else 1) if x3 else 0
     if b_words is not None:
         Bw = b_words
     d.M, d.N, d.K, d.b_kn = M, N, K, int(bool(b_kn))
     d.lda, d.ldb, d.ldc, d.ldcb = K, (N if b_kn else K), N, N
-    d.alpha = 1.0
     scratch = torch.empty(M, N, dtype=torch.float32, device=x.device)
     dx = torch.empty_like(x)
     ws = workspace(x.device)
@@ -973,14 +968,13 @@ class PatchEmbedFn(torch.autograd.Function):
         L = (D // patch) * (H // patch) * (W // patch)
         pd = C * patch ** 3
         hid = w.shape[0]
-        ctx.pb = None
+        patches = ctx.pb = None
         if _bf16_path(prec, pd) and (B * L) % 8 == 0 and hid % 8 == 0:
             # the bf16 GEMM operand straight from the gather kernel (no fp32 patch matrix, no cast pass).  Only where backward's
             # weight gradient can take the bf16 grouped launch (wgrad_or_defer: rows and both widths multiples of 8): its fp32
             # fallback needs the fp32 patch matrix this branch does not keep (e.g. 48^3 at batch 1: 27 token rows)
             z = torch.empty(B * L, hid, dtype=torch.float32, device=x_in.device)
             ctx.pb = torch.empty(B * L, pd, dtype=torch.bfloat16, device=x_in.device)
-            patches = x_in.new_empty(0)
             call("unetr_patch_gather", x_in.data_ptr(), None, ctx.pb.data_ptr(), B, C, D, H, W, patch, _stream())
             gemm_bf16(ctx.pb, weight_bf16(w), B * L, hid, pd, C=z, bias=b, res=pos, ldr=hid, res_mod=L)
         else:
@@ -1002,44 +996,52 @@ class PatchEmbedFn(torch.autograd.Function):
         return None, dw, db, dpos, None, None
 
 
-def _tblock_forward(x, n1w, n1b, wqkv, wp, bp, n2w, n2b, w1, b1, w2, b2, B, L, heads, prec, train, next_ln=None, emit_twin=False,
+# The route of one transformer block, decided once in forward from (prec, M, hid, mlp, dh) and the switches; backward and the
+# checkpoint recompute read it.  fast: bf16-stored operands for every GEMM (fp32 copies stay only where a kernel reads them);
+# b16att: q/k/v stay bf16 from the GEMM epilogue to the attention kernels' LDS-DMA; x3ride / x3ride_qkv (bf16x3): the LayerNorm
+# rides on the GEMM with K = mlp (forward of the next norm1, backward of norm2) / K = 3 hid (backward of norm1).
+BlockRoute = collections.namedtuple("BlockRoute", "fast b16att x3ride x3ride_qkv")
+# What backward needs of a block's forward, None where the route has no such tensor: the fp32 activations and LayerNorm statistics
+# (y1 y2 a: fp32 routes only; att: not with b16att; u, the pre-activation that only GELU' reads: training only), then the bf16
+# operands of the weight-gradient GEMMs (fast route only).
+BlockActs = collections.namedtuple("BlockActs", "y1 m1 r1 qkv att lse x1 y2 m2 r2 u a y1b attb y2b ab")
+
+
+def _block_route(prec, M, hid, mlp, dh):
+    fast = _bf16_path(prec, hid, mlp) and M % 8 == 0          # (the bf16 weight-gradient kernel wants whole 8-token groups)
+    x3 = prec == _capi.PREC_BF16X3 and ln_ride_enabled()
+    return BlockRoute(fast, fast and dh == 64, x3 and x3_ride_ok(M, hid, mlp), x3 and x3_ride_ok(M, hid, 3 * hid))
+
+
+def _tblock_forward(x, n1w, n1b, wqkv, wp, bp, n2w, n2b, w1, b1, w2, b2, B, L, heads, prec, route, train, next_ln=None, emit_twin=False,
                     next_wqkv=None):
-    """kernels of one transformer block; returns (x2, tensors backward needs, bf16 twins or None).  next_ln = (gamma, beta) of
-    the LayerNorm the next layer starts with: computed by the kernel that forms x2 and left on x2 (_stash_ln).  next_wqkv: the
-    qkv weight of that next layer, prefetched by the same kernel.  bf16 path: every non-GEMM launch prefetches the weights of
-    the GEMM(s) behind it (_prefetch)"""
-    hid = x.shape[1]
-    dh = hid // heads
-    M, mlp = x.shape[0], w1.shape[0]
-    if _bf16_path(prec, hid, mlp) and M % 8 == 0:     # (the bf16 weight-gradient kernel wants whole 8-token groups)
-        # bf16-stored operands: every GEMM input below is written as bf16 by its producer (fp32 copies stay for
-        # the weight-gradient GEMMs and the LayerNorm / attention backward kernels)
-        f32 = dict(dtype=torch.float32, device=x.device)
-        y1 = y2 = a = x.new_empty(0)         # the fp32 twins are not materialised: every consumer reads bf16
-        b16att = dh == 64   # q/k/v stay bf16 from the GEMM epilogue to the attention kernels' LDS-DMA
-        qkv = torch.empty(M, 3 * hid, dtype=torch.bfloat16 if b16att else torch.float32, device=x.device)
+    """kernels of one transformer block; returns (x2, BlockActs).  next_ln = (gamma, beta) of the LayerNorm the next layer starts
+    with: computed by the kernel that forms x2 and left on x2 (_stash_ln).  next_wqkv: the qkv weight of that next layer,
+    prefetched by the same kernel.  bf16 path: every non-GEMM launch prefetches the weights of the GEMM(s) behind it (_prefetch)"""
+    M, hid = x.shape
+    dh, mlp = hid // heads, w1.shape[0]
+    f32 = dict(dtype=torch.float32, device=x.device)
+    if route.fast:
+        qkv = torch.empty(M, 3 * hid, dtype=torch.bfloat16 if route.b16att else torch.float32, device=x.device)
         pre = _stashed_ln(x, n1w, n1b)       # norm1(x) may have been formed by the kernel that produced x
         if pre is not None:
             y1b, m1, r1 = pre
         else:
             y1b = bf16_like(x)
             _, m1, r1 = layernorm_fwd(x, n1w, n1b, bf16_out=y1b, want_fp32=False, pf=_prefetch("ln1_fwd", wqkv))
-        gemm_bf16(y1b, weight_bf16(wqkv), M, 3 * hid, hid, C=None if b16att else qkv, Cb=qkv if b16att else None)
-        attb = bf16_like(x)
-        if b16att:
-            att = x.new_empty(0)
+        gemm_bf16(y1b, weight_bf16(wqkv), M, 3 * hid, hid, C=None if route.b16att else qkv, Cb=qkv if route.b16att else None)
+        attb, att = bf16_like(x), None
+        if route.b16att:
             lse = attention_bf16_fwd(qkv, B, L, heads, dh, attb, pf=_prefetch("attn_fwd", wp, w1))
         else:
             att, lse = attention_fwd(qkv, B, L, heads, dh, prec, out_bf16=attb)
         x1 = torch.empty(M, hid, **f32)
         gemm_bf16(attb, weight_bf16(wp), M, hid, hid, C=x1, bias=bp, res=x, ldr=hid)
-        u = torch.empty(M, mlp, **f32) if train else None      # pre-activation, only GELU' in backward reads it
+        u = torch.empty(M, mlp, **f32) if train else None
         ab = torch.empty(M, mlp, dtype=torch.bfloat16, device=x.device)
         y2b = bf16_like(x)
         _, m2, r2 = layernorm_fwd(x1, n2w, n2b, bf16_out=y2b, want_fp32=False, pf=_prefetch("ln2_fwd", w2))
         gemm_bf16(y2b, weight_bf16(w1), M, mlp, hid, Cb=ab, bias=b1, act=1, pre=u)
-        if not train:
-            u = m1 = r1 = m2 = r2 = y1b = y2b = x.new_empty(0)
         x2 = torch.empty(M, hid, **f32)
         if next_ln is not None and not emit_twin:      # (a tapped block writes the bf16 twin of x2 from its own epilogue)
             xn = bf16_like(x)
@@ -1053,27 +1055,24 @@ def _tblock_forward(x, n1w, n1b, wqkv, wp, bp, n2w, n2b, w1, b1, w2, b2, B, L, h
             gemm_bf16(ab, weight_bf16(w2), M, hid, mlp, C=x2, Cb=x2b, bias=b2, res=x1, ldr=hid)
             if x2b is not None:
                 _attach_twin(x2, x2b)
-        twins = (y1b, attb, y2b, ab)          # bf16 operands of the weight-gradient GEMMs
+        return x2, BlockActs(None, m1, r1, qkv, att, lse, x1, None, m2, r2, u, None, y1b, attb, y2b, ab)
+    pre = _stashed_ln(x, n1w, n1b) if route.x3ride else None      # (bf16x3: norm1(x) may have ridden on the GEMM that produced x)
+    y1, m1, r1 = pre if pre is not None else layernorm_fwd(x, n1w, n1b)
+    qkv = linear_fwd(y1, wqkv, None, prec)
+    att, lse = attention_fwd(qkv, B, L, heads, dh, prec)
+    x1 = linear_fwd(att, wp, bp, prec, res=x)
+    y2, m2, r2 = layernorm_fwd(x1, n2w, n2b)
+    u = torch.empty(M, mlp, **f32)
+    a = linear_fwd(y2, w1, b1, prec, act=1, pre=u)
+    if route.x3ride and next_ln is not None:
+        # the next block's norm1 rides on the split-K sum of linear2 (as in bf16 mode): no reduce launch, no LayerNorm launch
+        x2 = torch.empty(M, hid, **f32)
+        xn = torch.empty_like(x2)
+        mn, rn = gemm_bf16_ln_fwd(a, w2, M, hid, mlp, x2, next_ln[0], next_ln[1], None, bias=b2, res=x1, ldr=hid, y=xn, b_words=weight_x3(w2))
+        _stash_ln(x2, next_ln[0], next_ln[1], xn, mn, rn)
     else:
-        twins = None
-        x3ride = prec == _capi.PREC_BF16X3 and ln_ride_enabled() and x3_ride_ok(M, hid, mlp)
-        pre = _stashed_ln(x, n1w, n1b) if x3ride else None      # (bf16x3: norm1(x) may have ridden on the GEMM that produced x)
-        y1, m1, r1 = pre if pre is not None else layernorm_fwd(x, n1w, n1b)
-        qkv = linear_fwd(y1, wqkv, None, prec)
-        att, lse = attention_fwd(qkv, B, L, heads, dh, prec)
-        x1 = linear_fwd(att, wp, bp, prec, res=x)
-        y2, m2, r2 = layernorm_fwd(x1, n2w, n2b)
-        u = torch.empty(M, mlp, dtype=torch.float32, device=x.device)
-        a = linear_fwd(y2, w1, b1, prec, act=1, pre=u)
-        if x3ride and next_ln is not None:
-            # the next block's norm1 rides on the split-K sum of linear2 (as in bf16 mode): no reduce launch, no LayerNorm launch
-            x2 = torch.empty(M, hid, dtype=torch.float32, device=x.device)
-            xn = torch.empty_like(x2)
-            mn, rn = gemm_bf16_ln_fwd(a, w2, M, hid, mlp, x2, next_ln[0], next_ln[1], None, bias=b2, res=x1, ldr=hid, y=xn, b_words=weight_x3(w2))
-            _stash_ln(x2, next_ln[0], next_ln[1], xn, mn, rn)
-        else:
-            x2 = linear_fwd(a, w2, b2, prec, res=x1)
-    return x2, (y1, m1, r1, qkv, att, lse, x1, y2, m2, r2, u, a), twins
+        x2 = linear_fwd(a, w2, b2, prec, res=x1)
+    return x2, BlockActs(y1, m1, r1, qkv, att, lse, x1, y2, m2, r2, u, a, None, None, None, None)
 
 
 WT_MAX_ROWS = 512     # the two operand forms are measured, and held bit for bit, at the small-M tile rules only (csrc/gemm_bf16.hip)
@@ -1085,6 +1084,28 @@ def _dgrad_operand(w, M):
     the forward form), else the bf16 shadow read as the [K, N] operand"""
     wt = weight_bf16_t(w) if M <= WT_MAX_ROWS else None
     return (wt, False) if wt is not None else (weight_bf16(w), True)
+
+
+def _dgrad_bf16(dyb, w, **out):
+    """dx[M, in] = dyb[M, out] . w on bf16-stored operands, into C= / Cb= through gemm_bf16's epilogue: on the transposed twin of w in
+    the forward kernel form where the fused optimizer epilogue keeps one current, else w [out, in] read as the [K, N] operand; same bits"""
+    wo, bkn = _dgrad_operand(w, dyb.shape[0])
+    gemm_bf16(dyb, wo, dyb.shape[0], w.shape[1], w.shape[0], b_kn=bkn, **out)
+
+
+def _dgrad_ln_bwd(route, x3ride, dy, dyb, w, prec, x, nw, nb, mean, rstd, dres, host, *ahead):
+    """The data gradient of Linear `w` run into the backward of the LayerNorm (nw, nb) in front of it: (dx, grad_nw, grad_nb, the
+    bf16 twin of dx or None).  fast: on bf16 twins, the LayerNorm kernel sums the K slabs of the GEMM itself and prefetches `ahead`
+    as `host`; x3ride: the same on fp32 operands with the word shadow of w; else the two launches"""
+    (M, N), K = x.shape, w.shape[0]
+    if route.fast:
+        dxb = bf16_like(x)
+        wo, bkn = _dgrad_operand(w, M)
+        return gemm_ln_bwd_params(dyb, wo, M, N, K, x, nw, nb, mean, rstd, dres=dres, dx_bf16=dxb,
+                                  pf=_prefetch(host, *ahead, dgrad=M), b_kn=bkn) + (dxb,)
+    if x3ride:
+        return gemm_ln_bwd_params(dy, w, M, N, K, x, nw, nb, mean, rstd, dres=dres, b_words=weight_x3(w)) + (None,)
+    return layernorm_bwd_params(linear_dgrad(dy, w, prec), x, nw, nb, mean, rstd, dres=dres) + (None,)
 
 
 class TransformerBlockFn(torch.autograd.Function):
@@ -1099,19 +1120,14 @@ class TransformerBlockFn(torch.autograd.Function):
         only): the qkv weight of the next block, read ahead by that kernel, and linear2 / linear1 of the block BELOW, whose
         backward starts with those two GEMMs right after this block's last backward launch"""
         _require_gpu(x)
-        xc = x.contiguous()
-        if xc is not x and hasattr(x, "_unetr_ln"):
-            xc._unetr_ln = x._unetr_ln
-        x = xc
+        x = _carry_ln(x, x.contiguous())
         train = any(ctx.needs_input_grad[:12])
-        x2, acts, twins = _tblock_forward(x, n1w, n1b, wqkv, wp, bp, n2w, n2b, w1, b1, w2, b2, B, L, heads, prec,
-                                          train and not ckpt, None if next_n1w is None else (next_n1w, next_n1b), bool(emit_twin), next_wqkv)
+        ctx.route = _block_route(prec, x.shape[0], x.shape[1], w1.shape[0], x.shape[1] // heads)
+        x2, acts = _tblock_forward(x, n1w, n1b, wqkv, wp, bp, n2w, n2b, w1, b1, w2, b2, B, L, heads, prec, ctx.route,
+                                   train and not ckpt, None if next_n1w is None else (next_n1w, next_n1b), bool(emit_twin), next_wqkv)
         ctx.below = (below_w2, below_w1)
         ctx.ckpt = bool(ckpt) and train
-        if ctx.ckpt:
-            acts, twins = (), None
-        ctx.twins = twins
-        ctx.save_for_backward(x, n1w, wqkv, wp, n2w, w1, w2, n1b, bp, n2b, b1, b2, *acts)
+        ctx.save_for_backward(x, n1w, wqkv, wp, n2w, w1, w2, n1b, bp, n2b, b1, b2, *(() if ctx.ckpt else acts))
         ctx.meta = (B, L, heads, x.shape[1] // heads, prec)
         return x2
 
@@ -1119,81 +1135,49 @@ class TransformerBlockFn(torch.autograd.Function):
     def backward(ctx, dx2):
         x, n1w, wqkv, wp, n2w, w1, w2, n1b, bp, n2b, b1, b2, *acts = ctx.saved_tensors
         B, L, heads, dh, prec = ctx.meta
-        twins = ctx.twins
+        route = ctx.route
         if ctx.ckpt:
-            _, acts, twins = _tblock_forward(x, n1w, n1b, wqkv, wp, bp, n2w, n2b, w1, b1, w2, b2, B, L, heads, prec, True)
-        y1, m1, r1, qkv, att, lse, x1, y2, m2, r2, u, a = acts
+            _, A = _tblock_forward(x, n1w, n1b, wqkv, wp, bp, n2w, n2b, w1, b1, w2, b2, B, L, heads, prec, route, True)
+        else:
+            A = BlockActs(*acts)
         M, hid = x.shape
         dx2 = dx2.contiguous()
         mlp = w1.shape[0]
-        fast = _bf16_path(prec, hid, mlp) and M % 8 == 0
-        f32 = dict(dtype=torch.float32, device=x.device)
         # MLP
-        y1b = attb = y2b = ab = dx2b = dub = None
-        if fast:
-            # data gradients dX = dY . W: on the transposed twin of W in the forward kernel form where the fused optimizer epilogue
-            # keeps one current (_dgrad_operand), else W [out, in] read as the [K_reduce, N_out] operand (b_kn); same bits
-            if twins is not None:
-                y1b, attb, y2b, ab = twins
+        du = dub = dx2b = None
+        if route.fast:
             dx2b = _twin(dx2)
             # (du exists as bf16 only: the weight gradient of linear1 is formed from these bf16 values, and so is its bias gradient
             # -- the fp32 copy was 5.3 MB written and read back per block for the column sum alone)
-            du, dub = None, torch.empty(M, mlp, dtype=torch.bfloat16, device=x.device)
-            wo, bkn = _dgrad_operand(w2, M)
-            gemm_bf16(dx2b, wo, M, mlp, hid, b_kn=bkn, Cb=dub, act=2, aux=u, ldaux=mlp)
+            dub = torch.empty(M, mlp, dtype=torch.bfloat16, device=x.device)
+            _dgrad_bf16(dx2b, w2, Cb=dub, act=2, aux=A.u, ldaux=mlp)
         else:
-            du = linear_dgrad(dx2, w2, prec, aux=u)
-        dw2 = wgrad_or_defer(dx2, a, prec, w2, dx2b, ab)
+            du = linear_dgrad(dx2, w2, prec, aux=A.u)
+        dw2 = wgrad_or_defer(dx2, A.a, prec, w2, dx2b, A.ab)
         db2 = colsum_or_defer(dx2, M, hid, hid, b2)
-        dw1 = wgrad_or_defer(du, y2, prec, w1, dub, y2b)
-        db1 = colsum_or_defer(dub if fast else du, M, mlp, mlp, b1)
-        if fast:
-            dx1b = bf16_like(x)
-            wo, bkn = _dgrad_operand(w1, M)
-            dx1, dn2w, dn2b = gemm_ln_bwd_params(dub, wo, M, hid, mlp, x1, n2w, n2b, m2, r2, dres=dx2, dx_bf16=dx1b,
-                                                 pf=_prefetch("ln2_bwd", wp, dgrad=M), b_kn=bkn)
-        else:
-            dx1b = None
-            if prec == _capi.PREC_BF16X3 and ln_ride_enabled() and x3_ride_ok(M, hid, mlp):
-                # (bf16x3: LayerNorm backward sums the K slabs of the data-gradient GEMM itself, as in bf16 mode)
-                dx1, dn2w, dn2b = gemm_ln_bwd_params(du, w1, M, hid, mlp, x1, n2w, n2b, m2, r2, dres=dx2, b_words=weight_x3(w1))
-            else:
-                dy2 = linear_dgrad(du, w1, prec)
-                dx1, dn2w, dn2b = layernorm_bwd_params(dy2, x1, n2w, n2b, m2, r2, dres=dx2, dx_bf16=dx1b)
+        dw1 = wgrad_or_defer(du, A.y2, prec, w1, dub, A.y2b)
+        db1 = colsum_or_defer(dub if route.fast else du, M, mlp, mlp, b1)
+        dx1, dn2w, dn2b, dx1b = _dgrad_ln_bwd(route, route.x3ride, du, dub, w1, prec, A.x1, n2w, n2b, A.m2, A.r2, dx2, "ln2_bwd", wp)
         # attention
-        b16att = fast and qkv.dtype == torch.bfloat16
-        if b16att:
-            dattb = bf16_like(x)
-            wo, bkn = _dgrad_operand(wp, M)
-            gemm_bf16(dx1b, wo, M, hid, hid, b_kn=bkn, Cb=dattb)
-        elif fast:
-            datt = torch.empty(M, hid, **f32)
-            wo, bkn = _dgrad_operand(wp, M)
-            gemm_bf16(dx1b, wo, M, hid, hid, b_kn=bkn, C=datt)
+        datt = dattb = dqkv = dqkvb = None
+        if route.fast:
+            if route.b16att:
+                dattb = bf16_like(x)
+            else:
+                datt = torch.empty(M, hid, dtype=torch.float32, device=x.device)
+            _dgrad_bf16(dx1b, wp, C=datt, Cb=dattb)
         else:
             datt = linear_dgrad(dx1, wp, prec)
-        dwp = wgrad_or_defer(dx1, att, prec, wp, dx1b, attb)
+        dwp = wgrad_or_defer(dx1, A.att, prec, wp, dx1b, A.attb)
         dbp = colsum_or_defer(dx1, M, hid, hid, bp)
-        if b16att:
-            dqkv = None
-            dqkvb = attention_bf16_bwd(qkv, attb, dattb, lse, B, L, heads, dh, pf=_prefetch("attn_bwd", wqkv, dgrad=M))
+        if route.b16att:
+            dqkvb = attention_bf16_bwd(A.qkv, A.attb, dattb, A.lse, B, L, heads, dh, pf=_prefetch("attn_bwd", wqkv, dgrad=M))
         else:
-            dqkvb = torch.empty(M, 3 * hid, dtype=torch.bfloat16, device=x.device) if fast else None
-            dqkv = attention_bwd(qkv, att, datt, lse, B, L, heads, dh, prec, dqkv_bf16=dqkvb)
-        dwqkv = wgrad_or_defer(dqkv, y1, prec, wqkv, dqkvb, y1b)
-        if fast:
-            dxb = bf16_like(x)
-            wo, bkn = _dgrad_operand(wqkv, M)
-            dx, dn1w, dn1b = gemm_ln_bwd_params(dqkvb, wo, M, hid, 3 * hid, x, n1w, n1b, m1, r1, dres=dx1, dx_bf16=dxb,
-                                                pf=_prefetch("ln1_bwd", *ctx.below, dgrad=M), b_kn=bkn)
-        else:
-            dxb = None
-            if prec == _capi.PREC_BF16X3 and ln_ride_enabled() and x3_ride_ok(M, hid, 3 * hid):
-                dx, dn1w, dn1b = gemm_ln_bwd_params(dqkv, wqkv, M, hid, 3 * hid, x, n1w, n1b, m1, r1, dres=dx1, b_words=weight_x3(wqkv))
-            else:
-                dy1 = linear_dgrad(dqkv, wqkv, prec)
-                dx, dn1w, dn1b = layernorm_bwd_params(dy1, x, n1w, n1b, m1, r1, dres=dx1, dx_bf16=dxb)
-        if fast:
+            dqkvb = torch.empty(M, 3 * hid, dtype=torch.bfloat16, device=x.device) if route.fast else None
+            dqkv = attention_bwd(A.qkv, A.att, datt, A.lse, B, L, heads, dh, prec, dqkv_bf16=dqkvb)
+        dwqkv = wgrad_or_defer(dqkv, A.y1, prec, wqkv, dqkvb, A.y1b)
+        dx, dn1w, dn1b, dxb = _dgrad_ln_bwd(route, route.x3ride_qkv, dqkv, dqkvb, wqkv, prec, x, n1w, n1b, A.m1, A.r1, dx1, "ln1_bwd", *ctx.below)
+        if dxb is not None:
             _attach_twin(dx, dxb)      # the block below picks its bf16 operand up from here (functional._twin)
         return (dx, dn1w, dn1b, dwqkv, dwp, dbp, dn2w, dn2b, dw1, db1, dw2, db2) + (None,) * 11
 

@@ -151,6 +151,8 @@ class World:
 
     def plain(self, a):
         if isinstance(a, ctypes.Array):
+            if a._type_ is ctypes.c_void_p:          # (the prefetch descriptor's pointers)
+                return [self.ptr(e) for e in a]
             return [self.struct(e) if isinstance(e, ctypes.Structure) else e for e in a]
         if isinstance(a, ctypes.Structure):
             return self.struct(a)
@@ -198,6 +200,9 @@ class World:
         dout = self.know("dout", torch.zeros(out.shape, dtype=out.dtype))
         self.note("backward")
         torch.autograd.backward([out], [dout])
+        self.grads(**wrt)
+
+    def grads(self, **wrt):
         got = {}
         for k, t in wrt.items():
             g = t.grad
@@ -460,9 +465,9 @@ case("wrappers, dedicated kernels decline", wrappers, decline={k: True for k in 
     "unetr_instnorm_bwd_apply_fin", "unetr_conv3_dgrad_stats", "unetr_conv3_dgrad_fused", "unetr_outconv_in_fwd")})
 
 
-def run_case(pkg, mp, name):
-    fn, prec, world, opt = CASES[name]
-    W = World(pkg, mp, prec, **world)
+def run_case(pkg, mp, name, cases=CASES, world_type=World):
+    fn, prec, world, opt = cases[name]
+    W = world_type(pkg, mp, prec, **world)
     try:
         fn(W, **opt)
     finally:
@@ -505,18 +510,18 @@ def test_the_log_has_no_other_scenarios(parent_log):
     assert sorted(parent_log["digest"]) == sorted(CASES) and sorted(parent_log["full"]) == sorted(FULL)
 
 
-def main(root):
+def main(root, cases=CASES, full=FULL, run=run_case):
     sys.path.insert(0, os.path.abspath(root))
     pkg = importlib.import_module("3dmedicalimagesegmentation_amd")
     assert os.path.dirname(os.path.dirname(os.path.abspath(pkg.__file__))) == os.path.abspath(root)
     logs = {}
-    for name in CASES:
+    for name in cases:
         with pytest.MonkeyPatch.context() as mp:
-            logs[name] = run_case(pkg, mp, name)
+            logs[name] = run(pkg, mp, name)
     if "--full" in sys.argv:          # every scenario entry by entry (to compare two trees)
         return print("\n".join(f"{name}: {line}" for name, log in logs.items() for line in lines(log)))
     dig = ",\n".join(f" {json.dumps(name)}: {json.dumps(digest(log))}" for name, log in logs.items())
-    full = ",\n".join(f" {json.dumps(name)}: [\n" + ",\n".join(lines(logs[name])) + "\n ]" for name in FULL)
+    full = ",\n".join(f" {json.dumps(name)}: [\n" + ",\n".join(lines(logs[name])) + "\n ]" for name in full)
     print('{"digest": {\n' + dig + '\n},\n"full": {\n' + full + "\n}}")
 
 
