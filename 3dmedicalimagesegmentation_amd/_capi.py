@@ -224,6 +224,9 @@ _SIGNATURES = {
     "unetr_aug_gather_affine": [ctypes.POINTER(AugDesc), P, c_int, P, P, P, P, P, c_size_t, P],
     "unetr_aug_intensity_sample": [ctypes.POINTER(AugDesc), ctypes.POINTER(AugIntensityDesc), P, P, P],
     "unetr_aug_intensity_apply": [ctypes.POINTER(AugDesc), P, P, P, c_size_t, P],
+    "unetr_aug_class_count": [P, P, c_int, c_int, c_int, c_long, c_int, c_float, P, c_size_t, P, P],
+    "unetr_aug_class_scatter": [P, P, c_int, c_int, c_int, c_long, c_int, c_float, P, c_size_t, P, P, P],
+    "unetr_aug_sample_classes": [ctypes.POINTER(AugDesc), ctypes.POINTER(AugAffineDesc), P, c_int, P, c_int, P, P, P, P, P, P, P],
     "unetr_resample_orient": [P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_double), c_int, c_int, c_int, P, P, P],
     "unetr_restore_native": [P, c_int, c_int, RestoreGeom, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
     "unetr_ccl": [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint, c_int, c_int, c_int, c_int, P, c_size_t, c_int, P],
@@ -237,7 +240,8 @@ _SIGNATURES = {
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + ("unetr_conv3_packed_bytes", "unetr_conv3_packed_1x1_bytes", "unetr_ranking_workspace_floats",
                                             "unetr_conv3_wgrad_rows", "unetr_tconv2_wgrad_rows", "unetr_outconv_in_bwd_rows", "unetr_hausdorff_workspace_bytes",
                                             "unetr_aug_index_ws_ints", "unetr_aug_gather_ws_bytes", "unetr_aug_gather_affine_ws_bytes", "unetr_ccl_workspace_bytes",
-                                            "unetr_surface_metrics_workspace_bytes", "unetr_aug_intensity_ws_bytes", "unetr_segloss_workspace_bytes")
+                                            "unetr_surface_metrics_workspace_bytes", "unetr_aug_intensity_ws_bytes", "unetr_segloss_workspace_bytes",
+                                            "unetr_aug_class_ws_ints")
 
 _lib = None
 
@@ -287,6 +291,8 @@ def load():
     lib.unetr_aug_gather_affine_ws_bytes.restype = c_size_t
     lib.unetr_aug_intensity_ws_bytes.argtypes = [ctypes.POINTER(AugDesc)]
     lib.unetr_aug_intensity_ws_bytes.restype = c_size_t
+    lib.unetr_aug_class_ws_ints.argtypes = [c_long, c_int]
+    lib.unetr_aug_class_ws_ints.restype = c_long
     lib.unetr_segloss_workspace_bytes.argtypes = [ctypes.POINTER(SegLossDesc)]
     lib.unetr_segloss_workspace_bytes.restype = c_size_t
     _lib = lib

@@ -17,6 +17,10 @@ docstring, DESIGN.md section 12, tests/augment_affine_ref.py).
 ``intensity=IntensityAugment(...)`` adds nnU-Net's intensity family on x after all of that: Gaussian blur, Gaussian noise,
 brightness, contrast and gamma, flagged per sample, from the same Philox stream; again the project's own semantics
 (IntensityAugment's and RandCropAugment's docstrings, DESIGN.md section 12, tests/augment_intensity_ref.py).
+
+``sampling="label_classes"`` is MONAI's RandCropByLabelClassesd: the crop centre is a voxel of a class drawn by ratio, from
+per-class voxel lists ``VolumeCache.build_class_indices`` builds on the GPU (map_classes_to_indices); the ratios live in device
+memory (``aug.class_ratios``), so a captured call can be steered between replays (tests/augment_classes_ref.py).
 """
 import ctypes
 import dataclasses
@@ -37,10 +41,12 @@ MAX_BLUR_SIGMA = 2.0    # the blur's radius (int)(max(4 sigma, 0.5) + 0.5) stays
 _MAXDIM_AFFINE = 1 << 24  # volume extent up to which a float32 coordinate still names every voxel
 PARAM_COLS = 8          # params row: volume, corner z, y, x, flip mask (bit a = spatial axis a), k, shift flag, offset (float bits)
 _VCOLS = 12             # device volume table row: img ptr, lbl ptr, fg ptr, nfg, bg ptr, nbg, C, L, D, H, W, 0
+_CCOLS = 2              # device class table row: concatenated class lists (int32) ptr, offsets (int64 [K + 1]) ptr
 _MAXC = 8
 _MAXS = 512
+MAX_CLASSES = 32        # one bit per class in the list kernels
 NORMALIZE_MODES = (None, "nonzero_channel_wise")
-SAMPLING_MODES = ("pos_neg", "uniform")
+SAMPLING_MODES = ("pos_neg", "uniform", "label_classes")
 
 
 class VolumeCache:
@@ -60,6 +66,9 @@ class VolumeCache:
         self._geometry = {}      # volume id -> preprocess.Geometry of add_raw (with the foreground crop): the way back
         self._origins = []       # per volume: (z0, y0, x0) of CropForegroundd's box on the grid add() was given
         self._table = None
+        self._class_cfg = None   # (num_classes, image_mask) once build_class_indices was called
+        self._classes = []       # per volume built so far: (lists int32, offsets int64 [K + 1] on the device, counts on the host)
+        self._class_table = None
 
     def __len__(self):
         return len(self._vols)
@@ -182,6 +191,88 @@ class VolumeCache:
             self._table = torch.tensor(rows, dtype=torch.int64).to(self.device)
         return self._table
 
+    # ---------------------------------------------------------------- per-class voxel lists (RandCropByLabelClassesd)
+    def build_class_indices(self, num_classes: Optional[int] = None, image_mask: bool = False) -> None:
+        """monai map_classes_to_indices for every volume held, and lazily for volumes added later: one int32 list of voxel
+        indices per class, ascending ravel order.  A single-channel label holds class ids: class c is ``label == c`` for c in
+        0..num_classes-1 (required, 1..32), an id >= num_classes is in no list.  A label of L > 1 channels is one-hot or
+        multi-label: class c is ``label[c] != 0``, num_classes must be None or L, lists may overlap.  ``image_mask`` keeps only
+        voxels with any_c(image > image_threshold) (MONAI's image_key / image_threshold).  Costs 4 bytes per listed voxel:
+        about one more image's worth per single-channel volume.  May synchronise; a second call with other arguments rebuilds."""
+        if num_classes is not None and not 1 <= int(num_classes) <= MAX_CLASSES:
+            raise ValueError(f"num_classes must be in 1..{MAX_CLASSES}, got {num_classes}")
+        cfg = (None if num_classes is None else int(num_classes), bool(image_mask))
+        for i, (_, L, *_dims) in enumerate(self.shapes):
+            _class_count_of(L, cfg[0], f"volume {i}")
+        if cfg != self._class_cfg:
+            self._class_cfg, self._classes, self._class_table = cfg, [], None
+        self._build_classes()
+
+    def _build_classes(self) -> None:
+        if self._class_cfg is None:
+            raise ValueError("no class lists: call build_class_indices() first")
+        num_classes, masked = self._class_cfg
+        dev = self.device
+        with torch.cuda.device(dev):
+            st = Fn._stream()
+            for i in range(len(self._classes), len(self._vols)):
+                img, lbl = self._vols[i][:2]
+                C, L, D, H, W = self.shapes[i]
+                K, V = _class_count_of(L, num_classes, f"volume {i}"), D * H * W
+                nws = load().unetr_aug_class_ws_ints(V, K)
+                ws = torch.empty(nws, dtype=torch.int32, device=dev)
+                offsets = torch.empty(K + 1, dtype=torch.int64, device=dev)
+                args = (img.data_ptr(), lbl.data_ptr(), C, L, K, V, int(masked), self.image_threshold, ws.data_ptr(), nws,
+                        offsets.data_ptr())
+                call("unetr_aug_class_count", *args, st)
+                off = offsets.tolist()
+                lists = torch.empty(max(off[K], 1), dtype=torch.int32, device=dev)
+                call("unetr_aug_class_scatter", *args, lists.data_ptr(), st)
+                self._classes.append((lists, offsets, [off[c + 1] - off[c] for c in range(K)]))
+                self._class_table = None
+
+    def _class_record(self, i: int):
+        if not 0 <= i < len(self._vols):
+            raise IndexError(f"volume {i} out of range")
+        self._build_classes()
+        return self._classes[i]
+
+    def class_indices(self, i: int, c: int) -> torch.Tensor:
+        """device int32 list of the voxels of class c in volume i (a view of the volume's concatenated lists)"""
+        lists, _, counts = self._class_record(i)
+        if not 0 <= c < len(counts):
+            raise IndexError(f"class {c} out of range")
+        start = sum(counts[:c])
+        return lists[start:start + counts[c]]
+
+    def class_counts(self, i: int):
+        """host list: the number of voxels of each class in volume i"""
+        return list(self._class_record(i)[2])
+
+    def class_offsets(self, i: int) -> torch.Tensor:
+        """device int64 [K + 1]: where each class list starts in the concatenated array; the last entry is the total"""
+        return self._class_record(i)[1]
+
+    def class_table(self) -> torch.Tensor:
+        """device int64 [n, 2] beside table(): pointer to the concatenated lists and to the offsets of every volume (a fresh
+        tensor after every build)"""
+        self._build_classes()
+        if self._class_table is None:
+            rows = [[lists.data_ptr(), offsets.data_ptr()] for lists, offsets, _ in self._classes]
+            self._class_table = torch.tensor(rows, dtype=torch.int64).to(self.device)
+        return self._class_table
+
+
+def _class_count_of(L: int, num_classes: Optional[int], what: str) -> int:
+    """K of a label with L channels under build_class_indices' rules"""
+    if L == 1:
+        if num_classes is None:
+            raise ValueError(f"{what}: a single-channel label holds class ids, num_classes is required")
+        return int(num_classes)
+    if num_classes is not None and int(num_classes) != L:
+        raise ValueError(f"{what}: a label of {L} channels has {L} classes, num_classes must be None or {L}, got {num_classes}")
+    return L
+
 
 def _triple(v, name):
     t = (v,) * 3 if isinstance(v, (int, float)) else tuple(v)
@@ -279,7 +370,19 @@ class RandCropAugment:
     stores its neutral value).  The draws are Philox blocks 5..7 of the sample's stream, the noise of voxel group g of channel c
     is block (n, s, 16 + c, 1 + g); ``params`` and ``affine`` do not move.  These semantics are this project's own (nnU-Net's
     operations, MONAI's formulas, float32 in a fixed order: DESIGN.md section 12, tests/augment_intensity_ref.py), NOT bit
-    parity with either.  With ``intensity=None`` the augment calls exactly the entry points it called before."""
+    parity with either.  With ``intensity=None`` the augment calls exactly the entry points it called before.
+
+    ``sampling="label_classes"`` (RandCropByLabelClassesd) centres each crop on a voxel of a class drawn by ``class_ratios``
+    (MONAI's ``ratios``; default all ones, nnU-Net's forced foreground over the classes present): ``num_classes`` is required
+    (1..32) for a single-channel label of class ids and must be None or L for a label of L > 1 channels; ``class_image_mask``
+    keeps only voxels with any_c(image > cache.image_threshold) (MONAI's image_key / image_threshold).  The lists come from
+    ``cache.build_class_indices`` (4 bytes per listed voxel).  A class without voxels in the sample's volume has weight 0; the
+    class is the first c with ``u * total < cum_c``.  Block 0 of the sample's Philox stream changes meaning in this mode only
+    (word 0 the class, word 1 the voxel of that class), so with the same seed every column of ``params`` but the corner, and
+    ``affine`` and ``intensity``, are what ``pos_neg`` writes.  ``aug.class_ratios`` [K] (float32, device) is read by the sampler
+    on every call: ``set_class_ratios`` checks host values, or write it on the device between replays of a captured call.
+    ``aug.classes`` [B] (int32) records the class drawn, -1 where no class was eligible and the corner was drawn uniformly.
+    The other modes call exactly the entry points they called before."""
 
     def __init__(self, cache: VolumeCache, spatial_size: Union[int, Sequence[int]] = 96, num_samples: int = 4, pos: float = 1,
                  neg: float = 1, sampling: str = "pos_neg", flip_prob: Union[float, Sequence[float], None] = (0.1, 0.1, 0.1),
@@ -288,7 +391,8 @@ class RandCropAugment:
                  seed: int = 0, batch_size: Optional[int] = None, order_capacity: Optional[int] = None,
                  affine_prob: float = 0.0, rotate_range: Union[float, Sequence[float], None] = None,
                  zoom_range: Optional[Sequence[float]] = None, zoom_per_axis: bool = False,
-                 intensity: Optional[IntensityAugment] = None):
+                 intensity: Optional[IntensityAugment] = None, num_classes: Optional[int] = None, class_ratios=None,
+                 class_image_mask: bool = False):
         if intensity is not None and not isinstance(intensity, IntensityAugment):
             raise ValueError(f"intensity must be an IntensityAugment or None, got {type(intensity).__name__}")
         S = tuple(int(s) for s in _triple(spatial_size, "spatial_size"))
@@ -301,6 +405,8 @@ class RandCropAugment:
             raise ValueError(f"batch_size ({B}) must be a positive multiple of num_samples ({num_samples})")
         if sampling not in SAMPLING_MODES:
             raise ValueError(f"sampling must be one of {SAMPLING_MODES}, got {sampling!r}")
+        if sampling != "label_classes" and (num_classes is not None or class_ratios is not None or class_image_mask):
+            raise ValueError('num_classes, class_ratios and class_image_mask belong to sampling="label_classes"')
         if pos < 0 or neg < 0:
             raise ValueError(f"pos and neg must be nonnegative, got pos={pos} neg={neg}")
         if pos + neg == 0:
@@ -346,6 +452,11 @@ class RandCropAugment:
                 raise ValueError(f"volume {i} of spatial shape {tuple(dims)} is smaller than the crop {S}")
             if float(affine_prob) > 0 and any(d > _MAXDIM_AFFINE for d in dims):
                 raise ValueError(f"volume {i} of spatial shape {tuple(dims)}: the affine gather supports extents up to 2**24")
+        K = 0
+        if sampling == "label_classes":
+            if num_classes is not None and not 1 <= int(num_classes) <= MAX_CLASSES:
+                raise ValueError(f"num_classes must be in 1..{MAX_CLASSES}, got {num_classes}")
+            K = _class_count_of(L, num_classes, "sampling='label_classes'")
         n = len(shapes)
         cap = max(n, 4096) if order_capacity is None else int(order_capacity)
         if cap < n:
@@ -398,6 +509,15 @@ class RandCropAugment:
             self.intensity = torch.zeros(B, INTENSITY_COLS, dtype=torch.int32, device=dev)
             self.intensity[:, 5:8] = 0x3F800000                                     # 1.0f: the neutral factors and gamma
             self._iws = torch.empty(load().unetr_aug_intensity_ws_bytes(ctypes.byref(d)), dtype=torch.uint8, device=dev)
+        self.num_classes = K
+        self.class_ratios = self.classes = None    # [K] float32 (read by the sampler on every call) and [B] int32 in label_classes mode
+        if K:
+            cache.build_class_indices(num_classes=None if L > 1 else K, image_mask=class_image_mask)
+            self._class_table = cache.class_table()
+            self._class_records = [cache._class_record(i) for i in range(n)]       # keeps this augment's lists alive
+            self.class_ratios = torch.ones(K, dtype=torch.float32, device=dev)
+            self.classes = torch.full((B,), -1, dtype=torch.int32, device=dev)
+            self.set_class_ratios(torch.ones(K) if class_ratios is None else class_ratios)
 
     # ---------------------------------------------------------------- schedule
     def set_order(self, ids) -> None:
@@ -410,6 +530,27 @@ class RandCropAugment:
             raise ValueError(f"volume ids must be in 0..{self.num_volumes - 1}")
         self._order[:h.numel()].copy_(ids.to(device=self.device, dtype=torch.int32))
         self._state[1:3].copy_(torch.tensor([0, h.numel()], dtype=torch.int64))
+
+    def set_class_ratios(self, ratios) -> None:
+        """the class ratios of sampling="label_classes" (MONAI's ``ratios``): [K] nonnegative weights, copied into the device
+        tensor ``class_ratios`` the sampler reads on every call, so a captured call follows them.  A host tensor or sequence is
+        checked: length K, finite, nonnegative, and every volume must hold a class with a positive ratio.  A device tensor is
+        copied without a synchronisation and unchecked: the sampler takes a negative or non-finite ratio as 0 and, for a
+        volume left without an eligible class, draws the corner uniformly (``classes`` = -1)."""
+        if self.class_ratios is None:
+            raise ValueError('class ratios need an augment built with sampling="label_classes"')
+        t = ratios if isinstance(ratios, torch.Tensor) else torch.as_tensor(ratios, dtype=torch.float32)
+        if tuple(t.shape) != (self.num_classes,):
+            raise ValueError(f"class_ratios: {self.num_classes} values (one per class) expected, got shape {tuple(t.shape)}")
+        if not t.is_cuda:
+            h = t.to(torch.float64)
+            if not bool(torch.isfinite(h).all()) or bool((h < 0).any()):
+                raise ValueError(f"class_ratios must be finite and nonnegative, got {h.tolist()}")
+            for i, (_, _, counts) in enumerate(self._class_records):
+                if not any(r > 0 and cnt > 0 for r, cnt in zip(h.tolist(), counts)):
+                    raise ValueError(f"class_ratios {h.tolist()}: volume {i} holds no voxel of a class with a positive ratio "
+                                     f"(class counts {counts})")
+        self.class_ratios.copy_(t.to(device=self.device, dtype=torch.float32), non_blocking=True)
 
     def reset(self, call: int = 0) -> None:
         """set the device call counter (the Philox counter of the next call) and rewind the cursor"""
@@ -443,14 +584,21 @@ class RandCropAugment:
         d = ctypes.byref(self._desc)
         if self.intensity is not None:         # before the sampler: it reads the call counter the sampler then advances
             call("unetr_aug_intensity_sample", d, ctypes.byref(self._idesc), self._state.data_ptr(), self.intensity.data_ptr(), st)
+        if self.classes is not None:
+            a = None if self.affine is None else ctypes.byref(self._adesc)
+            call("unetr_aug_sample_classes", d, a, self._table.data_ptr(), self.num_volumes, self._class_table.data_ptr(),
+                 self.num_classes, self.class_ratios.data_ptr(), self._order.data_ptr(), self._state.data_ptr(),
+                 self.params.data_ptr(), None if self.affine is None else self.affine.data_ptr(), self.classes.data_ptr(), st)
         if self.affine is None:
-            call("unetr_aug_sample", d, self._table.data_ptr(), self.num_volumes, self._order.data_ptr(), self._state.data_ptr(),
-                 self.params.data_ptr(), st)
+            if self.classes is None:
+                call("unetr_aug_sample", d, self._table.data_ptr(), self.num_volumes, self._order.data_ptr(), self._state.data_ptr(),
+                     self.params.data_ptr(), st)
             call("unetr_aug_gather", d, self._table.data_ptr(), self.num_volumes, self.params.data_ptr(), x.data_ptr(),
                  y.data_ptr(), self._ws.data_ptr(), self._ws.numel(), st)
         else:
-            call("unetr_aug_sample_affine", d, ctypes.byref(self._adesc), self._table.data_ptr(), self.num_volumes,
-                 self._order.data_ptr(), self._state.data_ptr(), self.params.data_ptr(), self.affine.data_ptr(), st)
+            if self.classes is None:
+                call("unetr_aug_sample_affine", d, ctypes.byref(self._adesc), self._table.data_ptr(), self.num_volumes,
+                     self._order.data_ptr(), self._state.data_ptr(), self.params.data_ptr(), self.affine.data_ptr(), st)
             call("unetr_aug_gather_affine", d, self._table.data_ptr(), self.num_volumes, self.params.data_ptr(),
                  self.affine.data_ptr(), x.data_ptr(), y.data_ptr(), self._ws.data_ptr(), self._ws.numel(), st)
         if self.intensity is not None:

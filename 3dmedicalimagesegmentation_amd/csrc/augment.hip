@@ -9,9 +9,15 @@
 //   aug_count_kernel     per chunk of AUG_CHUNK voxels the number of foreground / background voxels of map_binary_to_indices
 //   aug_scan_kernel      exclusive scan of the chunk counts (one workgroup) and the two totals
 //   aug_scatter_kernel   ordered compaction: each chunk again, AUG_CHUNK / 256 rounds of ballot + prefix, ascending ravel order
+// VolumeCache.build_class_indices (setup, may synchronise): map_classes_to_indices, the same trio for K <= 32 lists at once
+//   aug_class_count_kernel     per chunk the number of voxels of every class, from one read of the label: one ballot per class
+//   aug_class_scan_kernel      one workgroup per class: exclusive scan of its chunk counts and the list's length;
+//   aug_class_offsets_kernel   then where each list starts in the concatenated array (int64)
+//   aug_class_scatter_kernel   stable counting sort: chunk offset of the class + rank among the class's earlier voxels of the chunk
 // RandCropAugment.__call__ (per step: launches only, no host sync, no allocation):
 //   aug_sample_kernel    one workgroup: Philox4x64-10 draws, crop centres, the params table, counter and cursor advance;
-//                        <true> also draws the rotation / zoom of each sample and writes the affine table
+//                        <true, .> also draws the rotation / zoom of each sample and writes the affine table; <., true> takes
+//                        the crop centre from the list of a class drawn by the device ratios (RandCropByLabelClassesd)
 //   aug_gather_kernel    every output voxel back through rot90^k, the flips and the corner to its source voxel; C image
 //                        channels (+ shift) and L label bytes; with normalize also fp64 partial sums per workgroup;
 //                        <., true> takes the samples its affine table flags through the matrix to a position between
@@ -37,6 +43,8 @@ constexpr int AUG_MAXS = 512;         // crop extent per axis
 constexpr int AUG_NORM_WG = 64;       // workgroups per (sample, channel) of the normalize pass
 constexpr int AUG_ROW = 8;            // ints per params row: vol, z0, y0, x0, flip mask, k, shift flag, offset (float bits)
 constexpr int AUG_VCOLS = 12;         // int64 per volume table row: img, lbl, fg, nfg, bg, nbg, C, L, D, H, W, 0
+constexpr int AUG_MAXK = 32;          // classes of the per-class voxel lists (one bit each)
+constexpr int AUG_CCOLS = 2;          // int64 per class table row: concatenated lists (int32) ptr, offsets (int64 [K + 1]) ptr
 constexpr int AUG_AROW = 16;          // floats per affine row: flag, angle about axis 0, 1, 2, zoom of axis 0, 1, 2, M [3][3] row-major
 constexpr int AUG_BR0 = 8, AUG_BR1 = 16, AUG_BR2 = 16;   // output brick of one workgroup on a flagged sample (= AUG_TILE voxels)
 constexpr int AUG_MAXDIM_AFFINE = 1 << 24;               // extent up to which a float32 coordinate names every voxel
@@ -228,16 +236,160 @@ aug_scatter_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lb
     }
 }
 
+// ---------------------------------------------------------------- build_class_indices(): map_classes_to_indices as a stable counting sort
+// bit c of the result: the voxel is in the list of class c.  L == 1: class ids, an id >= K is in no list; L > 1 (K == L): channel
+// c is nonzero, lists may overlap.  masked: no list takes a voxel outside any_c(img > thr).
+__device__ __forceinline__ unsigned class_bits(const float* __restrict__ img, const uint8_t* __restrict__ lbl, int C, int L, int K,
+                                               long V, int masked, float thr, long v) {
+    unsigned bits = 0u;
+    if (L == 1) {
+        const int id = lbl[v];
+        if (id < K) bits = 1u << id;
+    } else {
+        for (int l = 0; l < L; ++l) bits |= (unsigned)(lbl[(long)l * V + v] != 0) << l;
+    }
+    if (masked && bits) {
+        bool any = false;
+        for (int c = 0; c < C; ++c) any |= img[(long)c * V + v] > thr;
+        if (!any) bits = 0u;
+    }
+    return bits;
+}
+
+// ws (ints): [cnt K][nblk][off K][nblk], class-major.  Lane c of every wave keeps the count of class c: one ballot per class
+// and round, no atomics.
+__global__ void __launch_bounds__(256)
+aug_class_count_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lbl, int C, int L, int K, long V, int masked,
+                       float thr, int* __restrict__ ws, int nblk) {
+    __shared__ int red[4][AUG_MAXK];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int mine = 0;
+    const long base = (long)blockIdx.x * AUG_CHUNK;
+    for (int i = 0; i < AUG_CHUNK / 256; ++i) {
+        const long v = base + i * 256 + threadIdx.x;
+        const unsigned bits = v < V ? class_bits(img, lbl, C, L, K, V, masked, thr, v) : 0u;
+        for (int c = 0; c < K; ++c) {
+            const int n = __popcll(__ballot(bits >> c & 1u));
+            if (lane == c) mine += n;
+        }
+    }
+    if (lane < K) red[wv][lane] = mine;
+    __syncthreads();
+    if (threadIdx.x < K)
+        ws[(long)threadIdx.x * nblk + blockIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+// one workgroup of 1024 threads per class, each as aug_scan_kernel takes one of its two lists: thread t scans a contiguous
+// segment, thread 0 the 1024 segment sums; the list's length goes to offsets[c + 1]
+__global__ void __launch_bounds__(1024) aug_class_scan_kernel(int* __restrict__ ws, int nblk, int K, long long* __restrict__ offsets) {
+    __shared__ int seg[1024];
+    const int per = (nblk + 1023) / 1024;
+    const int b0 = min(nblk, (int)threadIdx.x * per), b1 = min(nblk, b0 + per);
+    const int* cnt = ws + (long)blockIdx.x * nblk;
+    int* off = ws + ((long)K + blockIdx.x) * nblk;
+    int s = 0;
+    for (int b = b0; b < b1; ++b) s += cnt[b];
+    seg[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0;
+        for (int t = 0; t < 1024; ++t) { const int v = seg[t]; seg[t] = run; run += v; }
+        offsets[blockIdx.x + 1] = run;
+    }
+    __syncthreads();
+    int run = seg[threadIdx.x];
+    for (int b = b0; b < b1; ++b) { off[b] = run; run += cnt[b]; }
+}
+
+// offsets [K + 1] (int64) from the K list lengths the scan left in offsets[1..K]: where each list starts in the concatenated
+// array, in class order; offsets[K] is the total
+__global__ void aug_class_offsets_kernel(long long* __restrict__ offsets, int K) {
+    if (threadIdx.x == 0) {
+        long long run = 0;
+        offsets[0] = 0;
+        for (int c = 1; c <= K; ++c) { run += offsets[c]; offsets[c] = run; }
+    }
+}
+
+// The slot of a voxel in the list of its class: where the list starts (offsets), the scanned offset of the chunk, what earlier
+// rounds of the chunk put there (run), the waves before this one in the round (wtot) and the lanes below in the wave (ballot).
+// Every term counts voxels at lower ravel indices, so each list is ascending and the same on every run.
+__global__ void __launch_bounds__(256)
+aug_class_scatter_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lbl, int C, int L, int K, long V, int masked,
+                         float thr, const int* __restrict__ ws, int nblk, const long long* __restrict__ offsets,
+                         int* __restrict__ lists) {
+    __shared__ int wtot[AUG_MAXK][4];
+    __shared__ int run[AUG_MAXK];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if (threadIdx.x < K) run[threadIdx.x] = ws[((long)K + threadIdx.x) * nblk + blockIdx.x];
+    const long base = (long)blockIdx.x * AUG_CHUNK;
+    for (int i = 0; i < AUG_CHUNK / 256; ++i) {
+        const long v = base + i * 256 + threadIdx.x;
+        const unsigned bits = v < V ? class_bits(img, lbl, C, L, K, V, masked, thr, v) : 0u;
+        for (int c = 0; c < K; ++c) {
+            const int n = __popcll(__ballot(bits >> c & 1u));
+            if (lane == 0) wtot[c][wv] = n;
+        }
+        __syncthreads();
+        for (int c = 0; c < K; ++c) {
+            const unsigned long long m = __ballot(bits >> c & 1u);
+            if (bits >> c & 1u) {
+                int p = run[c] + __popcll(m & below);
+                for (int k = 0; k < wv; ++k) p += wtot[c][k];
+                lists[offsets[c] + p] = (int)v;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < K) run[threadIdx.x] += wtot[threadIdx.x][0] + wtot[threadIdx.x][1] + wtot[threadIdx.x][2] + wtot[threadIdx.x][3];
+        __syncthreads();                                     // the next round overwrites wtot
+    }
+}
+
 // ---------------------------------------------------------------- per call: sampler
 // state (int64): [call counter, cursor, len(order), 0]
 // AFFINE: block 3 word 0 flags the sample, words 1..3 are the angles about axes 0..2, block 4 words 0..2 the zooms (word 0
 // for all three unless zoom_per_axis); blocks 0..2 are drawn as without it.  Angles and zooms are lo + (hi - lo) * u in
 // double, stored as float32; M = (R0 . R1) . R2 . diag(1 / z) in double from the STORED values, rounded once.
-template <bool AFFINE>
+// CLASSES (RandCropByLabelClassesd, d.sampling == 2): block 0 word 0 picks the class by the DEVICE ratios, word 1 the voxel of
+// that class; every other word is drawn as without it.  affine may be null there: no block 3 / 4 draws, no affine table.
+struct AugClassArgs {
+    const long long* table;           // [nvol][AUG_CCOLS]
+    const float* ratios;              // [K], read on every call
+    int* classes;                     // [B]: the class drawn, -1 on the uniform fallback
+    int K;
+};
+
+// generate_label_classes_crop_centers for one sample: a class absent from the volume, or whose ratio is not a positive finite
+// number, has weight 0; the class is the first c with u * total < cum_c (sums in class order, double), the last weighted class
+// if rounding falls through; -1 when no class has weight, and the caller takes the uniform corner.  Never names an empty list.
+__device__ __forceinline__ int aug_pick_class(const float* __restrict__ ratios, const long long* __restrict__ offs, int K, double u) {
+#pragma clang fp contract(off)
+    double total = 0.0;
+    int last = -1;
+    for (int c = 0; c < K; ++c) {
+        const float r = ratios[c];
+        const double e = offs[c + 1] > offs[c] && r > 0.f && isfinite(r) ? (double)r : 0.0;
+        total += e;
+        if (e > 0.0) last = c;
+    }
+    if (last < 0) return -1;
+    const double t = u * total;
+    double cum = 0.0;
+    for (int c = 0; c < K; ++c) {
+        const float r = ratios[c];
+        const double e = offs[c + 1] > offs[c] && r > 0.f && isfinite(r) ? (double)r : 0.0;
+        cum += e;
+        if (e > 0.0 && t < cum) return c;
+    }
+    return last;
+}
+
+template <bool AFFINE, bool CLASSES>
 __global__ void __launch_bounds__(256)
 aug_sample_kernel(UnetrAugDesc d, UnetrAugAffineDesc af, const long long* __restrict__ vols, int nvol,
                   const int* __restrict__ order, long long* __restrict__ state, int* __restrict__ params,
-                  float* __restrict__ affine) {
+                  float* __restrict__ affine, AugClassArgs cl) {
 #pragma clang fp contract(off)
     const unsigned long long n = (unsigned long long)state[0];
     const long long cursor = state[1];
@@ -251,13 +403,23 @@ aug_sample_kernel(UnetrAugDesc d, UnetrAugAffineDesc af, const long long* __rest
         const long long dim[3] = {t[8], t[9], t[10]};
         const Ph4 w0 = aug_block(d.seed, n, s, 0), w1 = aug_block(d.seed, n, s, 1), w2 = aug_block(d.seed, n, s, 2);
         long long corner[3];
-        if (d.sampling == 0) {                               // RandCropByPosNegLabeld
+        long long idx = -1;                                  // the centre voxel; -1: draw the corner uniformly
+        if (CLASSES) {                                       // RandCropByLabelClassesd
+            const long long* ct = cl.table + (long)vol * AUG_CCOLS;
+            const long long* offs = (const long long*)ct[1];
+            const int cls = aug_pick_class(cl.ratios, offs, cl.K, u01(w0.v[0]));
+            if (cls >= 0)
+                idx = ((const int*)ct[0])[offs[cls] + randint(w0.v[1], (unsigned long long)(offs[cls + 1] - offs[cls]))];
+            cl.classes[s] = cls;
+        } else if (d.sampling == 0) {                        // RandCropByPosNegLabeld
             const long long nfg = t[3], nbg = t[5];
             const double pr = nfg == 0 ? 0.0 : (nbg == 0 ? 1.0 : d.pos_ratio);
             const bool pos = u01(w0.v[0]) < pr;
             const long long len = pos ? nfg : nbg;
             const int* list = (const int*)(pos ? t[2] : t[4]);
-            const long long idx = list[randint(w0.v[1], (unsigned long long)len)];
+            idx = list[randint(w0.v[1], (unsigned long long)len)];
+        }
+        if (idx >= 0) {
             const long long c[3] = {idx / (dim[1] * dim[2]), (idx / dim[2]) % dim[1], idx % dim[2]};
             for (int a = 0; a < 3; ++a) corner[a] = correct_center(c[a], S[a], dim[a]) - S[a] / 2;
         } else {                                             // RandSpatialCropSamplesd(random_size=False)
@@ -804,7 +966,7 @@ bool aug_desc_ok(const UnetrAugDesc* d) {
     for (int a = 0; a < 3; ++a) if (S[a] <= 0 || S[a] > AUG_MAXS) return false;
     if (d->ax0 < 0 || d->ax0 > 2 || d->ax1 < 0 || d->ax1 > 2 || d->ax0 == d->ax1 || S[d->ax0] != S[d->ax1]) return false;
     if (d->max_k <= 0 || d->B > 65535) return false;
-    return d->sampling == 0 || d->sampling == 1;
+    return d->sampling >= 0 && d->sampling <= 2;             // 2 (label classes) is drawn by unetr_aug_sample_classes alone
 }
 
 bool aug_affine_desc_ok(const UnetrAugAffineDesc* a) {
@@ -876,20 +1038,68 @@ extern "C" int unetr_aug_index_scatter(const float* img, const uint8_t* lbl, int
     return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
 }
 
+extern "C" long unetr_aug_class_ws_ints(long V, int K) {
+    return V <= 0 || K < 1 || K > AUG_MAXK ? 0 : 2L * K * cdiv(V, AUG_CHUNK);
+}
+
+static bool aug_class_args_ok(const float* img, const uint8_t* lbl, int C, int L, int K, long V, int image_mask) {
+    if (!lbl || (image_mask && !img) || C <= 0 || C > AUG_MAXC || L <= 0 || L > AUG_MAXC || V <= 0 || V > 0x7fffffffL) return false;
+    return K >= 1 && K <= AUG_MAXK && (L == 1 || K == L);
+}
+
+extern "C" int unetr_aug_class_count(const float* img, const uint8_t* lbl, int C, int L, int K, long V, int image_mask, float thr,
+                                     int* ws, size_t ws_ints, long long* offsets, void* stream) {
+    if (!aug_class_args_ok(img, lbl, C, L, K, V, image_mask) || !ws || !offsets) return UNETR_ERR_ARG;
+    if ((long)ws_ints < unetr_aug_class_ws_ints(V, K)) return UNETR_ERR_WORKSPACE;
+    const int nblk = cdiv(V, AUG_CHUNK);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(aug_class_count_kernel, dim3(nblk), dim3(256), 0, st, img, lbl, C, L, K, V, image_mask, thr, ws, nblk);
+    hipLaunchKernelGGL(aug_class_scan_kernel, dim3(K), dim3(1024), 0, st, ws, nblk, K, offsets);
+    hipLaunchKernelGGL(aug_class_offsets_kernel, dim3(1), dim3(64), 0, st, offsets, K);
+    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+}
+
+extern "C" int unetr_aug_class_scatter(const float* img, const uint8_t* lbl, int C, int L, int K, long V, int image_mask, float thr,
+                                       const int* ws, size_t ws_ints, const long long* offsets, int* lists, void* stream) {
+    if (!aug_class_args_ok(img, lbl, C, L, K, V, image_mask) || !ws || !offsets || !lists) return UNETR_ERR_ARG;
+    if ((long)ws_ints < unetr_aug_class_ws_ints(V, K)) return UNETR_ERR_WORKSPACE;
+    const int nblk = cdiv(V, AUG_CHUNK);
+    hipLaunchKernelGGL(aug_class_scatter_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, img, lbl, C, L, K, V, image_mask,
+                       thr, ws, nblk, offsets, lists);
+    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+}
+
 extern "C" int unetr_aug_sample(const UnetrAugDesc* d, const long long* vols, int nvol, const int* order, long long* state,
                                 int* params, void* stream) {
-    if (!aug_desc_ok(d) || !vols || nvol <= 0 || !order || !state || !params) return UNETR_ERR_ARG;
-    hipLaunchKernelGGL(aug_sample_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, *d, UnetrAugAffineDesc{}, vols, nvol,
-                       order, state, params, (float*)nullptr);
+    if (!aug_desc_ok(d) || d->sampling == 2 || !vols || nvol <= 0 || !order || !state || !params) return UNETR_ERR_ARG;
+    hipLaunchKernelGGL((aug_sample_kernel<false, false>), dim3(1), dim3(256), 0, (hipStream_t)stream, *d, UnetrAugAffineDesc{}, vols,
+                       nvol, order, state, params, (float*)nullptr, AugClassArgs{});
     return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
 }
 
 extern "C" int unetr_aug_sample_affine(const UnetrAugDesc* d, const UnetrAugAffineDesc* a, const long long* vols, int nvol,
                                        const int* order, long long* state, int* params, float* affine, void* stream) {
-    if (!aug_desc_ok(d) || !aug_affine_desc_ok(a) || !vols || nvol <= 0 || !order || !state || !params || !affine)
+    if (!aug_desc_ok(d) || d->sampling == 2 || !aug_affine_desc_ok(a) || !vols || nvol <= 0 || !order || !state || !params || !affine)
         return UNETR_ERR_ARG;
-    hipLaunchKernelGGL(aug_sample_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, *d, *a, vols, nvol, order, state,
-                       params, affine);
+    hipLaunchKernelGGL((aug_sample_kernel<true, false>), dim3(1), dim3(256), 0, (hipStream_t)stream, *d, *a, vols, nvol, order, state,
+                       params, affine, AugClassArgs{});
+    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+}
+
+extern "C" int unetr_aug_sample_classes(const UnetrAugDesc* d, const UnetrAugAffineDesc* a, const long long* vols, int nvol,
+                                        const long long* class_table, int K, const float* ratios, const int* order,
+                                        long long* state, int* params, float* affine, int* classes, void* stream) {
+    if (!aug_desc_ok(d) || d->sampling != 2 || !vols || nvol <= 0 || !class_table || K < 1 || K > AUG_MAXK || !ratios || !order ||
+        !state || !params || !classes)
+        return UNETR_ERR_ARG;
+    if ((a != nullptr) != (affine != nullptr) || (a && !aug_affine_desc_ok(a))) return UNETR_ERR_ARG;
+    const AugClassArgs cl{class_table, ratios, classes, K};
+    if (a)
+        hipLaunchKernelGGL((aug_sample_kernel<true, true>), dim3(1), dim3(256), 0, (hipStream_t)stream, *d, *a, vols, nvol, order,
+                           state, params, affine, cl);
+    else
+        hipLaunchKernelGGL((aug_sample_kernel<false, true>), dim3(1), dim3(256), 0, (hipStream_t)stream, *d, UnetrAugAffineDesc{},
+                           vols, nvol, order, state, params, (float*)nullptr, cl);
     return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
 }
 

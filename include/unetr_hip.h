@@ -586,7 +586,7 @@ int unetr_ranking_loss_bwd(const float* feat, int C, int S1, int S2, int S3, int
  * no contraction (csrc/augment.hip: aug_affine_taps).  Volume extents up to 2^24.  Its workspace has its own query. */
 typedef struct {
     int B, num_samples, C, L, S0, S1, S2;
-    int sampling;                     /* 0 RandCropByPosNegLabeld, 1 RandSpatialCropSamplesd */
+    int sampling;                     /* 0 RandCropByPosNegLabeld, 1 RandSpatialCropSamplesd, 2 RandCropByLabelClassesd (below) */
     int ax0, ax1;                     /* rot90 spatial axes (S[ax0] == S[ax1]) */
     int max_k, normalize;
     double pos_ratio;                 /* pos / (pos + neg) */
@@ -635,6 +635,29 @@ int unetr_aug_intensity_sample(const UnetrAugDesc* d, const UnetrAugIntensityDes
                                void* stream);
 size_t unetr_aug_intensity_ws_bytes(const UnetrAugDesc* d);
 int unetr_aug_intensity_apply(const UnetrAugDesc* d, const int* table, float* x, void* ws, size_t ws_bytes, void* stream);
+/* Class-balanced crop centres (MONAI 0.6.0 RandCropByLabelClassesd; DESIGN.md section 12, tests/augment_classes_ref.py).
+ * VolumeCache.build_class_indices: unetr_aug_class_count / _scatter build the voxel lists of map_classes_to_indices for K
+ * classes (1..32) from one read of the label per pass.  L == 1: class c is lbl == c, an id >= K is in no list; L > 1 (K must be
+ * L): class c is lbl[c] != 0, lists may overlap.  image_mask != 0 keeps only voxels with any_c(img > thr) (img may be NULL
+ * otherwise).  count writes offsets [K + 1] (DEVICE int64: cumulative list lengths in class order; offsets[K] is the total),
+ * scatter writes lists [offsets[K]] (int32): the K lists concatenated in class order, each in ascending ravel order, by a
+ * stable counting sort with no atomics.  ws of unetr_aug_class_ws_ints(V, K) ints, the same for both calls.
+ * unetr_aug_sample_classes is the sampler for UnetrAugDesc.sampling == 2 (which unetr_aug_sample / _affine refuse): it draws
+ * what they draw, except that block 0 word 0 picks the class of the centre and word 1 the voxel of that class.  class_table is a
+ * DEVICE table of int64 rows (lists ptr, offsets ptr), one per row of vols; ratios [K] is DEVICE float32, read on every call: a
+ * class without voxels in the volume, or whose ratio is not a positive finite number, has weight 0; the class is the first c with
+ * u * total < cum_c (double sums in class order).  With no weighted class the corner is uniform from words 0..2.  classes [B]
+ * (int32) records the class drawn, -1 for the uniform corner.  a and affine are both NULL (unetr_aug_sample's draws otherwise)
+ * or both given (unetr_aug_sample_affine's).  No host synchronisation.
+ * (Additions: no existing signature or struct moved, UNETR_ABI_VERSION stays.) */
+long unetr_aug_class_ws_ints(long V, int K);
+int unetr_aug_class_count(const float* img, const unsigned char* lbl, int C, int L, int K, long V, int image_mask, float thr,
+                          int* ws, size_t ws_ints, long long* offsets, void* stream);
+int unetr_aug_class_scatter(const float* img, const unsigned char* lbl, int C, int L, int K, long V, int image_mask, float thr,
+                            const int* ws, size_t ws_ints, const long long* offsets, int* lists, void* stream);
+int unetr_aug_sample_classes(const UnetrAugDesc* d, const UnetrAugAffineDesc* a, const long long* vols, int nvol,
+                             const long long* class_table, int K, const float* ratios, const int* order, long long* state,
+                             int* params, float* affine, int* classes, void* stream);
 
 /* ---- per-volume resampling and reorientation (csrc/preprocess.hip; unetr_segmentation_3d.py:326-331) ----
  * Spacingd(mode=("bilinear", "nearest")) -> Orientationd [-> ConvertToMultiChannelBasedOnBratsClassesd] as one gather: output voxel
