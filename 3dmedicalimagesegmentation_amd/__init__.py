@@ -7,6 +7,7 @@ The directory name starts with a digit, so import it with
 from .unetr import UNETR, UNETRLogits, default_precision  # noqa: F401
 from .losses import DiceCELoss, ranking_loss  # noqa: F401
 from .seg_losses import DiceFocalLoss, DiceLoss, FocalLoss, GeneralizedDiceLoss, SegLoss, TverskyLoss  # noqa: F401
+from .distance import BoundaryLoss, HausdorffDTLoss, distance_transform_edt, signed_distance_map  # noqa: F401
 from .optim import AdamW  # noqa: F401
 from .inference import DiceMetric, SlidingWindowInferer, sliding_window_inference  # noqa: F401
 from .metrics import (ConfusionMatrixMetric, HausdorffDistanceMetric, SurfaceDiceMetric, SurfaceDistanceMetric,  # noqa: F401
@@ -16,11 +17,12 @@ from .train_step import TrainStep  # noqa: F401
 from .augment import IntensityAugment, RandCropAugment, VolumeCache  # noqa: F401
 from .preprocess import Geometry, resample_orient, restore_native  # noqa: F401
 from .functional import invalidate_weight_shadows, refresh_derived_weights  # noqa: F401
-from . import _capi, augment, ddp, functional, inference, metrics, postprocess, preprocess, seg_losses, train_step  # noqa: F401
+from . import _capi, augment, ddp, distance, functional, inference, metrics, postprocess, preprocess, seg_losses, train_step  # noqa: F401
 
 __all__ = ["UNETR", "UNETRLogits", "DiceCELoss", "ranking_loss", "AdamW", "default_precision", "sliding_window_inference",
            "SlidingWindowInferer", "DiceMetric", "ConfusionMatrixMetric", "HausdorffDistanceMetric", "TrainStep", "invalidate_weight_shadows",
            "refresh_derived_weights",
            "VolumeCache", "RandCropAugment", "IntensityAugment", "resample_orient", "restore_native", "Geometry", "KeepLargestConnectedComponent", "connected_components",
            "remove_small_components", "surface_metrics", "SurfaceDistanceMetric", "SurfaceDiceMetric",
-           "SegLoss", "DiceLoss", "TverskyLoss", "GeneralizedDiceLoss", "FocalLoss", "DiceFocalLoss"]
+           "SegLoss", "DiceLoss", "TverskyLoss", "GeneralizedDiceLoss", "FocalLoss", "DiceFocalLoss",
+           "distance_transform_edt", "signed_distance_map", "BoundaryLoss", "HausdorffDTLoss"]

@@ -116,7 +116,17 @@ class SegLossDesc(ctypes.Structure):      # unetr_segloss_desc
                 ("lambda_region", c_float), ("lambda_voxel", c_float), ("class_weight", c_void_p)]
 
 
-SW_MAX_BATCH = 16                      # = UNETR_SW_MAX_BATCH
+class EdtDesc(ctypes.Structure):      # unetr_edt_desc
+    _fields_ = [("B", c_int), ("C", c_int), ("D", c_int), ("H", c_int), ("W", c_int),
+                ("form", c_int), ("field", c_int), ("squared", c_int), ("accumulate", c_int), ("has_spacing", c_int),
+                ("spacing", c_float * 3), ("alpha", c_float)]
+
+
+class DistLossDesc(ctypes.Structure):      # unetr_distloss_desc
+    _fields_ = [("B", c_int), ("C", c_int), ("V", c_long), ("multilabel", c_int), ("kind", c_int), ("include_background", c_int)]
+
+
+SW_MAX_BATCH = 16                     # = UNETR_SW_MAX_BATCH
 SW_ROW_INTS = 4 + 4 * SW_MAX_BATCH     # = UNETR_SW_ROW_INTS
 
 P = c_void_p
@@ -202,6 +212,9 @@ _SIGNATURES = {
     "unetr_dicece_bwd": [P, P, P, P, P, c_int, c_int, c_long, c_int, P],
     "unetr_segloss_fwd": [ctypes.POINTER(SegLossDesc), P, P, P, P, P, c_size_t, P],
     "unetr_segloss_bwd": [ctypes.POINTER(SegLossDesc), P, P, P, P, P, P],
+    "unetr_edt": [ctypes.POINTER(EdtDesc), P, P, P, c_size_t, P],
+    "unetr_distloss_fwd": [ctypes.POINTER(DistLossDesc), P, P, P, P, P, P, c_size_t, P],
+    "unetr_distloss_bwd": [ctypes.POINTER(DistLossDesc), P, P, P, P, P, P, P],
     "unetr_sw_accumulate": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
     "unetr_sw_finalize": [P, P, c_int, c_int, c_long, P],
     "unetr_dice_counts": [P, P, c_int, c_int, c_long, c_int, P, P, c_size_t, P],
@@ -241,7 +254,7 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES) + ("unetr_conv3_packed_bytes", "unetr_conv
                                             "unetr_conv3_wgrad_rows", "unetr_tconv2_wgrad_rows", "unetr_outconv_in_bwd_rows", "unetr_hausdorff_workspace_bytes",
                                             "unetr_aug_index_ws_ints", "unetr_aug_gather_ws_bytes", "unetr_aug_gather_affine_ws_bytes", "unetr_ccl_workspace_bytes",
                                             "unetr_surface_metrics_workspace_bytes", "unetr_aug_intensity_ws_bytes", "unetr_segloss_workspace_bytes",
-                                            "unetr_aug_class_ws_ints")
+                                            "unetr_aug_class_ws_ints", "unetr_edt_workspace_bytes", "unetr_distloss_workspace_bytes")
 
 _lib = None
 
@@ -295,6 +308,10 @@ def load():
     lib.unetr_aug_class_ws_ints.restype = c_long
     lib.unetr_segloss_workspace_bytes.argtypes = [ctypes.POINTER(SegLossDesc)]
     lib.unetr_segloss_workspace_bytes.restype = c_size_t
+    lib.unetr_edt_workspace_bytes.argtypes = [ctypes.POINTER(EdtDesc)]
+    lib.unetr_edt_workspace_bytes.restype = c_size_t
+    lib.unetr_distloss_workspace_bytes.argtypes = [ctypes.POINTER(DistLossDesc)]
+    lib.unetr_distloss_workspace_bytes.restype = c_size_t
     _lib = lib
     return lib
 

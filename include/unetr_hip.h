@@ -788,6 +788,59 @@ int unetr_gemm_bf16_grouped_wgrad_adamw_t(const unetr_grouped_problem* probs, in
                                           const int* step_index, void* shadow_t, void* stream);
 int unetr_transpose_bf16_grouped(const void* src_arena, void* dst_arena, const unetr_transpose_problem* probs, int n, void* stream);
 
+/* ---- dense exact Euclidean distance transform and the distance fields (csrc/edt.hip) -----------------------
+ * N = B*C binary masks [D,H,W], 1 <= C <= 16 and D, H, W <= 512 (else UNETR_ERR_UNSUPPORTED), derived from src inside the first pass:
+ *   MASK       float32 [B,C,D,H,W], the mask is one where the value != 0;      MASK_U8    the same from bytes (torch.bool / uint8)
+ *   CLASS_IDS  float32 class ids [B,D,H,W], the mask of channel c is one where (int)id == c
+ *   SOFTMAX    float32 logits [B,C,D,H,W], one where softmax over the channels > 0.5;      SIGMOID    where sigmoid > 0.5
+ * out [B,C,D,H,W] float32, every element written:
+ *   DISTANCE   the distance to the nearest voxel where the mask is 0 (0 on those voxels; squared = 1: its square); +inf everywhere
+ *              for a mask without a zero
+ *   SIGNED     d_fg outside the object, -(d_bg - u) inside it; d_fg / d_bg = the distance to the nearest voxel where the mask is
+ *              one / zero, u = 1 without a spacing, else the smallest spacing
+ *   UNSIGNED   (d_fg + d_bg)^alpha, alpha > 0; accumulate = 1 adds it to what out holds
+ *   SIGNED and UNSIGNED are 0 everywhere for a mask that is empty or fills the volume.
+ * spacing[3] = (z, y, x) voxel size when has_spacing, else 1.  float32 arithmetic: every term (s k)^2 with two roundings, the sum
+ * as (x + y) + z; exact integers without a spacing.
+ * ws: 16-byte aligned.  unetr_edt_workspace_bytes = what runs all B items in one group of three launches (0 for a descriptor that
+ * is refused); any ws that holds one item's share (that / B) is accepted and the items then run in groups.  Launches on one
+ * stream only: no allocation, no host synchronisation.
+ * (Additions: no existing signature moved, UNETR_ABI_VERSION stays.) */
+enum { UNETR_EDT_FORM_MASK = 0, UNETR_EDT_FORM_MASK_U8 = 1, UNETR_EDT_FORM_CLASS_IDS = 2, UNETR_EDT_FORM_SOFTMAX = 3,
+       UNETR_EDT_FORM_SIGMOID = 4 };
+enum { UNETR_EDT_FIELD_DISTANCE = 0, UNETR_EDT_FIELD_SIGNED = 1, UNETR_EDT_FIELD_UNSIGNED = 2 };
+typedef struct unetr_edt_desc {
+    int B, C, D, H, W;
+    int form, field, squared, accumulate, has_spacing;
+    float spacing[3];
+    float alpha;
+} unetr_edt_desc;
+size_t unetr_edt_workspace_bytes(const unetr_edt_desc* d);
+int unetr_edt(const unetr_edt_desc* d, const void* src, float* out, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- distance-map losses (csrc/dist_loss.hip) on logits [B,C,V] fp32, 1 <= C <= 16 -------------------------
+ * multilabel = 0: target [B,V] float class ids, p = softmax over the channels; multilabel = 1: target [B,C,V] float mask, p = sigmoid.
+ *   BOUNDARY   out[0] = *weight * mean over (b, included c, v) of p * field            (field = the SIGNED field of the target;
+ *                                                                                        target itself is not read and may be NULL)
+ *   HAUSDORFF  out[0] = *weight * mean over (b, included c, v) of (p - g)^2 * field    (field = UNSIGNED^alpha of the prediction
+ *                                                                                        mask + that of the target; no gradient)
+ * The mean runs over all channels, or 1..C-1 with include_background = 0 (C >= 2); an excluded channel still takes part in the
+ * softmax.  weight: one float32 in device memory, read when the kernels run.  ws: 16-byte aligned, unetr_distloss_workspace_bytes.
+ * Fixed-order partial sums, finalized by one block in double: reproducible run to run, no float atomics.
+ * unetr_distloss_bwd: dlogits = *dloss (device scalar; NULL = 1) * dout[0]/dlogits, every element written.
+ * Launches only: no allocation, no host synchronisation.  (Additions: no existing signature moved, UNETR_ABI_VERSION stays.) */
+enum { UNETR_DISTLOSS_BOUNDARY = 0, UNETR_DISTLOSS_HAUSDORFF = 1 };
+typedef struct unetr_distloss_desc {
+    int B, C;
+    long V;
+    int multilabel, kind, include_background;
+} unetr_distloss_desc;
+size_t unetr_distloss_workspace_bytes(const unetr_distloss_desc* d);
+int unetr_distloss_fwd(const unetr_distloss_desc* d, const float* logits, const float* target, const float* field,
+                       const float* weight, float* out, void* ws, size_t ws_bytes, void* stream);
+int unetr_distloss_bwd(const unetr_distloss_desc* d, const float* logits, const float* target, const float* field,
+                       const float* weight, const float* dloss, float* dlogits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
