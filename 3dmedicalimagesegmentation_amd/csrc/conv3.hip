@@ -22,7 +22,9 @@
 // ds_read_b32 per element does the same.  Accumulators for (tap, ci-tile) pairs stay in registers while the
 // workgroup walks many voxel tiles; per-workgroup partial sums are reduced in a fixed order.
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 #include "common.hpp"
 #include "../../include/unetr_hip.h"
@@ -585,10 +587,17 @@ __device__ __forceinline__ void flush_stats(int cur_b, bool with3, f32x4 (&rs1)[
 //   WL 0: weights from global / L2 per tap group with a one-group register prefetch (kept for NTB 4 with several slabs, where
 //         two images do not fit).  That path exposes an L2 round trip per group of three taps: at 12^3 x 256 channels, where
 //         one workgroup per CU leaves nothing to hide it, a slab took 10 us for 108 MFMAs per wave.
-template <int NTB, int WL> constexpr int conv_pipe_lds_bytes(int pitch) { return NHALO * pitch + WL * 27 * NTB * 1024; }
+//   WL 1 with more than one slab: ONE image refilled per slab -- the DMA is issued when every wave has left the previous slab's
+//         MFMA phase and lands under the window store, so part of its latency is exposed; in exchange NTB 4 keeps its weights in LDS
+//         (149.5 KB) where WL 0 pays an L2 round trip per tap.  Which of the forms a launch gets: slab_pick() below.
+constexpr int conv_pipe_lds_bytes(int ntb, int wl) { return NHALO * 64 + wl * 27 * ntb * 1024; }
+// workgroups per CU a variant is built for (the host sizes its grid by the same number)
+constexpr int conv_pipe_wg_per_cu(bool pair, int ntb, int wl, int fuse) {
+    return ((pair || conv_pipe_lds_bytes(ntb, wl) <= 80 * 1024) &&
+            (fuse == 2 ? (pair && ntb == 1) : (fuse == 3 ? ntb == 1 : (fuse == 1 && (ntb == 1 || (!pair && ntb == 2)))))) ? 2 : 1;
+}
 template <class P, int NTB, bool PAIR, int XM, int FUSE, int WL = 0>
-__global__ void __launch_bounds__(256, ((PAIR || conv_pipe_lds_bytes<NTB, WL>(64) <= 80 * 1024) &&
-                                        (FUSE == 2 ? (PAIR && NTB == 1) : (FUSE == 3 ? NTB == 1 : (FUSE == 1 && (NTB == 1 || (!PAIR && NTB == 2)))))) ? 2 : 1)
+__global__ void __launch_bounds__(256, conv_pipe_wg_per_cu(PAIR, NTB, WL, FUSE))
 conv3_fwd_pipe_kernel(const void* __restrict__ x, long ldx, const char* __restrict__ wp, typename ActOf<P>::type* __restrict__ y, long ldy, int accumulate,
                       int D, int H, int W, int Cin, int Cout, int ntx, int nty, int ntz, int ntiles,
                       float* __restrict__ part, const char* __restrict__ wp3, typename ActOf<P>::type* __restrict__ y3, long ldy3,
@@ -778,6 +787,7 @@ conv3_fwd_pipe_kernel(const void* __restrict__ x, long ldx, const char* __restri
             if constexpr (BST) xn_load();
           } else {
             __syncthreads();                       // everyone is done reading the previous window
+            if constexpr (WLN == 1) { if (wrot && wit > 0) wdma(slab, 0); }      // single image: refilled now that nobody reads it
             if constexpr (XM == 2) halo_store_planned<P, NCH>(R, plan, halo);    // (waits for the prefetched loads)
             else halo_store<P, NCH, XM, LAY>(R, PITCH, halo);
             if constexpr (WLN > 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's weight DMA pieces have landed
@@ -791,7 +801,7 @@ conv3_fwd_pipe_kernel(const void* __restrict__ x, long ldx, const char* __restri
                 int ntile = tile, nslb = slab + 1;
                 if (nslb == nslab) { ntile = tile + gridDim.x; nslb = 0; }
                 if constexpr (WLN > 0) {
-                    if (wrot && ntile < ntiles) wdma(nslb, (wit + 1) & 1);      // (that image was last read before the barrier above)
+                    if (WLN == 2 && wrot && ntile < ntiles) wdma(nslb, (wit + 1) & 1);      // (that image was last read before the barrier above)
                 }
                 if (ntile < ntiles) {
                     int ax = tx, ay = ty, az = tz, ab = b;
@@ -842,7 +852,7 @@ conv3_fwd_pipe_kernel(const void* __restrict__ x, long ldx, const char* __restri
                 }
             } else if constexpr (WLN > 0) {
                 const int xo3[3] = {lay_off<LAY>(r, g, PITCH), lay_off<LAY>(r + 1, g, PITCH), lay_off<LAY>(r + 2, g, PITCH)};
-                const char* wb = wlds + (wrot ? (wit & 1) : slab) * WBYTES + lane * 16;
+                const char* wb = wlds + (WLN == 1 ? 0 : (wrot ? (wit & 1) : slab)) * WBYTES + lane * 16;
                 if constexpr (has3) {
 #pragma unroll
                     for (int j = 0; j < NTB; ++j) w3res[j] = *(const u32x4*)(wp3 + ((long)slab * Cout + (nt0 + j) * 16 + r) * 64 + g * 16);
@@ -1974,6 +1984,87 @@ int pack_t(const float* w, void* wp, int Cin, int Cout, int mode, hipStream_t st
 // k3 > 0: FUSE 4 (y3 = second input); bst: FUSE 5 (y3 = the pre-norm tensor xn, wp3 = its statistics, part = backward-statistics rows)
 struct FuseArgs { float* part; const void* wp3; void* y3; long ldy3; float* part3; int rows; int k3; int bst = 0; };
 
+// ---- slab-mode dispatch of conv3_fwd_pipe_kernel: output tiles per workgroup (ntb), weight images (wl), grid -----------------
+// resident = workgroups the chip really holds of the chosen variant: CUs x min(what its __launch_bounds__ asks for, what its LDS
+// bytes leave room for in 160 KB).  grid.x * grid.y never exceeds it -- a longer grid queues behind the resident workgroups and
+// ends in a partly filled round -- and the tiles are dealt round-robin (tile = blockIdx.x + k * grid.x), so the walks of two
+// workgroups differ by at most one tile.
+constexpr int PIPE_CUS = 256;
+// output tiles per workgroup of the generic rule: as many workgroups as possible up to 512
+inline int generic_ntb(long spatial, int ntn) {
+    int ntb = 1;
+    if ((ntn & (ntn - 1)) == 0) {  // power of two
+        ntb = std::min(ntn, 8);
+        while (ntb > 1 && spatial * (ntn / ntb) < 512) ntb >>= 1;
+    }
+    return ntb;
+}
+struct SlabPick { int ntb, wl, gx, gy, resident, lds; };
+inline int slab_resident(int ntb, int wl, int fuse) {
+    const int lds = conv_pipe_lds_bytes(ntb, wl);
+    return PIPE_CUS * std::min(conv_pipe_wg_per_cu(false, ntb, wl, fuse), 160 * 1024 / lds);
+}
+// grid.x for `spatial` tiles under a cap of resident workgroups: the fewest tiles per workgroup the cap allows, then the fewest
+// workgroups that still reach it (fewer weight fills, the same makespan); a multiple of the 8 XCDs whenever a workgroup walks
+// more than one tile (tile_coords keeps a walk in batch order only then: the fused statistics are flushed per batch item)
+inline long balanced_gx(long spatial, long cap) {
+    if (cap >= spatial) return spatial;
+    cap = std::max<long>(8, cap / 8 * 8);
+    const long walk = cdiv(spatial, cap);
+    return std::min<long>(cap, cdiv(cdiv(spatial, walk), 8) * 8);
+}
+// Volumes of fewer than 512 tiles (the 12^3 and 24^3 decoder levels at batch 2): every (tile, slab) step of a workgroup costs a
+// fixed part (window and weight fill, two barriers, the exposed end of the prefetch) plus a part per output tile, and a workgroup
+// that holds a CU alone hides neither.  Measured per launch, us, 20 launches in one hipGraph (profiles/lowres_conv_rounds.txt;
+// "2 img" = WL 2, "1 img" = WL 1; grids as this function sizes them; * = what the rule below picks):
+//   launch (contraction -> outputs, FUSE)   previous      ntb 1, 2 img  ntb 1, 1 img  ntb 2, 2 img  ntb 2, 1 img  ntb 4, WL 0  ntb 4, 1 img
+//   12^3 256 -> 128, FUSE 2                 45.7 (18x8)   45.8          43.7 *        54.9          53.2          112.5        73.8
+//   12^3 128 -> 128, FUSE 1                 23.8 (18x8)   23.7          23.3 *        28.5          28.1           57.8        39.4
+//   12^3 128 -> 128, FUSE 5                 24.4 (18x8)   24.6          24.1 *        29.5          29.0           61.4        41.8
+//   12^3 128 -> 256, FUSE 4                 49.3 (18x16)  43.6 (16x16)  42.3          37.4          36.9 *         70.9        48.1
+//   24^3 128 -> 64,  FUSE 2                 61.7 (144x4)  55.5 (48x4)   52.6          53.5 (72x2)   52.2           72.7        50.5 * (144x1)
+//   24^3  64 -> 64,  FUSE 1                 36.0 (144x4)  30.8 (48x4)   29.4 (72x4)   29.1 (72x2)   28.9           36.5        27.9 * (144x1)
+//   24^3  64 -> 64,  FUSE 5                 38.8 (144x4)  33.1 (48x4)   31.6          31.3 (72x2)   30.9           39.2        30.1 * (144x1)
+//   24^3  64 -> 128, FUSE 4                 52.8 (144x4)  53.6 (32x8)   51.2          45.4 (48x4)   44.6 *         59.7        47.7 (72x2)
+// One image refilled per slab is never slower than two; WL 0 (weights from L2 per tap) is the slowest form everywhere.  Among
+// ntb 1 / 2 / 4 the fastest is the one with the smallest  tiles walked per CU x (1 + ntb)  -- the fixed part of a step weighs about
+// as much as one output tile -- with the larger ntb on a tie; that product reproduces the order of all eight rows.
+// ntb0: the generic rule's choice, kept for volumes of 512 tiles and more.
+// UNETR_CONV3_SLAB_CFG (tuning hook, and the way back to the previous dispatch for the bit-equality tests): "old", or
+// "ntb[,wl[,gx]]" -- ntb 1 / 2 / 4, wl 0 / 1 / 2 weight images, gx an upper bound on grid.x; 0 / -1 / 0 = this rule's own value.
+inline SlabPick slab_pick(long spatial, int ntn, int nslab, int fuse, int ntb0) {
+    const char* e = getenv("UNETR_CONV3_SLAB_CFG");
+    if ((e && !strcmp(e, "old")) || spatial >= 512) {
+        // many tiles per workgroup (48^3 and up at batch 2), where a part-filled last round is a small share of a long walk:
+        // grid.x capped at 256 / 512 by the LDS bytes alone, grid.y on top of it (the grids those layers were tuned at)
+        int wl = nslab == 1 ? 1 : 2;
+        if (conv_pipe_lds_bytes(ntb0, wl) > 160 * 1024) wl = 0;
+        const bool two = conv_pipe_lds_bytes(ntb0, wl) <= 80 * 1024;
+        long cap = test_max_wg(two ? 512 : 256);
+        if (cap < spatial) cap = std::max<long>(8, cap / 8 * 8);
+        return SlabPick{ntb0, wl, (int)std::min(spatial, cap), ntn / ntb0, slab_resident(ntb0, wl, fuse), conv_pipe_lds_bytes(ntb0, wl)};
+    }
+    int ntb = 1, wl = 1;
+    long best = -1, gxf = 0;
+    for (int t = 1; t <= 4; t <<= 1) {
+        if (ntn % t) continue;
+        const long cost = (long)cdiv(spatial * (ntn / t), PIPE_CUS) * (1 + t);
+        if (best < 0 || cost <= best) { best = cost; ntb = t; }
+    }
+    if (e) {
+        int a = 0, b = -1, c = 0;
+        sscanf(e, "%d,%d,%d", &a, &b, &c);
+        if ((a == 1 || a == 2 || a == 4) && ntn % a == 0) ntb = a;
+        if (nslab > 1 && ((b == 2 && ntb <= 2) || (b == 0 && ntb == 4))) wl = b;      // (the forms that are instantiated)
+        gxf = c;
+    }
+    SlabPick p{ntb, wl, 0, ntn / ntb, slab_resident(ntb, wl, fuse), conv_pipe_lds_bytes(ntb, wl)};
+    long cap = test_max_wg(std::max<long>(1, p.resident / p.gy));
+    if (gxf > 0) cap = std::min(cap, gxf);
+    p.gx = (int)balanced_gx(spatial, cap);
+    return p;
+}
+
 // x_f32: the input tensor is fp32 even in bf16 mode (the image in front of encoder1: <= 16 channels, pair layout only)
 template <class P>
 int fwd_t(const void* x, long ldx, const void* wp, void* yv, long ldy, int accumulate, int B, int D, int H, int W, int Cin, int Cout,
@@ -1984,19 +2075,16 @@ int fwd_t(const void* x, long ldx, const void* wp, void* yv, long ldy, int accum
     const int ntx = cdiv(W, TX), nty = cdiv(H, TY), ntz = cdiv(D, TZ);
     const long spatial = (long)B * ntx * nty * ntz;
     const int ntn = Cout / 16;
-    int ntb = 1;
-    if ((ntn & (ntn - 1)) == 0) {  // power of two
-        ntb = std::min(ntn, 8);
-        while (ntb > 1 && spatial * (ntn / ntb) < 512) ntb >>= 1;
-    }
-    int xm = (((uintptr_t)x & 15) == 0 && (ldx & 3) == 0 && (Cin & 3) == 0) ? 1 : 0;
+    int ntb = generic_ntb(spatial, ntn);
+    int xm =(((uintptr_t)x & 15) == 0 && (ldx & 3) == 0 && (Cin & 3) == 0) ? 1 : 0;
     if (B16 && !x_f32) {
         if (((uintptr_t)x & 15) || (ldx & 7) || (Cin & 7)) return UNETR_ERR_UNSUPPORTED;     // bf16 rows: whole 16-byte pieces
         xm = 2;
     }
     if (B16 && fz && fz->k3 > 0 && ((fz->ldy3 & 7) || ((uintptr_t)fz->y3 & 15) || (fz->k3 & 7))) return UNETR_ERR_UNSUPPORTED;
     if ((long)D * H * W * ldx >= (1L << 31)) return UNETR_ERR_UNSUPPORTED;      // 32-bit in-item offsets (halo_load)
-    // persistent grid: at most cap resident workgroups.  A workgroup that walks several
+    // grid.x of a persistent grid (the image kernel, pair mode): at most cap workgroups along the tile walk.  It bounds grid.x
+    // alone -- a grid.y > 1 multiplies on top of it (slab mode sizes both: slab_pick).  A workgroup that walks several
     // tiles must see them in non-decreasing batch order (the fused statistics are flushed when the batch item changes): tile_coords
     // guarantees that for grids that are multiples of the 8 XCDs
     auto grid_x = [&](long cap) {
@@ -2026,13 +2114,16 @@ int fwd_t(const void* x, long ldx, const void* wp, void* yv, long ldy, int accum
         // the transposed accumulator tile is stored four channels (8 / 16 bytes) per lane
         if ((ldy & 3) || ((uintptr_t)y & (B16 ? 7 : 15)) || (fz && fz->k3 == 0 && fz->y3 && ((uintptr_t)fz->y3 & (B16 ? 7 : 15)))) return UNETR_ERR_UNSUPPORTED;
         if (pair && ntb > 2) ntb = 2;
-        // slab mode: weights resident in LDS (see the kernel); two workgroups per CU only while a workgroup stays under 80 KB
-        const int nslab = cdiv(Cin, 4 * P::CH);
-        int wl = pair ? 0 : (nslab == 1 ? 1 : 2);
-        if (!pair && NHALO * 64 + wl * 27 * ntb * 1024 > 160 * 1024) wl = 0;
-        const bool two = pair || NHALO * 64 + wl * 27 * ntb * 1024 <= 80 * 1024;
-        // resident workgroups (VGPR / LDS-limited); more would queue behind them
-        dim3 pgrid(grid_x(two ? 512 : 256), ntn / ntb);
+        const bool late1x1 = Cin <= 4 * P::CH;      // single-slab window: the 1x1x1 product is formed after the tile (FUSE 3)
+        // pair mode: two workgroups per CU.  Slab mode: weights resident in LDS (see the kernel), form and grid by slab_pick
+        int wl = 0;
+        dim3 pgrid(grid_x(512), ntn / ntb);
+        if (!pair) {
+            const int fuse = !fz ? 0 : (fz->k3 > 0 ? 4 : (fz->bst ? 5 : (fz->wp3 ? (late1x1 ? 3 : 2) : 1)));
+            const SlabPick sp = slab_pick(spatial, ntn, cdiv(Cin, 4 * P::CH), fuse, ntb);
+            ntb = sp.ntb; wl = sp.wl;
+            pgrid = dim3((unsigned)sp.gx, (unsigned)sp.gy);
+        }
 #define LAUNCH_PIPE_F(NTB_, PAIR_, XM_, FUSE_, WL_)                                                                               \
     hipLaunchKernelGGL((conv3_fwd_pipe_kernel<P, NTB_, PAIR_, XM_, FUSE_, WL_>), pgrid, dim3(256), 0, st, x, ldx, (const char*)wp, y, ldy, \
                        accumulate, D, H, W, Cin, Cout, ntx, nty, ntz, (int)spatial, fz ? fz->part : nullptr,                       \
@@ -2065,7 +2156,6 @@ int fwd_t(const void* x, long ldx, const void* wp, void* yv, long ldy, int accum
         else if constexpr (NTB_ == 4) { if (wl == 1) LAUNCH_PIPE_W(4, false, 1); else LAUNCH_PIPE_W(4, false, 0); }                \
         else { if (wl == 1) LAUNCH_PIPE_W(NTB_, false, 1); else LAUNCH_PIPE_W(NTB_, false, 2); }                                   \
     } while (0)
-        const bool late1x1 = Cin <= 4 * P::CH;      // single-slab window: the 1x1x1 product is formed after the tile (FUSE 3)
         if (fz && fz->k3 == 0) fz->rows = (int)pgrid.x;          // one partial row per workgroup and batch item, zeroed in-kernel
         if constexpr (P::CH == 8) {
             if (pair) {
@@ -2376,6 +2466,23 @@ extern "C" long unetr_conv3_wgrad_rows(int B, int D, int H, int W, int Cin, int 
         PREC_DISPATCH(prec, return wgrad_t<P>(dummy, ldx, dummy, Cout, nullptr, has3 ? dummy : nullptr, Cout, nullptr, B, D, H, W, Cin, Cout, nullptr, 0, nullptr, x_f32, true, &rows));
     };
     return run() == UNETR_OK ? rows : -1;
+}
+
+// what a slab-mode forward / data-gradient launch of this shape is dispatched as (no launch, no device needed): out = {output tiles
+// per workgroup, weight images, grid.x, grid.y, resident workgroups of that variant, its LDS bytes}.  Cin = contraction channels,
+// Cout = produced channels (a data gradient passes them swapped, as its entry point does); fuse = the kernel's FUSE code.
+// UNETR_ERR_UNSUPPORTED: the shape does not take the slab-mode persistent kernel.
+extern "C" int unetr_conv3_slab_dispatch(int B, int D, int H, int W, int Cin, int Cout, int prec, int fuse, int* out) {
+    if (!out || B <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || fuse < 0 || fuse > 5) return UNETR_ERR_ARG;
+    if (prec != UNETR_PREC_BF16 && prec != UNETR_PREC_F32 && prec != UNETR_PREC_BF16X3) return UNETR_ERR_ARG;
+    const int SL = prec == UNETR_PREC_BF16 ? 32 : 16;
+    const int ntx = cdiv(W, TX), nty = cdiv(H, TY), ntz = cdiv(D, TZ), ntn = Cout / 16;
+    const long spatial = (long)B * ntx * nty * ntz;
+    const int ntb0 = generic_ntb(spatial, ntn);
+    if (Cout % 16 || (prec == UNETR_PREC_BF16 && Cin <= 16) || ntb0 > 4 || ntx > 255 || nty > 255 || ntz > 255 || B > 255) return UNETR_ERR_UNSUPPORTED;
+    const SlabPick sp = slab_pick(spatial, ntn, cdiv(Cin, SL), fuse, ntb0);
+    out[0] = sp.ntb; out[1] = sp.wl; out[2] = sp.gx; out[3] = sp.gy; out[4] = sp.resident; out[5] = sp.lds;
+    return UNETR_OK;
 }
 
 // unetr_conv3_wgrad without its reduce launch: the per-workgroup partial sums stay in `part` -- [rows][27 Cin Cout] followed, when dy3

@@ -303,6 +303,13 @@ int unetr_conv3_dgrad_fused(const void* dc1, long ld1, const void* wpack_dgrad, 
                             const void* w3pack_t /* optional: kind-3 pack of w3 (unetr_conv3_pack_grouped); NULL = packed here from w3 */,
                             void* dx, long lddx, int B, int D, int H, int W, int Cin, int Cout, int prec,
                             float* ws, size_t ws_bytes, void* stream);
+/* Query, no launch and no device: how a forward / data-gradient launch with >= 32 (bf16) / any (fp32, bf16x3) contraction channels
+ * Cin and Cout produced channels is dispatched.  fuse: 0 plain, 1 statistics, 2 / 3 statistics + 1x1x1 branch (Cin > / <= one
+ * k-block), 4 unetr_conv3_dgrad_fused, 5 unetr_conv3_dgrad_stats (the data gradients pass the conv's Cout as Cin here).
+ * out[6] = {output tiles of 16 channels per workgroup, weight images in LDS, grid.x (= partial rows), grid.y, workgroups of that
+ * kernel variant the chip holds at once, LDS bytes of its window and weight images}; grid.x * grid.y <= out[4] whenever the volume has fewer than 512 tiles.
+ * (Addition: no existing signature moved, UNETR_ABI_VERSION stays.) */
+int unetr_conv3_slab_dispatch(int B, int D, int H, int W, int Cin, int Cout, int prec, int fuse, int* out);
 /* All weight re-packs of a step in one launch (descriptors in the kernel arguments, <= 64 per launch).  kind 0 / 1: what
  * unetr_conv3_pack_weight(mode 0 / 1) writes; kind 2: unetr_conv3_pack_1x1; kind 3: the transposed 1x1x1 layout that
  * unetr_conv3_dgrad_fused builds internally.  `out` buffers sized by unetr_conv3_packed_bytes / _packed_1x1_bytes. */
