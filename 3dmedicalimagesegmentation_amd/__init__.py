@@ -8,6 +8,7 @@ from .unetr import UNETR, UNETRLogits, default_precision  # noqa: F401
 from .losses import DiceCELoss, ranking_loss  # noqa: F401
 from .seg_losses import DiceFocalLoss, DiceLoss, FocalLoss, GeneralizedDiceLoss, SegLoss, TverskyLoss  # noqa: F401
 from .distance import BoundaryLoss, HausdorffDTLoss, distance_transform_edt, signed_distance_map  # noqa: F401
+from .topk_loss import DiceTopKLoss, TopKLoss, kth_value, percentile  # noqa: F401
 from .optim import AdamW  # noqa: F401
 from .inference import DiceMetric, SlidingWindowInferer, sliding_window_inference  # noqa: F401
 from .metrics import (ConfusionMatrixMetric, HausdorffDistanceMetric, SurfaceDiceMetric, SurfaceDistanceMetric,  # noqa: F401
@@ -17,7 +18,7 @@ from .train_step import TrainStep  # noqa: F401
 from .augment import IntensityAugment, RandCropAugment, VolumeCache  # noqa: F401
 from .preprocess import Geometry, resample_orient, restore_native  # noqa: F401
 from .functional import invalidate_weight_shadows, refresh_derived_weights  # noqa: F401
-from . import _capi, augment, ddp, distance, functional, inference, metrics, postprocess, preprocess, seg_losses, train_step  # noqa: F401
+from . import _capi, augment, ddp, distance, functional, inference, metrics, postprocess, preprocess, seg_losses, topk_loss, train_step  # noqa: F401
 
 __all__ = ["UNETR", "UNETRLogits", "DiceCELoss", "ranking_loss", "AdamW", "default_precision", "sliding_window_inference",
            "SlidingWindowInferer", "DiceMetric", "ConfusionMatrixMetric", "HausdorffDistanceMetric", "TrainStep", "invalidate_weight_shadows",
@@ -25,4 +26,5 @@ __all__ = ["UNETR", "UNETRLogits", "DiceCELoss", "ranking_loss", "AdamW", "defau
            "VolumeCache", "RandCropAugment", "IntensityAugment", "resample_orient", "restore_native", "Geometry", "KeepLargestConnectedComponent", "connected_components",
            "remove_small_components", "surface_metrics", "SurfaceDistanceMetric", "SurfaceDiceMetric",
            "SegLoss", "DiceLoss", "TverskyLoss", "GeneralizedDiceLoss", "FocalLoss", "DiceFocalLoss",
-           "distance_transform_edt", "signed_distance_map", "BoundaryLoss", "HausdorffDTLoss"]
+           "distance_transform_edt", "signed_distance_map", "BoundaryLoss", "HausdorffDTLoss",
+           "TopKLoss", "DiceTopKLoss", "kth_value", "percentile"]

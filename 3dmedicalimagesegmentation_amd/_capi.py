@@ -126,6 +126,17 @@ class DistLossDesc(ctypes.Structure):      # unetr_distloss_desc
     _fields_ = [("B", c_int), ("C", c_int), ("V", c_long), ("multilabel", c_int), ("kind", c_int), ("include_background", c_int)]
 
 
+class TopKCEDesc(ctypes.Structure):      # unetr_topkce_desc
+    _fields_ = [("B", c_int), ("C", c_int), ("V", c_long), ("multilabel", c_int), ("has_ignore", c_int), ("ignore_index", c_int),
+                ("class_weight", c_void_p)]
+
+
+class SelectResult(ctypes.Structure):      # unetr_select_result
+    _fields_ = [("value", c_float), ("n_beyond", ctypes.c_uint), ("n_equal", ctypes.c_uint)]
+
+
+SELECT_LARGEST, SELECT_PLAIN_HIST = 1, 2      # = UNETR_SELECT_*
+
 SW_MAX_BATCH = 16                     # = UNETR_SW_MAX_BATCH
 SW_ROW_INTS = 4 + 4 * SW_MAX_BATCH     # = UNETR_SW_ROW_INTS
 
@@ -216,6 +227,9 @@ _SIGNATURES = {
     "unetr_edt": [ctypes.POINTER(EdtDesc), P, P, P, c_size_t, P],
     "unetr_distloss_fwd": [ctypes.POINTER(DistLossDesc), P, P, P, P, P, P, c_size_t, P],
     "unetr_distloss_bwd": [ctypes.POINTER(DistLossDesc), P, P, P, P, P, P, P],
+    "unetr_select_kth": [P, c_long, P, c_int, c_int, P, P, c_size_t, P],
+    "unetr_topkce_fwd": [ctypes.POINTER(TopKCEDesc), P, P, P, P, P, P, P, c_size_t, P],
+    "unetr_topkce_bwd": [ctypes.POINTER(TopKCEDesc), P, P, P, P, P, P, P],
     "unetr_sw_accumulate": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
     "unetr_sw_finalize": [P, P, c_int, c_int, c_long, P],
     "unetr_dice_counts": [P, P, c_int, c_int, c_long, c_int, P, P, c_size_t, P],
@@ -255,7 +269,8 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES) + ("unetr_conv3_packed_bytes", "unetr_conv
                                             "unetr_conv3_wgrad_rows", "unetr_tconv2_wgrad_rows", "unetr_outconv_in_bwd_rows", "unetr_hausdorff_workspace_bytes",
                                             "unetr_aug_index_ws_ints", "unetr_aug_gather_ws_bytes", "unetr_aug_gather_affine_ws_bytes", "unetr_ccl_workspace_bytes",
                                             "unetr_surface_metrics_workspace_bytes", "unetr_aug_intensity_ws_bytes", "unetr_segloss_workspace_bytes",
-                                            "unetr_aug_class_ws_ints", "unetr_edt_workspace_bytes", "unetr_distloss_workspace_bytes")
+                                            "unetr_aug_class_ws_ints", "unetr_edt_workspace_bytes", "unetr_distloss_workspace_bytes",
+                                            "unetr_select_workspace_bytes", "unetr_topkce_workspace_bytes")
 
 _lib = None
 
@@ -313,6 +328,10 @@ def load():
     lib.unetr_edt_workspace_bytes.restype = c_size_t
     lib.unetr_distloss_workspace_bytes.argtypes = [ctypes.POINTER(DistLossDesc)]
     lib.unetr_distloss_workspace_bytes.restype = c_size_t
+    lib.unetr_select_workspace_bytes.argtypes = [c_long]
+    lib.unetr_select_workspace_bytes.restype = c_size_t
+    lib.unetr_topkce_workspace_bytes.argtypes = [ctypes.POINTER(TopKCEDesc)]
+    lib.unetr_topkce_workspace_bytes.restype = c_size_t
     _lib = lib
     return lib
 

@@ -25,6 +25,7 @@ memory (``aug.class_ratios``), so a captured call can be steered between replays
 import ctypes
 import dataclasses
 import math
+import struct
 from typing import Optional, Sequence, Tuple, Union
 
 import torch
@@ -74,9 +75,20 @@ class VolumeCache:
         return len(self._vols)
 
     def add(self, image: torch.Tensor, label: torch.Tensor, scale_range: Optional[Sequence[float]] = None,
-            crop_foreground: bool = False) -> int:
+            crop_foreground: bool = False, scale_percentiles: Optional[Sequence[float]] = None) -> int:
         """ScaleIntensityRanged(a_min, a_max, b_min, b_max, clip=True) when scale_range is given, CropForegroundd(source_key=
-        "image", margin=0) when crop_foreground, then the index lists; returns the volume's id.  May synchronise."""
+        "image", margin=0) when crop_foreground, then the index lists; returns the volume's id.  May synchronise.
+        scale_percentiles=(lower, upper, b_min, b_max): ScaleIntensityRangePercentilesd(lower, upper, b_min, b_max, clip=True,
+        relative=False) as MONAI 0.6.0 is recalled to define it (parity-unpinned): a_min / a_max are the two percentiles of the
+        whole image as given, before the foreground crop (topk_loss.percentile, rounded to float32), then the scale_range path."""
+        if scale_percentiles is not None:
+            if scale_range is not None:
+                raise ValueError("scale_range and scale_percentiles exclude each other")
+            lower, upper, pb_min, pb_max = (float(v) for v in scale_percentiles)
+            if not (0.0 <= lower <= 100.0 and 0.0 <= upper <= 100.0):
+                raise ValueError(f"scale_percentiles: percentages in [0, 100] expected, got {lower}, {upper}")
+            if lower >= upper:
+                raise ValueError(f"scale_percentiles: lower < upper expected, got {lower} >= {upper}")
         if image.dim() != 4 or label.dim() != 4 or image.shape[1:] != label.shape[1:]:
             raise ValueError(f"image [C,D,H,W] and label [L,D,H,W] with the same spatial shape expected, got "
                              f"{tuple(image.shape)} and {tuple(label.shape)}")
@@ -92,6 +104,10 @@ class VolumeCache:
             img = image.detach().to(device=dev, dtype=torch.float32, copy=True).contiguous()
             lbl = label.detach().to(device=dev, dtype=torch.float32).contiguous()
             mode, consts = 0, (0.0, 1.0, 1.0, 0.0, 0.0)
+            if scale_percentiles is not None:
+                from .topk_loss import percentile
+                a_min, a_max = (struct.unpack("f", struct.pack("f", v))[0] for v in percentile(img, (lower, upper)).tolist())
+                scale_range = (a_min, a_max, pb_min, pb_max)
             if scale_range is not None:
                 a_min, a_max, b_min, b_max = (float(v) for v in scale_range)
                 mode = 2 if a_max - a_min == 0.0 else 1

@@ -848,6 +848,60 @@ int unetr_distloss_fwd(const unetr_distloss_desc* d, const float* logits, const 
 int unetr_distloss_bwd(const unetr_distloss_desc* d, const float* logits, const float* target, const float* field,
                        const float* weight, const float* dloss, float* dlogits, void* stream);
 
+/* ---- exact order statistic of an fp32 array (csrc/select.hip): a radix select over the bit pattern -----------
+ * x[n] fp32, contiguous, 1 <= n < 2^31 (else UNETR_ERR_UNSUPPORTED), any alignment (16-byte loads when n % 4 == 0 and x is 16-byte
+ * aligned, one element per thread otherwise).  The 0-based rank r is read from device memory (*rank, clamped to [0, n-1]) WHEN THE
+ * KERNELS RUN; rank == NULL takes rank_host (0 <= rank_host < n) instead.  flags: UNETR_SELECT_LARGEST = r-th largest, else r-th
+ * smallest; UNETR_SELECT_PLAIN_HIST = the first histogram pass without its LDS-contention remedy (a measurement switch, same result).
+ * Order: the keys  bits ^ (sign ? 0xFFFFFFFF : 0x80000000)  as unsigned integers -- negatives, -0 < +0, denormals and +-inf are all
+ * ordered, NaNs sort at the two ends.
+ * out (device memory): value = the element of that rank; n_beyond = elements strictly beyond it on the selected side (greater for
+ * LARGEST, smaller otherwise); n_equal = elements with the same bits.
+ * Six launches on `stream` -- init, four 8-bit histogram passes (each picks its predecessor's digit in its prologue), final pick --
+ * with integer counts only: bitwise reproducible; no allocation, no host synchronisation, no data-dependent loop, no hand-off
+ * between workgroups inside a kernel.  ws: 16-byte aligned, unetr_select_workspace_bytes(n) = (4*256 + 16) * 4 = 4160 bytes (0 for an
+ * n that is refused); the init launch zeroes every histogram word that is read, so the scratch may hold anything.
+ * (Additions: no existing signature moved, UNETR_ABI_VERSION stays.) */
+enum { UNETR_SELECT_LARGEST = 1, UNETR_SELECT_PLAIN_HIST = 2 };
+typedef struct unetr_select_result {
+    float value;
+    unsigned n_beyond, n_equal;
+} unetr_select_result;
+size_t unetr_select_workspace_bytes(long n);
+int unetr_select_kth(const float* x, long n, const int* rank, int rank_host, int flags, unetr_select_result* out, void* ws,
+                     size_t ws_bytes, void* stream);
+
+/* ---- top-k cross entropy (csrc/topk_loss.hip) on logits [B,C,V] fp32, 1 <= C <= 16 and B*V < 2^31 (else UNETR_ERR_UNSUPPORTED) ---
+ * multilabel = 0: label [B,V] float class ids; multilabel = 1: mask [B,C,V], the class of a voxel is the FIRST argmax of its mask
+ * (as seg_loss.hip).  Per-voxel value  u_v = w[y_v] * (logf(sum_c e^(z_c - max)) - (z_y - max)),  w = class_weight [C] (non-negative,
+ * device memory, multilabel = 0 only) or NULL = 1; with has_ignore (multilabel = 0 only) a voxel labelled ignore_index has no value
+ * and no gradient.
+ *   N = number of voxels with a value over the WHOLE batch (all B*V),  K = max(1, floor((double)N * (double)*k / 100.0)),
+ *   k = a percentage in (0, 100], one float32 in device memory, read when the kernels run (N and K are computed on the device);
+ *   t = the K-th largest value, n_gt = #{u > t}, n_eq = #{u == t};
+ *   X = (sum_{u > t} u + (K - n_gt) * t) / K    (= torch.topk(u, K).values.mean()), summed in a fixed order, finalized in double;
+ *   dX/du_v = 1/K where u > t, (K - n_gt) / (n_eq * K) where u == t, 0 elsewhere: ties at the threshold share the remaining weight
+ *   equally (deterministic, no indices; differs from topk's arbitrary pick only on exact ties).
+ * unetr_topkce_fwd: values [B*V] floats receives u (an ignored voxel: -1) and is kept for backward together with coef [4] =
+ *   {1/K, (K - n_gt)/(n_eq K), t, 0}; out [4] = {X, t, K, N}.  Ten launches: values, rank, the six of unetr_select_kth, sum, final.
+ *   ws: 16-byte aligned, unetr_topkce_workspace_bytes = 4160 (the select's) + 32 + 4 * B * ceil(V / 1024) + 4 * ceil(B*V / 4096),
+ *   rounded up to a multiple of 16 (0 for a descriptor that is refused).
+ * unetr_topkce_bwd: dlogits = *dloss (device scalar; NULL = 1) * dX/du_v * w_y * (softmax - onehot), every element written; it
+ *   compares the bits of `values` with t, never a recomputed value.
+ * Launches only: no allocation, no host synchronisation, no float atomics.  (Additions: no existing signature moved,
+ * UNETR_ABI_VERSION stays.) */
+typedef struct unetr_topkce_desc {
+    int B, C;
+    long V;
+    int multilabel, has_ignore, ignore_index;
+    const float* class_weight;
+} unetr_topkce_desc;
+size_t unetr_topkce_workspace_bytes(const unetr_topkce_desc* d);
+int unetr_topkce_fwd(const unetr_topkce_desc* d, const float* logits, const float* label, const float* k, float* values, float* out,
+                     float* coef, void* ws, size_t ws_bytes, void* stream);
+int unetr_topkce_bwd(const unetr_topkce_desc* d, const float* logits, const float* label, const float* values, const float* coef,
+                     const float* dloss, float* dlogits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
