@@ -174,6 +174,28 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ double wave_max_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_sum_u(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// ---- the radix select of select.hip, for the kernels that compare values in its order or lay its scratch into their workspace
+// (topk_loss.hip).  Order key of an fp32 bit pattern: unsigned, ascending in the total order select.hip's header describes; flip =
+// 0xFFFFFFFF turns "r-th largest" into "r-th smallest".
+__device__ __forceinline__ uint32_t sel_key(uint32_t bits, uint32_t flip) {
+    return (bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u)) ^ flip;
+}
+constexpr int SEL_BINS = 256;
+constexpr int SEL_PASSES = 4;
+constexpr int SEL_HIST_WORDS = SEL_PASSES * SEL_BINS;
+constexpr int SEL_STATE_WORDS = 16;                 // state[p] = (prefix, rank) for p = 0..3, padded
+constexpr size_t SEL_WS_BYTES = (size_t)(SEL_HIST_WORDS + SEL_STATE_WORDS) * sizeof(uint32_t);      // = unetr_select_workspace_bytes
 
 // ---- AdamW element update (torch.optim.AdamW: decoupled weight decay, bias-corrected moments), shared by the streaming optimizer
 // kernel (norm_misc.hip) and the fused epilogue of the grouped ViT weight gradient (gemm_bf16.hip) so that both give the same bits

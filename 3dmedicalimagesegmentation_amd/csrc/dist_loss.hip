@@ -14,12 +14,11 @@
 // iteration otherwise), one float partial per block from a fixed shuffle / LDS tree, then one block that adds the partials in
 // double in a fixed order: reproducible run to run, no float atomics.  Backward: one pass, one voxel per thread, as
 // segloss_bwd_kernel (its 16-byte form was measured slower there for its occupancy: profiles/seg_loss.txt, section 4).
-// Every access is bounded by V.
-#include "common.hpp"
+// Every access is bounded by V.  Channel dispatch, base pointers, alignment rule, softmax exponentials and block tails: voxel_loss.hpp.
+#include "voxel_loss.hpp"
 
 namespace {
 
-constexpr int MAXC = 16;
 constexpr int FVPB = 4096;  // voxels per forward block (one partial each)
 constexpr int BVPB = 256;   // voxels per backward block: one per thread
 
@@ -29,12 +28,8 @@ __device__ __forceinline__ void probs(const float (&z)[C], float (&p)[C]) {
 #pragma unroll
         for (int c = 0; c < C; ++c) p[c] = 1.f / (1.f + expf(-z[c]));
     } else {
-        float mx = -3.0e38f, se = 0.f;
-#pragma unroll
-        for (int c = 0; c < C; ++c) mx = fmaxf(mx, z[c]);
-#pragma unroll
-        for (int c = 0; c < C; ++c) { p[c] = expf(z[c] - mx); se += p[c]; }
-        const float inv = 1.f / se;
+        float mx;
+        const float inv = 1.f / softmax_exp<C>(z, p, mx);
 #pragma unroll
         for (int c = 0; c < C; ++c) p[c] *= inv;
     }
@@ -66,13 +61,13 @@ distloss_fwd_kernel(const float* __restrict__ logits, const float* __restrict__ 
     __shared__ float red[4];
     const int b = blockIdx.y;
     const long v0 = (long)blockIdx.x * FVPB, v1 = std::min<long>(V, v0 + FVPB);
-    const float* lg = logits + (long)b * C * V;
-    const float* fd = field + (long)b * C * V;
-    const bool need_t = kind == UNETR_DISTLOSS_HAUSDORFF;
-    const float* tg = need_t ? target + (SIG ? (long)b * C * V : (long)b * V) : nullptr;
+    const float* lg = item_channels<C>(logits, b, V);
+    const float* fd = item_channels<C>(field, b, V);
+    const bool need_t = kind == UNETR_DISTLOSS_HAUSDORFF;      // the boundary loss never reads the target
+    const float* tg = need_t ? item_target<C, SIG>(target, b, V) : nullptr;
     float acc = 0.f;
-    const bool vec = (V & 3) == 0 && ((((uintptr_t)logits) | ((uintptr_t)field) | (need_t ? (uintptr_t)target : 0)) & 15) == 0;
-    if (vec) {
+    // its own walk: a third tensor, read for the included channels only, and a target that only one of the two kinds reads
+    if (vec4_ok(V, logits, field, need_t ? target : nullptr)) {
         for (long v = v0 + 4 * threadIdx.x; v < v1; v += 1024) {
             f32x4 zv[C], av[C], tv[SIG ? C : 1];
 #pragma unroll
@@ -111,10 +106,7 @@ distloss_fwd_kernel(const float* __restrict__ logits, const float* __restrict__ 
             acc += fwd_voxel<C, SIG>(z, t, a, kind, c0);
         }
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    acc = wave_sum(acc);
-    if (lane == 0) red[wave] = acc;
-    __syncthreads();
+    block_wave_sums<1>(&acc, red);
     if (threadIdx.x == 0) part[(long)b * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
@@ -126,9 +118,7 @@ distloss_final_kernel(const float* __restrict__ part, long npart, const float* _
     __shared__ double sh[FIN_WAVES];
     double s = 0.0;
     for (long i = threadIdx.x; i < npart; i += FIN_THREADS) s += (double)part[i];
-    s = wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
+    block_wave_sums<1>(&s, sh);
     if (threadIdx.x == 0) {
         s = 0.0;
         for (int w = 0; w < FIN_WAVES; ++w) s += sh[w];
@@ -145,9 +135,9 @@ distloss_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ 
     const int b = blockIdx.y;
     const long v = (long)blockIdx.x * BVPB + threadIdx.x;
     if (v >= V) return;
-    const float* lg = logits + (long)b * C * V;
-    const float* fd = field + (long)b * C * V;
-    float* dl = dlogits + (long)b * C * V;
+    const float* lg = item_channels<C>(logits, b, V);
+    const float* fd = item_channels<C>(field, b, V);
+    float* dl = item_channels<C>(dlogits, b, V);
     const float sc = (dloss ? *dloss : 1.f) * weight[0] * inv_count;
     float z[C], p[C], a[C];
 #pragma unroll
@@ -157,7 +147,7 @@ distloss_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ 
     }
     probs<C, SIG>(z, p);
     if (kind == UNETR_DISTLOSS_HAUSDORFF) {
-        const float* tg = target + (SIG ? (long)b * C * V : (long)b * V);
+        const float* tg = item_target<C, SIG>(target, b, V);
         const int lab = SIG ? -1 : (int)tg[v];
 #pragma unroll
         for (int c = 0; c < C; ++c) {
@@ -178,8 +168,7 @@ distloss_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ 
 }
 
 int check_desc(const unetr_distloss_desc* d) {
-    if (!d || d->B <= 0 || d->V <= 0 || d->B > 65535) return UNETR_ERR_ARG;
-    if (d->C < 1 || d->C > MAXC) return UNETR_ERR_UNSUPPORTED;
+    if (int rc = check_voxel_desc(d)) return rc;
     if (d->kind != UNETR_DISTLOSS_BOUNDARY && d->kind != UNETR_DISTLOSS_HAUSDORFF) return UNETR_ERR_ARG;
     if (!d->include_background && d->C == 1) return UNETR_ERR_ARG;
     return UNETR_OK;
@@ -190,15 +179,6 @@ double mean_count(const unetr_distloss_desc* d) {
 }
 
 }  // namespace
-
-#define DIST_DISPATCH(C_, CALL) \
-    switch (C_) {               \
-        case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break;       \
-        case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; case 8: CALL(8); break;       \
-        case 9: CALL(9); break; case 10: CALL(10); break; case 11: CALL(11); break; case 12: CALL(12); break; \
-        case 13: CALL(13); break; case 14: CALL(14); break; case 15: CALL(15); break; case 16: CALL(16); break; \
-        default: return UNETR_ERR_UNSUPPORTED;                                                                \
-    }
 
 extern "C" size_t unetr_distloss_workspace_bytes(const unetr_distloss_desc* d) {
     if (check_desc(d) != UNETR_OK) return 0;
@@ -214,9 +194,8 @@ extern "C" int unetr_distloss_fwd(const unetr_distloss_desc* d, const float* log
     const long V = d->V;
     float* part = (float*)ws;
     hipStream_t st = (hipStream_t)stream;
-#define CALL_F(CC) hipLaunchKernelGGL((distloss_fwd_kernel<CC, false>), dim3(nchunk, B), dim3(256), 0, st, logits, target, field, V, kind, c0, part)
-#define CALL_FS(CC) hipLaunchKernelGGL((distloss_fwd_kernel<CC, true>), dim3(nchunk, B), dim3(256), 0, st, logits, target, field, V, kind, c0, part)
-    if (d->multilabel) { DIST_DISPATCH(d->C, CALL_FS) } else { DIST_DISPATCH(d->C, CALL_F) }
+    VOXEL_DISPATCH(d->C, d->multilabel, hipLaunchKernelGGL((distloss_fwd_kernel<CC, SIG>), dim3(nchunk, B), dim3(256), 0, st, logits, target,
+                                                           field, V, kind, c0, part));
     hipLaunchKernelGGL(distloss_final_kernel, dim3(1), dim3(FIN_THREADS), 0, st, part, (long)B * nchunk, weight, mean_count(d), out);
     return unetr_check_launch();
 }
@@ -229,8 +208,7 @@ extern "C" int unetr_distloss_bwd(const unetr_distloss_desc* d, const float* log
     const long V = d->V;
     const float inv_count = (float)(1.0 / mean_count(d));
     hipStream_t st = (hipStream_t)stream;
-#define CALL_B(CC) hipLaunchKernelGGL((distloss_bwd_kernel<CC, false>), dim3(nblk, B), dim3(256), 0, st, logits, target, field, weight, dloss, inv_count, dlogits, V, kind, c0)
-#define CALL_BS(CC) hipLaunchKernelGGL((distloss_bwd_kernel<CC, true>), dim3(nblk, B), dim3(256), 0, st, logits, target, field, weight, dloss, inv_count, dlogits, V, kind, c0)
-    if (d->multilabel) { DIST_DISPATCH(d->C, CALL_BS) } else { DIST_DISPATCH(d->C, CALL_B) }
+    VOXEL_DISPATCH(d->C, d->multilabel, hipLaunchKernelGGL((distloss_bwd_kernel<CC, SIG>), dim3(nblk, B), dim3(256), 0, st, logits, target,
+                                                           field, weight, dloss, inv_count, dlogits, V, kind, c0));
     return unetr_check_launch();
 }

@@ -12,14 +12,13 @@
 // logits against argmax_c(target) (first maximal channel, torch.argmax's rule).
 //
 // HBM-bound: one pass over logits+label for the forward (fixed-order partial buffers -> reproducible), one
-// pass for the backward that recomputes the softmax and writes dlogits.
+// pass for the backward that recomputes the softmax and writes dlogits.  Channel dispatch, base pointers, alignment rule, target
+// decode and softmax exponentials: voxel_loss.hpp.
 #include <algorithm>
-#include "common.hpp"
-#include "../../include/unetr_hip.h"
+#include "voxel_loss.hpp"
 
 namespace {
 
-constexpr int MAXC = 16;
 constexpr int LVPB = 4096;  // voxels per block
 
 template <int C, bool SIG>
@@ -29,27 +28,25 @@ dicece_fwd_kernel(const float* __restrict__ logits, const float* __restrict__ la
     __shared__ float red[4][3 * C + 1];
     const int b = blockIdx.y;
     const long v0 = (long)blockIdx.x * LVPB, v1 = std::min<long>(V, v0 + LVPB);
+    const float* lg = item_channels<C>(logits, b, V);
+    const float* lb = item_target<C, SIG>(label, b, V);
     float accI[C], accP[C], accG[C], ce = 0.f;
 #pragma unroll
     for (int c = 0; c < C; ++c) { accI[c] = 0.f; accP[c] = 0.f; accG[c] = 0.f; }
     // softmax / one-hot form on whole 4-voxel groups: one 16-byte load per channel and for the labels, all of an iteration's loads
     // in flight together (one voxel per iteration was 16 dependent memory round trips per thread: 19 us for 35 MB)
-    const bool vec = !SIG && (V & 3) == 0 && ((((uintptr_t)logits) | ((uintptr_t)label)) & 15) == 0;
-    if (vec) {
+    if (!SIG && vec4_ok(V, logits, label)) {
         for (long v = v0 + 4 * threadIdx.x; v < v1; v += 1024) {      // (LVPB and V are multiples of 4: whole groups)
             f32x4 zv[C];
 #pragma unroll
-            for (int c = 0; c < C; ++c) zv[c] = *(const f32x4*)(logits + ((long)b * C + c) * V + v);
-            const f32x4 lv = *(const f32x4*)(label + (long)b * V + v);
+            for (int c = 0; c < C; ++c) zv[c] = *(const f32x4*)(lg + (long)c * V + v);
+            const f32x4 lv = *(const f32x4*)(lb + v);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float z[C], mx = -3.0e38f;
+                float z[C], mx;
 #pragma unroll
-                for (int c = 0; c < C; ++c) { z[c] = zv[c][e]; mx = fmaxf(mx, z[c]); }
-                float se = 0.f;
-#pragma unroll
-                for (int c = 0; c < C; ++c) { z[c] = expf(z[c] - mx); se += z[c]; }
-                const float inv = 1.f / se;
+                for (int c = 0; c < C; ++c) z[c] = zv[c][e];
+                const float inv = 1.f / softmax_exp<C>(z, z, mx);
                 const int lab = (int)lv[e];
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
@@ -61,30 +58,23 @@ dicece_fwd_kernel(const float* __restrict__ logits, const float* __restrict__ la
         }
     } else
     for (long v = v0 + threadIdx.x; v < v1; v += 256) {
-        float z[C], mx = -3.0e38f;
+        float x[C], z[C], mx;
 #pragma unroll
-        for (int c = 0; c < C; ++c) { z[c] = logits[((long)b * C + c) * V + v]; mx = fmaxf(mx, z[c]); }
-        float se = 0.f;
-#pragma unroll
-        for (int c = 0; c < C; ++c) { z[c] = expf(z[c] - mx); se += z[c]; }
-        const float inv = 1.f / se;
+        for (int c = 0; c < C; ++c) x[c] = lg[(long)c * V + v];
+        const float inv = 1.f / softmax_exp<C>(x, z, mx);
         if constexpr (SIG) {
-            float t[C], tmax = -3.0e38f;
-            int lab = 0;
+            float t[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) t[c] = lb[(long)c * V + v];
+            const int lab = mask_argmax<C>(t);
 #pragma unroll
             for (int c = 0; c < C; ++c) {
-                t[c] = label[((long)b * C + c) * V + v];
-                if (t[c] > tmax) { tmax = t[c]; lab = c; }
-            }
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const float x = logits[((long)b * C + c) * V + v];
-                const float sg = 1.f / (1.f + expf(-x));
+                const float sg = 1.f / (1.f + expf(-x[c]));
                 accP[c] += sg; accI[c] += sg * t[c]; accG[c] += t[c];
                 if (c == lab) ce -= logf(z[c] * inv);
             }
         } else {
-            const int lab = (int)label[(long)b * V + v];
+            const int lab = (int)lb[v];
 #pragma unroll
             for (int c = 0; c < C; ++c) {
                 float p = z[c] * inv;
@@ -153,83 +143,67 @@ dicece_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ la
     const long total = (long)B * V;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int b = (int)(i / V); const long v = i - (long)b * V;
-        float z[C], mx = -3.0e38f;
+        const float* lg = item_channels<C>(logits, b, V);
+        const float* lb = item_target<C, SIG>(label, b, V);
+        float* dl = item_channels<C>(dlogits, b, V);
+        const float* cf = coef + (long)b * C * 2;
+        float x[C], z[C], mx;
 #pragma unroll
-        for (int c = 0; c < C; ++c) { z[c] = logits[((long)b * C + c) * V + v]; mx = fmaxf(mx, z[c]); }
-        float se = 0.f;
-#pragma unroll
-        for (int c = 0; c < C; ++c) { z[c] = expf(z[c] - mx); se += z[c]; }
-        const float inv = 1.f / se;
+        for (int c = 0; c < C; ++c) x[c] = lg[(long)c * V + v];
+        const float inv = 1.f / softmax_exp<C>(x, z, mx);
         if constexpr (SIG) {
-            float t[C], tmax = -3.0e38f;
-            int lab = 0;
+            float t[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) t[c] = lb[(long)c * V + v];
+            const int lab = mask_argmax<C>(t);
 #pragma unroll
             for (int c = 0; c < C; ++c) {
-                t[c] = label[((long)b * C + c) * V + v];
-                if (t[c] > tmax) { tmax = t[c]; lab = c; }
-            }
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const float x = logits[((long)b * C + c) * V + v];
-                const float sg = 1.f / (1.f + expf(-x));
-                const float* cf = coef + ((long)b * C + c) * 2;
-                const float dz = (cf[0] * t[c] + cf[1]) * sg * (1.f - sg) + (z[c] * inv - (c == lab ? 1.f : 0.f)) * ce_scale;
-                dlogits[((long)b * C + c) * V + v] = up * dz;
+                const float sg = 1.f / (1.f + expf(-x[c]));
+                const float dz = (cf[2 * c] * t[c] + cf[2 * c + 1]) * sg * (1.f - sg) + (z[c] * inv - (c == lab ? 1.f : 0.f)) * ce_scale;
+                dl[(long)c * V + v] = up * dz;
             }
             continue;
         }
-        const int lab = (int)label[(long)b * V + v];
+        const int lab = (int)lb[v];
         float gp[C], dot = 0.f;
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             z[c] *= inv;                                   // p_c
-            const float* cf = coef + ((long)b * C + c) * 2;
-            gp[c] = (c == lab ? cf[0] : 0.f) + cf[1];      // dDice/dp_c
+            gp[c] = (c == lab ? cf[2 * c] : 0.f) + cf[2 * c + 1];      // dDice/dp_c
             dot += z[c] * gp[c];
         }
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             float dz = z[c] * (gp[c] - dot) + (z[c] - (c == lab ? 1.f : 0.f)) * ce_scale;
-            dlogits[((long)b * C + c) * V + v] = up * dz;
+            dl[(long)c * V + v] = up * dz;
         }
     }
 }
 
 }  // namespace
 
-#define DICE_DISPATCH(C_, CALL) \
-    switch (C_) {               \
-        case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break;       \
-        case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; case 8: CALL(8); break;       \
-        case 9: CALL(9); break; case 10: CALL(10); break; case 11: CALL(11); break; case 12: CALL(12); break; \
-        case 13: CALL(13); break; case 14: CALL(14); break; case 15: CALL(15); break; case 16: CALL(16); break; \
-        default: return UNETR_ERR_UNSUPPORTED;                                                                \
-    }
-
 extern "C" int unetr_dicece_fwd(const float* logits, const float* label, int B, int C, long V, int sigmoid_multilabel,
                                 float smooth_nr, float smooth_dr, float* out, float* coef, float* ws, size_t ws_bytes,
                                 void* stream) {
-    if (!logits || !label || !out || !coef || B <= 0 || V <= 0 || B > 65535) return UNETR_ERR_ARG;
-    if (C < 1 || C > MAXC) return UNETR_ERR_UNSUPPORTED;
+    if (!logits || !label || !out || !coef) return UNETR_ERR_ARG;
+    if (int rc = check_voxel_dims(B, C, V)) return rc;
     int nchunk = cdiv(V, LVPB);
     if (!ws || (size_t)B * nchunk * (3 * C + 1) * sizeof(float) > ws_bytes) return UNETR_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-#define CALL_F(CC) hipLaunchKernelGGL((dicece_fwd_kernel<CC, false>), dim3(nchunk, B), dim3(256), 0, st, logits, label, V, ws)
-#define CALL_FS(CC) hipLaunchKernelGGL((dicece_fwd_kernel<CC, true>), dim3(nchunk, B), dim3(256), 0, st, logits, label, V, ws)
-    if (sigmoid_multilabel) { DICE_DISPATCH(C, CALL_FS) } else { DICE_DISPATCH(C, CALL_F) }
+    VOXEL_DISPATCH(C, sigmoid_multilabel,
+                   hipLaunchKernelGGL((dicece_fwd_kernel<CC, SIG>), dim3(nchunk, B), dim3(256), 0, st, logits, label, V, ws));
     hipLaunchKernelGGL(dicece_final_kernel, dim3(1), dim3(256), 0, st, ws, B, C, nchunk, V, smooth_nr, smooth_dr, out, coef);
     return unetr_check_launch();
 }
 
 extern "C" int unetr_dicece_bwd(const float* logits, const float* label, const float* coef, const float* dloss,
                                 float* dlogits, int B, int C, long V, int sigmoid_multilabel, void* stream) {
-    if (!logits || !label || !coef || !dlogits || B <= 0 || V <= 0) return UNETR_ERR_ARG;
-    if (C < 1 || C > MAXC) return UNETR_ERR_UNSUPPORTED;
+    if (!logits || !label || !coef || !dlogits) return UNETR_ERR_ARG;
+    if (int rc = check_voxel_dims(B, C, V, false)) return rc;      // (one grid dimension over B*V: no cap on B)
     hipStream_t st = (hipStream_t)stream;
     long total = (long)B * V;
     int blocks = (int)std::max<long>(1, std::min<long>((total + 255) / 256, 8192));
-#define CALL_B(CC) hipLaunchKernelGGL((dicece_bwd_kernel<CC, false>), dim3(blocks), dim3(256), 0, st, logits, label, coef, dloss, dlogits, B, V)
-#define CALL_BS(CC) hipLaunchKernelGGL((dicece_bwd_kernel<CC, true>), dim3(blocks), dim3(256), 0, st, logits, label, coef, dloss, dlogits, B, V)
-    if (sigmoid_multilabel) { DICE_DISPATCH(C, CALL_BS) } else { DICE_DISPATCH(C, CALL_B) }
+    VOXEL_DISPATCH(C, sigmoid_multilabel, hipLaunchKernelGGL((dicece_bwd_kernel<CC, SIG>), dim3(blocks), dim3(256), 0, st, logits,
+                                                             label, coef, dloss, dlogits, B, V));
     return unetr_check_launch();
 }

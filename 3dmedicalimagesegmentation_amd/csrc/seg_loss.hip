@@ -15,13 +15,13 @@
 //
 // ignore_index (one-hot mode): a voxel whose label equals it adds to no sum and gets a zero gradient; the voxel means then
 // divide by what G counted, so the finalize needs no further partial.
+//
+// Channel dispatch, base pointers, alignment rule, target decode, softmax exponentials and the finalize's block tail: voxel_loss.hpp.
 #include <algorithm>
-#include "common.hpp"
-#include "../../include/unetr_hip.h"
+#include "voxel_loss.hpp"
 
 namespace {
 
-constexpr int MAXC = 16;
 constexpr int FVPB = 4096;  // voxels per forward block (one partial row each)
 constexpr int BVPB = 256;   // voxels per backward block: one per thread
 
@@ -68,32 +68,11 @@ struct SegAcc {
     float I[C], P[C], G[C], x;
 };
 
-// target of one voxel as t[C] (one-hot of the label, or the mask) and the CE class (label, or first argmax of the mask)
-template <int C>
-__device__ __forceinline__ void onehot_target(int lab, float (&t)[C]) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) t[c] = c == lab ? 1.f : 0.f;
-}
-template <int C>
-__device__ __forceinline__ int mask_argmax(const float (&t)[C]) {
-    float tmax = -3.0e38f;
-    int lab = 0;
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-        if (t[c] > tmax) { tmax = t[c]; lab = c; }
-    return lab;
-}
-
 template <int C, bool SIG>
 __device__ __forceinline__ void seg_fwd_voxel(const float (&z)[C], const float (&t)[C], int lab, const SegCfg& cfg, const float (&w)[C],
                                               SegAcc<C>& acc) {
     float e[C], mx = -3.0e38f, se = 0.f;
-    if (!SIG || cfg.voxel == UNETR_SEGLOSS_VOXEL_CE) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) mx = fmaxf(mx, z[c]);
-#pragma unroll
-        for (int c = 0; c < C; ++c) { e[c] = expf(z[c] - mx); se += e[c]; }
-    }
+    if (!SIG || cfg.voxel == UNETR_SEGLOSS_VOXEL_CE) se = softmax_exp<C>(z, e, mx);
     const float inv = 1.f / se;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
@@ -127,15 +106,14 @@ segloss_fwd_kernel(const float* __restrict__ logits, const float* __restrict__ l
     __shared__ float red[4][3 * C + 1];
     const int b = blockIdx.y;
     const long v0 = (long)blockIdx.x * FVPB, v1 = std::min<long>(V, v0 + FVPB);
-    const float* lg = logits + (long)b * C * V;
-    const float* lb = label + (SIG ? (long)b * C * V : (long)b * V);
     SegAcc<C> acc;
     float w[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) { acc.I[c] = 0.f; acc.P[c] = 0.f; acc.G[c] = 0.f; w[c] = cfg.cw ? cfg.cw[c] : 1.f; }
     acc.x = 0.f;
-    const bool vec = (V & 3) == 0 && ((((uintptr_t)logits) | ((uintptr_t)label)) & 15) == 0;
-    if (vec) {
+    const float* lg = item_channels<C>(logits, b, V);
+    const float* lb = item_target<C, SIG>(label, b, V);
+    if (vec4_ok(V, logits, label)) {
         // whole 4-voxel groups (FVPB and V are multiples of 4): one 16-byte load per channel of the logits and of the mask, or one
         // for the labels, all of an iteration's loads in flight together
         for (long v = v0 + 4 * threadIdx.x; v < v1; v += 1024) {
@@ -201,11 +179,6 @@ segloss_fwd_kernel(const float* __restrict__ logits, const float* __restrict__ l
 constexpr int FIN_THREADS = 1024, FIN_WAVES = FIN_THREADS / 64;
 
 constexpr int FIN_LDS_SUMS = 3 * 256;      // per-(b,c) sums stay in LDS up to B*C = 256, else in the workspace
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // Single block.  Phase 1: one wave per (b, c) reduces the partial rows in double (fixed order: lanes stride over the chunks,
 // shuffle tree) into sums[(b*C+c)*3 + {I,P,G}].  Phase 2: one wave per item (a batch item, or the whole batch with batch=1), lane c
@@ -289,9 +262,8 @@ segloss_final_kernel(const float* __restrict__ part, double* sums, unetr_segloss
         const double G = sums[3 * i + 2];
         wd += (d.class_weight ? (double)d.class_weight[i % C] : 1.0) * G; cnt += G;
     }
-    racc = wave_sum_d(racc); wd = wave_sum_d(wd); cnt = wave_sum_d(cnt); xs = wave_sum_d(xs);
-    if (lane == 0) { sh[wave][0] = racc; sh[wave][1] = wd; sh[wave][2] = cnt; sh[wave][3] = xs; }
-    __syncthreads();
+    const double mine[4] = {racc, wd, cnt, xs};
+    block_wave_sums<4>(mine, &sh[0][0]);
     if (threadIdx.x == 0) {
         racc = wd = cnt = xs = 0.0;
         for (int w = 0; w < FIN_WAVES; ++w) { racc += sh[w][0]; wd += sh[w][1]; cnt += sh[w][2]; xs += sh[w][3]; }
@@ -313,12 +285,8 @@ __device__ __forceinline__ void seg_bwd_voxel(float (&z)[C], const float (&t)[C]
                                               const float (&ca)[C], const float (&cb)[C], const float (&ck)[C], float vs, float up) {
     float sm[C], dz[C];
     if (!SIG || cfg.voxel == UNETR_SEGLOSS_VOXEL_CE) {
-        float mx = -3.0e38f, se = 0.f;
-#pragma unroll
-        for (int c = 0; c < C; ++c) mx = fmaxf(mx, z[c]);
-#pragma unroll
-        for (int c = 0; c < C; ++c) { sm[c] = expf(z[c] - mx); se += sm[c]; }
-        const float inv = 1.f / se;
+        float mx;
+        const float inv = 1.f / softmax_exp<C>(z, sm, mx);
 #pragma unroll
         for (int c = 0; c < C; ++c) sm[c] *= inv;
     }
@@ -368,9 +336,9 @@ segloss_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ l
     const int b = blockIdx.y;
     const long v = (long)blockIdx.x * BVPB + threadIdx.x;
     if (v >= V) return;
-    const float* lg = logits + (long)b * C * V;
-    const float* lb = label + (SIG ? (long)b * C * V : (long)b * V);
-    float* dl = dlogits + (long)b * C * V;
+    const float* lg = item_channels<C>(logits, b, V);
+    const float* lb = item_target<C, SIG>(label, b, V);
+    float* dl = item_channels<C>(dlogits, b, V);
     const float up = dloss ? *dloss : 1.f;
     const float vs = coef[(long)B * C * 3];
     float w[C], ca[C], cb[C], ck[C];
@@ -400,8 +368,7 @@ segloss_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ l
 }
 
 int check_desc(const unetr_segloss_desc* d) {
-    if (!d || d->B <= 0 || d->V <= 0 || d->B > 65535) return UNETR_ERR_ARG;
-    if (d->C < 1 || d->C > MAXC) return UNETR_ERR_UNSUPPORTED;
+    if (int rc = check_voxel_desc(d)) return rc;
     if (d->region < UNETR_SEGLOSS_REGION_NONE || d->region > UNETR_SEGLOSS_REGION_GDL || d->voxel < UNETR_SEGLOSS_VOXEL_NONE ||
         d->voxel > UNETR_SEGLOSS_VOXEL_FOCAL || d->w_type < UNETR_SEGLOSS_W_SQUARE || d->w_type > UNETR_SEGLOSS_W_UNIFORM)
         return UNETR_ERR_ARG;
@@ -431,15 +398,6 @@ size_t part_bytes(const unetr_segloss_desc* d) {      // the partial rows, round
 
 }  // namespace
 
-#define SEG_DISPATCH(C_, CALL) \
-    switch (C_) {              \
-        case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break;       \
-        case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; case 8: CALL(8); break;       \
-        case 9: CALL(9); break; case 10: CALL(10); break; case 11: CALL(11); break; case 12: CALL(12); break; \
-        case 13: CALL(13); break; case 14: CALL(14); break; case 15: CALL(15); break; case 16: CALL(16); break; \
-        default: return UNETR_ERR_UNSUPPORTED;                                                                \
-    }
-
 extern "C" size_t unetr_segloss_workspace_bytes(const unetr_segloss_desc* d) {
     if (check_desc(d) != UNETR_OK) return 0;
     return part_bytes(d) + (size_t)d->B * d->C * 3 * sizeof(double);
@@ -456,9 +414,8 @@ extern "C" int unetr_segloss_fwd(const unetr_segloss_desc* d, const float* logit
     float* part = (float*)ws;
     double* sums = (double*)((char*)ws + part_bytes(d));
     hipStream_t st = (hipStream_t)stream;
-#define CALL_F(CC) hipLaunchKernelGGL((segloss_fwd_kernel<CC, false>), dim3(nchunk, B), dim3(256), 0, st, logits, label, V, cfg, part)
-#define CALL_FS(CC) hipLaunchKernelGGL((segloss_fwd_kernel<CC, true>), dim3(nchunk, B), dim3(256), 0, st, logits, label, V, cfg, part)
-    if (d->multilabel) { SEG_DISPATCH(d->C, CALL_FS) } else { SEG_DISPATCH(d->C, CALL_F) }
+    VOXEL_DISPATCH(d->C, d->multilabel,
+                   hipLaunchKernelGGL((segloss_fwd_kernel<CC, SIG>), dim3(nchunk, B), dim3(256), 0, st, logits, label, V, cfg, part));
     hipLaunchKernelGGL(segloss_final_kernel, dim3(1), dim3(FIN_THREADS), 0, st, part, sums, *d, nchunk, out, coef);
     return unetr_check_launch();
 }
@@ -471,8 +428,7 @@ extern "C" int unetr_segloss_bwd(const unetr_segloss_desc* d, const float* logit
     const long V = d->V;
     const SegCfg cfg = make_cfg(d);
     hipStream_t st = (hipStream_t)stream;
-#define CALL_B(CC) hipLaunchKernelGGL((segloss_bwd_kernel<CC, false>), dim3(nblk, B), dim3(256), 0, st, logits, label, coef, dloss, dlogits, B, V, cfg)
-#define CALL_BS(CC) hipLaunchKernelGGL((segloss_bwd_kernel<CC, true>), dim3(nblk, B), dim3(256), 0, st, logits, label, coef, dloss, dlogits, B, V, cfg)
-    if (d->multilabel) { SEG_DISPATCH(d->C, CALL_BS) } else { SEG_DISPATCH(d->C, CALL_B) }
+    VOXEL_DISPATCH(d->C, d->multilabel, hipLaunchKernelGGL((segloss_bwd_kernel<CC, SIG>), dim3(nblk, B), dim3(256), 0, st, logits, label,
+                                                           coef, dloss, dlogits, B, V, cfg));
     return unetr_check_launch();
 }

@@ -30,19 +30,12 @@
 
 namespace {
 
+// (the order key sel_key, the bin and pass counts and the scratch size SEL_WS_BYTES: common.hpp, shared with topk_loss.hip)
 constexpr int SEL_THREADS = 256;                    // = SEL_BINS: the pick runs one bin per thread
-constexpr int SEL_BINS = 256;
-constexpr int SEL_PASSES = 4;
 constexpr int SEL_CHUNK = 4096;                     // elements per chunk: one per workgroup up to SEL_MAX_GRID chunks (n = 4 Mi),
 constexpr int SEL_MAX_GRID = 1024;                  // above that the workgroups stride over the chunks
 constexpr int SEL_COPIES = 8;
-constexpr int SEL_HIST_WORDS = SEL_PASSES * SEL_BINS;
-constexpr int SEL_STATE_WORDS = 16;                 // state[p] = (prefix, rank) for p = 0..3, padded
-constexpr size_t SEL_WS_BYTES = (size_t)(SEL_HIST_WORDS + SEL_STATE_WORDS) * sizeof(uint32_t);
 
-__device__ __forceinline__ uint32_t sel_key(uint32_t bits, uint32_t flip) {
-    return (bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u)) ^ flip;
-}
 __device__ __forceinline__ uint32_t sel_unkey(uint32_t key, uint32_t flip) {
     key ^= flip;
     return (key >> 31) ? key ^ 0x80000000u : ~key;

@@ -13,18 +13,17 @@
 // so a largest-K select with K <= N never reaches a sentinel, and the sum pass never takes one.  Backward, one launch, one voxel per
 // thread: it compares the bits forward stored in `values` with t -- never a recomputed value -- and reads the logits only where the
 // voxel's weight is not zero.  No float atomics: reproducible run to run.  Every access is bounded by V (or B*V).
+// Channel dispatch, base pointers, alignment rule, target decode, softmax exponentials and block tails: voxel_loss.hpp; the order key
+// and the size of the select's scratch: common.hpp.
 #include <algorithm>
-#include "common.hpp"
-#include "../../include/unetr_hip.h"
+#include "voxel_loss.hpp"
 
 namespace {
 
-constexpr int MAXC = 16;
 constexpr int TK_VPB = 1024;     // voxels per block of the value pass: four per thread
 constexpr int TK_SPB = 4096;     // values per block of the sum pass (one partial each)
 constexpr int TK_BVPB = 256;     // voxels per backward block: one per thread
 constexpr float TK_SENTINEL = -1.f;
-constexpr size_t TK_SELECT_WS = (4 * 256 + 16) * sizeof(uint32_t);      // = unetr_select_workspace_bytes
 constexpr int TK_META_WORDS = 8; // rank, N, K, pad, then the unetr_select_result (3 words), pad
 
 struct TkCfg {
@@ -32,28 +31,13 @@ struct TkCfg {
     int has_ignore, ignore;
 };
 
-__device__ __forceinline__ uint32_t tk_key(float f) {
-    const uint32_t b = __builtin_bit_cast(uint32_t, f);
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-
-template <int C>
-__device__ __forceinline__ int tk_mask_argmax(const float (&t)[C]) {
-    float tmax = -3.0e38f;
-    int lab = 0;
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-        if (t[c] > tmax) { tmax = t[c]; lab = c; }
-    return lab;
-}
+// a value's place in the order the select ran in (sel_key without the flip: larger value, larger key)
+__device__ __forceinline__ uint32_t tk_key(float f) { return sel_key(__builtin_bit_cast(uint32_t, f), 0u); }
 
 template <int C>
 __device__ __forceinline__ float tk_voxel_value(const float (&z)[C], int lab, const TkCfg& cfg, const float (&w)[C]) {
-    float mx = -3.0e38f, se = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, z[c]);
-#pragma unroll
-    for (int c = 0; c < C; ++c) se += expf(z[c] - mx);
+    float e[C], mx;
+    const float se = softmax_exp<C>(z, e, mx);
     float zl = 0.f, wl = 1.f;
 #pragma unroll
     for (int c = 0; c < C; ++c)
@@ -66,12 +50,6 @@ __device__ __forceinline__ float tk_voxel_value(const float (&z)[C], int lab, co
     return wl * (logf(se) - (zl - mx));
 }
 
-__device__ __forceinline__ uint32_t wave_sum_u(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 template <int C, bool SIG>
 __global__ void __launch_bounds__(256)
 topk_val_kernel(const float* __restrict__ logits, const float* __restrict__ label, long V, TkCfg cfg, float* __restrict__ values,
@@ -79,15 +57,14 @@ topk_val_kernel(const float* __restrict__ logits, const float* __restrict__ labe
     __shared__ uint32_t red[4];
     const int b = blockIdx.y;
     const long v0 = (long)blockIdx.x * TK_VPB, v1 = std::min<long>(V, v0 + TK_VPB);
-    const float* lg = logits + (long)b * C * V;
-    const float* lb = label + (SIG ? (long)b * C * V : (long)b * V);
+    const float* lg = item_channels<C>(logits, b, V);
+    const float* lb = item_target<C, SIG>(label, b, V);
     float* val = values + (long)b * V;
     float w[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) w[c] = cfg.cw ? cfg.cw[c] : 1.f;
     uint32_t cnt = 0u;
-    const bool vec = (V & 3) == 0 && ((((uintptr_t)logits) | ((uintptr_t)label) | ((uintptr_t)values)) & 15) == 0;
-    if (vec) {
+    if (vec4_ok(V, logits, label, values)) {
         // TK_VPB and V are multiples of 4: a group that starts below v1 ends below it
         const long v = v0 + 4 * threadIdx.x;
         if (v < v1) {
@@ -111,7 +88,7 @@ topk_val_kernel(const float* __restrict__ logits, const float* __restrict__ labe
                     float t[C];
 #pragma unroll
                     for (int c = 0; c < C; ++c) t[c] = tv[c][e];
-                    lab = tk_mask_argmax<C>(t);
+                    lab = mask_argmax<C>(t);
                 } else {
                     lab = (int)tv[0][e];
                     valid = !(cfg.has_ignore && lab == cfg.ignore);
@@ -130,7 +107,7 @@ topk_val_kernel(const float* __restrict__ logits, const float* __restrict__ labe
                 float t[C];
 #pragma unroll
                 for (int c = 0; c < C; ++c) t[c] = lb[(long)c * V + v];
-                lab = tk_mask_argmax<C>(t);
+                lab = mask_argmax<C>(t);
             } else {
                 lab = (int)lb[v];
                 valid = !(cfg.has_ignore && lab == cfg.ignore);
@@ -141,9 +118,7 @@ topk_val_kernel(const float* __restrict__ logits, const float* __restrict__ labe
             cnt += valid ? 1u : 0u;
         }
     }
-    cnt = wave_sum_u(cnt);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
-    __syncthreads();
+    block_wave_sums<1>(&cnt, red);
     if (threadIdx.x == 0) part_cnt[(long)b * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
@@ -153,9 +128,7 @@ topk_rank_kernel(const uint32_t* __restrict__ part_cnt, int nblk, const float* _
     __shared__ uint32_t red[4];
     uint32_t cnt = 0u;
     for (int i = threadIdx.x; i < nblk; i += 256) cnt += part_cnt[i];
-    cnt = wave_sum_u(cnt);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
-    __syncthreads();
+    block_wave_sums<1>(&cnt, red);
     if (threadIdx.x == 0) {
         const long N = (long)red[0] + red[1] + red[2] + red[3];
         long K = (long)floor((double)N * (double)*k / 100.0);
@@ -170,8 +143,7 @@ topk_sum_kernel(const float* __restrict__ values, long n, const unetr_select_res
     const uint32_t kt = tk_key(sel->value);
     const long i0 = (long)blockIdx.x * TK_SPB, i1 = std::min<long>(n, i0 + TK_SPB);
     float s = 0.f;
-    const bool vec = (n & 3) == 0 && (((uintptr_t)values) & 15) == 0;
-    if (vec) {
+    if (vec4_ok(n, values)) {
         for (long i = i0 + 4 * threadIdx.x; i < i1; i += 1024) {
             const f32x4 u = *(const f32x4*)(values + i);
 #pragma unroll
@@ -183,9 +155,7 @@ topk_sum_kernel(const float* __restrict__ values, long n, const unetr_select_res
             s += tk_key(u) > kt ? u : 0.f;
         }
     }
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
+    block_wave_sums<1>(&s, red);
     if (threadIdx.x == 0) part_sum[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
@@ -196,9 +166,7 @@ topk_final_kernel(const float* __restrict__ part_sum, int nsum, const int* __res
     __shared__ double red[4];
     double s = 0.0;
     for (int i = threadIdx.x; i < nsum; i += 256) s += (double)part_sum[i];
-    s = wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
+    block_wave_sums<1>(&s, red);
     if (threadIdx.x == 0) {
         s = red[0] + red[1] + red[2] + red[3];
         const double K = (double)meta[2], t = (double)sel->value;
@@ -215,7 +183,7 @@ topk_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ labe
     const int b = blockIdx.y;
     const long v = (long)blockIdx.x * TK_BVPB + threadIdx.x;
     if (v >= V) return;
-    float* dl = dlogits + (long)b * C * V;
+    float* dl = item_channels<C>(dlogits, b, V);
     const uint32_t ku = tk_key(values[(long)b * V + v]), kt = tk_key(coef[2]);
     float g = ku > kt ? coef[0] : ku == kt ? coef[1] : 0.f;
     if (g == 0.f) {                                  // below the threshold, or ignored (the sentinel is below every real value)
@@ -223,22 +191,21 @@ topk_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ labe
         for (int c = 0; c < C; ++c) dl[(long)c * V + v] = 0.f;
         return;
     }
-    const float* lg = logits + (long)b * C * V;
-    const float* lb = label + (SIG ? (long)b * C * V : (long)b * V);
+    const float* lg = item_channels<C>(logits, b, V);
+    const float* lb = item_target<C, SIG>(label, b, V);
     int lab;
     if constexpr (SIG) {
         float t[C];
 #pragma unroll
         for (int c = 0; c < C; ++c) t[c] = lb[(long)c * V + v];
-        lab = tk_mask_argmax<C>(t);
+        lab = mask_argmax<C>(t);
     } else {
         lab = (int)lb[v];
     }
-    float z[C], mx = -3.0e38f, se = 0.f;
+    float z[C], e[C], mx;
 #pragma unroll
-    for (int c = 0; c < C; ++c) { z[c] = lg[(long)c * V + v]; mx = fmaxf(mx, z[c]); }
-#pragma unroll
-    for (int c = 0; c < C; ++c) { z[c] = expf(z[c] - mx); se += z[c]; }
+    for (int c = 0; c < C; ++c) z[c] = lg[(long)c * V + v];
+    const float se = softmax_exp<C>(z, e, mx);
     float wl = 1.f;
     if (cfg.cw) {
 #pragma unroll
@@ -248,12 +215,11 @@ topk_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ labe
     g *= (dloss ? *dloss : 1.f) * wl;
     const float inv = 1.f / se;
 #pragma unroll
-    for (int c = 0; c < C; ++c) dl[(long)c * V + v] = g * (z[c] * inv - (c == lab ? 1.f : 0.f));
+    for (int c = 0; c < C; ++c) dl[(long)c * V + v] = g * (e[c] * inv - (c == lab ? 1.f : 0.f));
 }
 
 int check_desc(const unetr_topkce_desc* d) {
-    if (!d || d->B <= 0 || d->V <= 0 || d->B > 65535) return UNETR_ERR_ARG;
-    if (d->C < 1 || d->C > MAXC) return UNETR_ERR_UNSUPPORTED;
+    if (int rc = check_voxel_desc(d)) return rc;
     if ((long)d->B * d->V >= (1L << 31)) return UNETR_ERR_UNSUPPORTED;
     if (d->multilabel && (d->has_ignore || d->class_weight)) return UNETR_ERR_UNSUPPORTED;
     return UNETR_OK;
@@ -269,18 +235,9 @@ TkCfg make_cfg(const unetr_topkce_desc* d) {
 
 }  // namespace
 
-#define TK_DISPATCH(C_, CALL) \
-    switch (C_) {             \
-        case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break;       \
-        case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; case 8: CALL(8); break;       \
-        case 9: CALL(9); break; case 10: CALL(10); break; case 11: CALL(11); break; case 12: CALL(12); break; \
-        case 13: CALL(13); break; case 14: CALL(14); break; case 15: CALL(15); break; case 16: CALL(16); break; \
-        default: return UNETR_ERR_UNSUPPORTED;                                                                \
-    }
-
 extern "C" size_t unetr_topkce_workspace_bytes(const unetr_topkce_desc* d) {
     if (check_desc(d) != UNETR_OK) return 0;
-    const size_t n = TK_SELECT_WS + TK_META_WORDS * 4 + 4 * (size_t)d->B * cdiv(d->V, TK_VPB) + 4 * (size_t)cdiv((long)d->B * d->V, TK_SPB);
+    const size_t n = SEL_WS_BYTES + TK_META_WORDS * 4 + 4 * (size_t)d->B * cdiv(d->V, TK_VPB) + 4 * (size_t)cdiv((long)d->B * d->V, TK_SPB);
     return (n + 15) & ~(size_t)15;
 }
 
@@ -293,16 +250,15 @@ extern "C" int unetr_topkce_fwd(const unetr_topkce_desc* d, const float* logits,
     const long V = d->V, n = (long)B * V;
     const int nsum = cdiv(n, TK_SPB);
     const TkCfg cfg = make_cfg(d);
-    int* meta = (int*)((char*)ws + TK_SELECT_WS);
+    int* meta = (int*)((char*)ws + SEL_WS_BYTES);
     unetr_select_result* sel = (unetr_select_result*)(meta + 4);
     uint32_t* part_cnt = (uint32_t*)(meta + TK_META_WORDS);
     float* part_sum = (float*)(part_cnt + nblk);
     hipStream_t st = (hipStream_t)stream;
-#define CALL_V(CC) hipLaunchKernelGGL((topk_val_kernel<CC, false>), dim3(nchunk, B), dim3(256), 0, st, logits, label, V, cfg, values, part_cnt)
-#define CALL_VS(CC) hipLaunchKernelGGL((topk_val_kernel<CC, true>), dim3(nchunk, B), dim3(256), 0, st, logits, label, V, cfg, values, part_cnt)
-    if (d->multilabel) { TK_DISPATCH(d->C, CALL_VS) } else { TK_DISPATCH(d->C, CALL_V) }
+    VOXEL_DISPATCH(d->C, d->multilabel, hipLaunchKernelGGL((topk_val_kernel<CC, SIG>), dim3(nchunk, B), dim3(256), 0, st, logits, label, V, cfg,
+                                                           values, part_cnt));
     hipLaunchKernelGGL(topk_rank_kernel, dim3(1), dim3(256), 0, st, part_cnt, nblk, k, meta);
-    if (int rc = unetr_select_kth(values, n, meta, 0, UNETR_SELECT_LARGEST, sel, ws, TK_SELECT_WS, stream)) return rc;
+    if (int rc = unetr_select_kth(values, n, meta, 0, UNETR_SELECT_LARGEST, sel, ws, SEL_WS_BYTES, stream)) return rc;
     hipLaunchKernelGGL(topk_sum_kernel, dim3(nsum), dim3(256), 0, st, values, n, sel, part_sum);
     hipLaunchKernelGGL(topk_final_kernel, dim3(1), dim3(256), 0, st, part_sum, nsum, meta, sel, out, coef);
     return unetr_check_launch();
@@ -316,8 +272,7 @@ extern "C" int unetr_topkce_bwd(const unetr_topkce_desc* d, const float* logits,
     const long V = d->V;
     const TkCfg cfg = make_cfg(d);
     hipStream_t st = (hipStream_t)stream;
-#define CALL_B(CC) hipLaunchKernelGGL((topk_bwd_kernel<CC, false>), dim3(nblk, B), dim3(256), 0, st, logits, label, values, coef, dloss, dlogits, V, cfg)
-#define CALL_BS(CC) hipLaunchKernelGGL((topk_bwd_kernel<CC, true>), dim3(nblk, B), dim3(256), 0, st, logits, label, values, coef, dloss, dlogits, V, cfg)
-    if (d->multilabel) { TK_DISPATCH(d->C, CALL_BS) } else { TK_DISPATCH(d->C, CALL_B) }
+    VOXEL_DISPATCH(d->C, d->multilabel, hipLaunchKernelGGL((topk_bwd_kernel<CC, SIG>), dim3(nblk, B), dim3(256), 0, st, logits, label, values,
+                                                           coef, dloss, dlogits, V, cfg));
     return unetr_check_launch();
 }

@@ -9,6 +9,7 @@ import torch
 import torch.nn as nn
 
 from . import functional as Fn
+from . import loss_common as lc
 from ._capi import DistLossDesc, EdtDesc, call, call_rc
 
 _FORM = {"mask": 0, "mask_u8": 1, "class_ids": 2, "softmax": 3, "sigmoid": 4}
@@ -103,15 +104,9 @@ class DistLossFn(torch.autograd.Function):
         Fn._require_gpu(logits)
         if logits.dim() != 5:
             raise ValueError(f"logits must be [B,C,*S] with three spatial dimensions, got {tuple(logits.shape)}")
-        logits = logits.contiguous()
-        target = target.contiguous().to(torch.float32)
-        B, C, S = logits.shape[0], logits.shape[1], tuple(logits.shape[2:])
-        V = S[0] * S[1] * S[2]
         ml = cfg["multilabel"]
-        if ml and target.numel() != B * C * V:
-            raise ValueError(f"multi-label target must be [B,C,*spatial] like the logits, got {tuple(target.shape)}")
-        if not ml and target.numel() != B * V:
-            raise ValueError(f"label must be [B,1,*spatial] class indices, got {tuple(target.shape)}")
+        logits, target, B, C, V = Fn._loss_inputs(logits, target, ml)
+        S = tuple(logits.shape[2:])
         tform = "mask" if ml else "class_ids"
         if cfg["kind"] == _KIND["boundary"]:
             field = _edt(target, tform, B, C, S, "signed", spacing)
@@ -147,41 +142,23 @@ class _DistanceLoss(nn.Module):
 
     def __init__(self, alpha, include_background, to_onehot_y, softmax, sigmoid, spacing, weight, reduction):
         super().__init__()
-        if reduction != "mean":
-            raise NotImplementedError(f"reduction={reduction!r}: the HIP loss family implements reduction='mean'")
-        if softmax and sigmoid:
-            raise ValueError("softmax=True and sigmoid=True exclude each other")
-        if (bool(to_onehot_y), bool(softmax), bool(sigmoid)) not in ((True, True, False), (False, False, True)):
-            raise NotImplementedError("the HIP loss family implements to_onehot_y=True with softmax=True and to_onehot_y=False with "
-                                      f"sigmoid=True; got to_onehot_y={to_onehot_y}, softmax={softmax}, sigmoid={sigmoid}")
+        lc.require_mean(reduction)
+        multilabel = lc.activation_form(to_onehot_y, softmax, sigmoid)
         if not float(alpha) > 0.0:
             raise ValueError(f"alpha={alpha!r}: expected a positive exponent")
         self.alpha = float(alpha)
         self.spacing = _spacing(spacing)
-        self.cfg = dict(multilabel=int(not to_onehot_y), kind=_KIND[self._kind], include_background=int(bool(include_background)))
-        self.register_buffer("weight", torch.full((1,), float(weight), dtype=torch.float32,
-                                                  device="cuda" if torch.cuda.is_available() else "cpu"), persistent=False)
+        self.cfg = dict(multilabel=int(multilabel), kind=_KIND[self._kind], include_background=int(bool(include_background)))
+        self.register_buffer("weight", lc.device_scalar(weight), persistent=False)
 
     def set_weight(self, w: float) -> None:
         """write the device scalar (a fill launch on the current stream, no synchronisation)"""
         self.weight.fill_(float(w))
 
-    def _check(self, input, target):
-        if self.cfg["multilabel"]:
-            if target.shape != input.shape:
-                raise ValueError("to_onehot_y=False needs a target shaped like the logits [B,C,*spatial]")
-        elif target.shape[1] != 1:
-            raise ValueError("target must be [B,1,*spatial] class indices (to_onehot_y=True)")
-        if not self.cfg["include_background"] and input.shape[1] == 1:
-            raise ValueError("include_background=False needs more than one channel")
-
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-        self._check(input, target)
-        if self.weight.device != input.device and input.is_cuda:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("the loss weight is not on the logits' device yet: run the loss once before capturing it")
-            self.weight = self.weight.to(input.device)
-        return DistLossFn.apply(input, target, self.weight, self.cfg, self.spacing, self.alpha)
+        lc.check_call(input, target, self.cfg)
+        weight = lc.scalar_on(self, "weight", input, "the loss weight")
+        return DistLossFn.apply(input, target, weight, self.cfg, self.spacing, self.alpha)
 
 
 class BoundaryLoss(_DistanceLoss):

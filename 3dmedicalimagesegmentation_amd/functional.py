@@ -1552,6 +1552,21 @@ def to_channels_last(x_in):
     return y
 
 
+def _loss_inputs(logits, label, multilabel):
+    """forward prologue of the per-voxel loss Functions -> (logits, label, B, C, V): contiguous fp32 device logits [B,C,*spatial] and
+    the label as contiguous fp32, class ids [B,1,*spatial] or, multilabel, a mask shaped like the logits"""
+    _require_gpu(logits)
+    logits = logits.contiguous()
+    label = label.contiguous().to(torch.float32)
+    B, C = logits.shape[0], logits.shape[1]
+    V = logits.numel() // (B * C)
+    if multilabel and label.numel() != B * C * V:
+        raise ValueError(f"multi-label target must be [B,C,*spatial] like the logits, got {tuple(label.shape)}")
+    if not multilabel and label.numel() != B * V:
+        raise ValueError(f"label must be [B,1,*spatial] class indices, got {tuple(label.shape)}")
+    return logits, label, B, C, V
+
+
 class DiceCEFn(torch.autograd.Function):
     """DiceCELoss -> (loss, dice, ce) as a 3-vector.  multilabel=False: DiceCELoss(to_onehot_y=True, softmax=True)
     (unetr_segmentation_3d.py:404); multilabel=True: DiceCELoss(to_onehot_y=False, sigmoid=True) (:477-482)."""
@@ -1560,15 +1575,7 @@ class DiceCEFn(torch.autograd.Function):
     def forward(ctx, logits, label, smooth_nr, smooth_dr, multilabel=False, scalar=False):
         """scalar=True: returns the 0-dim loss itself (what DiceCELoss.forward hands to backward()): selecting element 0 of the
         3-vector through autograd cost a fill, a zero and a copy launch in every backward pass"""
-        _require_gpu(logits)
-        logits = logits.contiguous()
-        label = label.contiguous().to(torch.float32)
-        B, C = logits.shape[0], logits.shape[1]
-        V = logits.numel() // (B * C)
-        if multilabel and label.numel() != B * C * V:
-            raise ValueError(f"multi-label target must be [B,C,*spatial] like the logits, got {tuple(label.shape)}")
-        if not multilabel and label.numel() != B * V:
-            raise ValueError(f"label must be [B,1,*spatial] class indices, got {tuple(label.shape)}")
+        logits, label, B, C, V = _loss_inputs(logits, label, multilabel)
         out = torch.empty(3, dtype=torch.float32, device=logits.device)
         coef = torch.empty(B * C * 2, dtype=torch.float32, device=logits.device)
         ws = workspace(logits.device)
@@ -1605,15 +1612,7 @@ class SegLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, label, cfg, class_weight=None, scalar=False):
         """scalar=True: returns the 0-dim loss itself, as DiceCEFn does"""
-        _require_gpu(logits)
-        logits = logits.contiguous()
-        label = label.contiguous().to(torch.float32)
-        B, C = logits.shape[0], logits.shape[1]
-        V = logits.numel() // (B * C)
-        if cfg["multilabel"] and label.numel() != B * C * V:
-            raise ValueError(f"multi-label target must be [B,C,*spatial] like the logits, got {tuple(label.shape)}")
-        if not cfg["multilabel"] and label.numel() != B * V:
-            raise ValueError(f"label must be [B,1,*spatial] class indices, got {tuple(label.shape)}")
+        logits, label, B, C, V = _loss_inputs(logits, label, cfg["multilabel"])
         if not cfg["include_background"] and C == 1:
             raise ValueError("include_background=False needs more than one channel")
         if class_weight is not None and class_weight.numel() != C:

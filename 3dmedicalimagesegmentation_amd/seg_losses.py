@@ -7,6 +7,7 @@ import torch
 import torch.nn as nn
 
 from . import functional as Fn
+from . import loss_common as lc
 
 _REGION = {"none": 0, "dice": 1, "jaccard": 2, "tversky": 3, "generalized_dice": 4}
 _VOXEL = {"none": 0, "ce": 1, "focal": 2}
@@ -35,15 +36,8 @@ class SegLoss(nn.Module):
             raise ValueError(f"w_type={w_type!r}: expected one of {sorted(_W_TYPE)}")
         if region == "none" and voxel == "none":
             raise ValueError("region='none' and voxel='none': the loss has no term")
-        if reduction != "mean":
-            raise NotImplementedError(f"reduction={reduction!r}: the HIP loss family implements reduction='mean'")
-        if softmax and sigmoid:
-            raise ValueError("softmax=True and sigmoid=True exclude each other")
-        multilabel = not to_onehot_y
-        if region != "none" or voxel == "ce":
-            if (bool(to_onehot_y), bool(softmax), bool(sigmoid)) not in ((True, True, False), (False, False, True)):
-                raise NotImplementedError("the HIP loss family implements to_onehot_y=True with softmax=True and to_onehot_y=False with "
-                                          f"sigmoid=True; got to_onehot_y={to_onehot_y}, softmax={softmax}, sigmoid={sigmoid}")
+        lc.require_mean(reduction)
+        multilabel = lc.activation_form(to_onehot_y, softmax, sigmoid, required=region != "none" or voxel == "ce")
         if squared_pred and region in ("tversky", "generalized_dice"):
             raise NotImplementedError(f"squared_pred=True is not defined for region={region!r}")
         if ignore_index is not None and multilabel:
@@ -53,9 +47,7 @@ class SegLoss(nn.Module):
                 raise ValueError("class_weight weighs the voxel term, and voxel='none'")
             if voxel == "ce" and multilabel:
                 raise NotImplementedError("class_weight with voxel='ce' needs class-id targets (to_onehot_y=True)")
-            class_weight = [float(w) for w in (class_weight.tolist() if isinstance(class_weight, torch.Tensor) else class_weight)]
-            if not class_weight or min(class_weight) < 0:
-                raise ValueError("class_weight must hold one non-negative entry per channel")
+            class_weight = lc.class_weight_list(class_weight)
         self.region, self.voxel = region, voxel
         self.class_weight = class_weight
         self.cfg = dict(multilabel=int(multilabel), region=_REGION[region], voxel=_VOXEL[voxel],
@@ -68,23 +60,10 @@ class SegLoss(nn.Module):
         self._cw = {}      # device -> class_weight as a device buffer, created at first use
 
     def _check(self, input, target):
-        if self.cfg["multilabel"]:
-            if target.shape != input.shape:
-                raise ValueError("to_onehot_y=False needs a target shaped like the logits [B,C,*spatial]")
-        elif target.shape[1] != 1:
-            raise ValueError("target must be [B,1,*spatial] class indices (to_onehot_y=True)")
-        if not self.cfg["include_background"] and input.shape[1] == 1:
-            raise ValueError("include_background=False needs more than one channel")
-        if self.class_weight is not None and len(self.class_weight) != input.shape[1]:
-            raise ValueError(f"class_weight has {len(self.class_weight)} entries for {input.shape[1]} channels")
+        lc.check_call(input, target, self.cfg, self.class_weight)
 
     def _weights(self, device):
-        if self.class_weight is None or device.type != "cuda":
-            return None
-        w = self._cw.get(device)
-        if w is None:
-            w = self._cw[device] = torch.tensor(self.class_weight, dtype=torch.float32, device=device)
-        return w
+        return lc.weights_on(self._cw, self.class_weight, device)
 
     def terms(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         """3-vector (loss, region term, voxel term), the terms before their lambdas; only element 0 carries gradient."""

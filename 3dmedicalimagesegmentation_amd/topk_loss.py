@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import functional as Fn
+from . import loss_common as lc
 from ._capi import SELECT_LARGEST, TopKCEDesc, call
 from .seg_losses import SegLoss, _activation
 
@@ -109,15 +110,7 @@ class TopKCEFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, label, k, cfg, class_weight=None):
-        Fn._require_gpu(logits)
-        logits = logits.contiguous()
-        label = label.contiguous().to(torch.float32)
-        B, C = logits.shape[0], logits.shape[1]
-        V = logits.numel() // (B * C)
-        if cfg["multilabel"] and label.numel() != B * C * V:
-            raise ValueError(f"multi-label target must be [B,C,*spatial] like the logits, got {tuple(label.shape)}")
-        if not cfg["multilabel"] and label.numel() != B * V:
-            raise ValueError(f"label must be [B,1,*spatial] class indices, got {tuple(label.shape)}")
+        logits, label, B, C, V = Fn._loss_inputs(logits, label, cfg["multilabel"])
         if class_weight is not None and class_weight.numel() != C:
             raise ValueError(f"class_weight has {class_weight.numel()} entries for {C} channels")
         d = TopKCEDesc(B=B, C=C, V=V, **cfg)
@@ -163,57 +156,28 @@ class TopKLoss(nn.Module):
                  ignore_index=None, reduction: str = "mean") -> None:
         super().__init__()
         k = _check_k(k)
-        if reduction != "mean":
-            raise NotImplementedError(f"reduction={reduction!r}: the HIP loss family implements reduction='mean'")
-        if softmax and sigmoid:
-            raise ValueError("softmax=True and sigmoid=True exclude each other")
-        if (bool(to_onehot_y), bool(softmax), bool(sigmoid)) not in ((True, True, False), (False, False, True)):
-            raise NotImplementedError("the HIP loss family implements to_onehot_y=True with softmax=True and to_onehot_y=False with "
-                                      f"sigmoid=True; got to_onehot_y={to_onehot_y}, softmax={softmax}, sigmoid={sigmoid}")
-        multilabel = not to_onehot_y
+        lc.require_mean(reduction)
+        multilabel = lc.activation_form(to_onehot_y, softmax, sigmoid)
         if ignore_index is not None and multilabel:
             raise NotImplementedError("ignore_index needs class-id targets (to_onehot_y=True)")
         if class_weight is not None:
             if multilabel:
                 raise NotImplementedError("class_weight needs class-id targets (to_onehot_y=True)")
-            class_weight = [float(w) for w in (class_weight.tolist() if isinstance(class_weight, torch.Tensor) else class_weight)]
-            if not class_weight or min(class_weight) < 0:
-                raise ValueError("class_weight must hold one non-negative entry per channel")
+            class_weight = lc.class_weight_list(class_weight)
         self.class_weight = class_weight
         self.cfg = dict(multilabel=int(multilabel), has_ignore=int(ignore_index is not None),
                         ignore_index=int(ignore_index) if ignore_index is not None else 0)
         self._cw = {}      # device -> class_weight as a device buffer, created at first use
-        self.register_buffer("k", torch.full((1,), k, dtype=torch.float32, device="cuda" if torch.cuda.is_available() else "cpu"),
-                             persistent=False)
+        self.register_buffer("k", lc.device_scalar(k), persistent=False)
 
     def set_k(self, k: float) -> None:
         """write the device scalar (a fill launch on the current stream, no synchronisation)"""
         self.k.fill_(_check_k(k))
 
-    def _check(self, input, target):
-        if self.cfg["multilabel"]:
-            if target.shape != input.shape:
-                raise ValueError("to_onehot_y=False needs a target shaped like the logits [B,C,*spatial]")
-        elif target.shape[1] != 1:
-            raise ValueError("target must be [B,1,*spatial] class indices (to_onehot_y=True)")
-        if self.class_weight is not None and len(self.class_weight) != input.shape[1]:
-            raise ValueError(f"class_weight has {len(self.class_weight)} entries for {input.shape[1]} channels")
-
-    def _weights(self, device):
-        if self.class_weight is None or device.type != "cuda":
-            return None
-        w = self._cw.get(device)
-        if w is None:
-            w = self._cw[device] = torch.tensor(self.class_weight, dtype=torch.float32, device=device)
-        return w
-
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-        self._check(input, target)
-        if self.k.device != input.device and input.is_cuda:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("k is not on the logits' device yet: run the loss once before capturing it")
-            self.k = self.k.to(input.device)
-        return TopKCEFn.apply(input, target, self.k, self.cfg, self._weights(input.device))
+        lc.check_call(input, target, self.cfg, self.class_weight)
+        k = lc.scalar_on(self, "k", input, "k")
+        return TopKCEFn.apply(input, target, k, self.cfg, lc.weights_on(self._cw, self.class_weight, input.device))
 
 
 class DiceTopKLoss(nn.Module):
