@@ -6,14 +6,12 @@
 //   aug_prep_kernel      ScaleIntensityRanged (same float32 operations as MONAI, no contraction) in place, the bounding box
 //                        of any_c(image > 0) by integer atomics, a flag for label values that are not integers in 0..255
 //   aug_crop_kernel      copies the foreground box: image float32, label uint8
-//   aug_count_kernel     per chunk of AUG_CHUNK voxels the number of foreground / background voxels of map_binary_to_indices
-//   aug_scan_kernel      exclusive scan of the chunk counts (one workgroup) and the two totals
-//   aug_scatter_kernel   ordered compaction: each chunk again, AUG_CHUNK / 256 rounds of ballot + prefix, ascending ravel order
-// VolumeCache.build_class_indices (setup, may synchronise): map_classes_to_indices, the same trio for K <= 32 lists at once
-//   aug_class_count_kernel     per chunk the number of voxels of every class, from one read of the label: one ballot per class
-//   aug_class_scan_kernel      one workgroup per class: exclusive scan of its chunk counts and the list's length;
-//   aug_class_offsets_kernel   then where each list starts in the concatenated array (int64)
-//   aug_class_scatter_kernel   stable counting sort: chunk offset of the class + rank among the class's earlier voxels of the chunk
+//   aug_count_kernel<2>    per chunk of AUG_CHUNK voxels the number of foreground / background voxels of map_binary_to_indices
+//   aug_scan_kernel        one workgroup per list: exclusive scan of its chunk counts and the list's length
+//   aug_scatter_kernel<2>  ordered compaction: each chunk again, AUG_CHUNK / 256 rounds of ballot + prefix, ascending ravel order
+// VolumeCache.build_class_indices (setup, may synchronise): map_classes_to_indices, the same three kernels (<0>) for K <= 32 lists
+// at once: one ballot per class from one read of the label, a stable counting sort; between scan and scatter
+//   aug_class_offsets_kernel   where each list starts in the concatenated array (int64)
 // RandCropAugment.__call__ (per step: launches only, no host sync, no allocation):
 //   aug_sample_kernel    one workgroup: Philox4x64-10 draws, crop centres, the params table, counter and cursor advance;
 //                        <true, .> also draws the rotation / zoom of each sample and writes the affine table; <., true> takes
@@ -152,93 +150,23 @@ aug_crop_kernel(const float* __restrict__ img, const float* __restrict__ lbl, in
     else olbl[(ch - C) * v + dst] = (uint8_t)lbl[(ch - C) * V + src];
 }
 
-// ---------------------------------------------------------------- add(): map_binary_to_indices as an ordered compaction
-__device__ __forceinline__ void fg_bg(const float* __restrict__ img, const uint8_t* __restrict__ lbl, int C, int L, long V,
-                                      float thr, long v, bool& fg, bool& bg) {
-    fg = false;
+// ---------------------------------------------------------------- add() / build_class_indices(): one ordered compaction
+// map_binary_to_indices (the foreground and the background list) and map_classes_to_indices (K <= AUG_MAXK class lists) are the same
+// stable counting sort with another membership rule: bit c of a voxel's word says that it is in list c.
+// fg / bg: bit 0 = any label channel nonzero, bit 1 = not that and any image channel > thr.
+__device__ __forceinline__ unsigned fg_bg(const float* __restrict__ img, const uint8_t* __restrict__ lbl, int C, int L, long V,
+                                          float thr, long v) {
+    bool fg = false;
+#pragma clang loop vectorize(disable)                        // (the stride is V: a vector body would only serve V == 1)
     for (int l = 0; l < L; ++l) fg |= lbl[(long)l * V + v] != 0;
     bool any = false;
+#pragma clang loop vectorize(disable)
     for (int c = 0; c < C; ++c) any |= img[(long)c * V + v] > thr;
-    bg = !fg && any;
+    return (unsigned)fg | (unsigned)(!fg && any) << 1;
 }
 
-// ws (ints): [cnt_fg nblk][cnt_bg nblk][off_fg nblk][off_bg nblk][total_fg, total_bg]
-__global__ void __launch_bounds__(256)
-aug_count_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lbl, int C, int L, long V, float thr,
-                 int* __restrict__ ws, int nblk) {
-    __shared__ int red[2][4];
-    int nf = 0, nb = 0;
-    const long base = (long)blockIdx.x * AUG_CHUNK;
-    for (int i = 0; i < AUG_CHUNK / 256; ++i) {
-        const long v = base + i * 256 + threadIdx.x;
-        if (v >= V) break;
-        bool f, b;
-        fg_bg(img, lbl, C, L, V, thr, v, f, b);
-        nf += f; nb += b;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { nf += __shfl_xor(nf, o, 64); nb += __shfl_xor(nb, o, 64); }
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][wv] = nf; red[1][wv] = nb; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        ws[blockIdx.x] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        ws[nblk + blockIdx.x] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    }
-}
-
-// one workgroup of 1024 threads: thread t scans a contiguous segment, thread 0 scans the 1024 segment sums
-__global__ void __launch_bounds__(1024) aug_scan_kernel(int* __restrict__ ws, int nblk) {
-    __shared__ int seg[2][1024];
-    const int per = (nblk + 1023) / 1024;
-    const int b0 = min(nblk, (int)threadIdx.x * per), b1 = min(nblk, b0 + per);
-    for (int k = 0; k < 2; ++k) {
-        int s = 0;
-        for (int b = b0; b < b1; ++b) s += ws[k * nblk + b];
-        seg[k][threadIdx.x] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        const int k = threadIdx.x;
-        int run = 0;
-        for (int t = 0; t < 1024; ++t) { const int s = seg[k][t]; seg[k][t] = run; run += s; }
-        ws[4 * nblk + k] = run;
-    }
-    __syncthreads();
-    for (int k = 0; k < 2; ++k) {
-        int run = seg[k][threadIdx.x];
-        for (int b = b0; b < b1; ++b) { ws[(2 + k) * nblk + b] = run; run += ws[k * nblk + b]; }
-    }
-}
-
-__global__ void __launch_bounds__(256)
-aug_scatter_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lbl, int C, int L, long V, float thr,
-                   const int* __restrict__ ws, int nblk, int* __restrict__ fgi, int* __restrict__ bgi) {
-    __shared__ int wtot[2][4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int of = ws[2 * nblk + blockIdx.x], ob = ws[3 * nblk + blockIdx.x];
-    const long base = (long)blockIdx.x * AUG_CHUNK;
-    for (int i = 0; i < AUG_CHUNK / 256; ++i) {
-        const long v = base + i * 256 + threadIdx.x;
-        bool f = false, b = false;
-        if (v < V) fg_bg(img, lbl, C, L, V, thr, v, f, b);
-        const unsigned long long mf = __ballot(f), mb = __ballot(b);
-        if (lane == 0) { wtot[0][wv] = __popcll(mf); wtot[1][wv] = __popcll(mb); }
-        __syncthreads();
-        int pf = of, pb = ob;
-        for (int k = 0; k < wv; ++k) { pf += wtot[0][k]; pb += wtot[1][k]; }
-        if (f) fgi[pf + __popcll(mf & below)] = (int)v;
-        if (b) bgi[pb + __popcll(mb & below)] = (int)v;
-        of += wtot[0][0] + wtot[0][1] + wtot[0][2] + wtot[0][3];
-        ob += wtot[1][0] + wtot[1][1] + wtot[1][2] + wtot[1][3];
-        __syncthreads();
-    }
-}
-
-// ---------------------------------------------------------------- build_class_indices(): map_classes_to_indices as a stable counting sort
-// bit c of the result: the voxel is in the list of class c.  L == 1: class ids, an id >= K is in no list; L > 1 (K == L): channel
-// c is nonzero, lists may overlap.  masked: no list takes a voxel outside any_c(img > thr).
+// classes.  L == 1: class ids, an id >= K is in no list; L > 1 (K == L): channel c is nonzero, lists may overlap.  masked: no list
+// takes a voxel outside any_c(img > thr).
 __device__ __forceinline__ unsigned class_bits(const float* __restrict__ img, const uint8_t* __restrict__ lbl, int C, int L, int K,
                                                long V, int masked, float thr, long v) {
     unsigned bits = 0u;
@@ -256,18 +184,25 @@ __device__ __forceinline__ unsigned class_bits(const float* __restrict__ img, co
     return bits;
 }
 
-// ws (ints): [cnt K][nblk][off K][nblk], class-major.  Lane c of every wave keeps the count of class c: one ballot per class
-// and round, no atomics.
-__global__ void __launch_bounds__(256)
-aug_class_count_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lbl, int C, int L, int K, long V, int masked,
-                       float thr, int* __restrict__ ws, int nblk) {
+// KT = 2: the fg / bg pair, two lists known at compile time; KT = 0: K class lists, K at run time
+struct AugMember { const float* img; const uint8_t* lbl; int C, L, K; long V; int masked; float thr; };
+template <int KT>
+__device__ __forceinline__ unsigned aug_list_bits(const AugMember& m, long v) {
+    if (v >= m.V) return 0u;
+    return KT ? fg_bg(m.img, m.lbl, m.C, m.L, m.V, m.thr, v) : class_bits(m.img, m.lbl, m.C, m.L, m.K, m.V, m.masked, m.thr, v);
+}
+
+// ws (ints): [cnt K][nblk][off K][nblk], list-major (fg / bg: + its two totals).  Per chunk of AUG_CHUNK voxels the number of voxels
+// of every list, from one read of the volume: lane c of every wave keeps the count of list c, one ballot per list and round, no atomics.
+template <int KT>
+__global__ void __launch_bounds__(256) aug_count_kernel(AugMember m, int* __restrict__ ws, int nblk) {
+    const int K = KT ? KT : m.K;
     __shared__ int red[4][AUG_MAXK];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     int mine = 0;
     const long base = (long)blockIdx.x * AUG_CHUNK;
     for (int i = 0; i < AUG_CHUNK / 256; ++i) {
-        const long v = base + i * 256 + threadIdx.x;
-        const unsigned bits = v < V ? class_bits(img, lbl, C, L, K, V, masked, thr, v) : 0u;
+        const unsigned bits = aug_list_bits<KT>(m, base + i * 256 + threadIdx.x);
         for (int c = 0; c < K; ++c) {
             const int n = __popcll(__ballot(bits >> c & 1u));
             if (lane == c) mine += n;
@@ -279,14 +214,15 @@ aug_class_count_kernel(const float* __restrict__ img, const uint8_t* __restrict_
         ws[(long)threadIdx.x * nblk + blockIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// one workgroup of 1024 threads per class, each as aug_scan_kernel takes one of its two lists: thread t scans a contiguous
-// segment, thread 0 the 1024 segment sums; the list's length goes to offsets[c + 1]
-__global__ void __launch_bounds__(1024) aug_class_scan_kernel(int* __restrict__ ws, int nblk, int K, long long* __restrict__ offsets) {
+// one workgroup of 1024 threads per list: exclusive scan of its chunk counts -- thread t scans a contiguous segment, thread 0 the
+// 1024 segment sums -- and the list's length to totals[list] (fg / bg: the two ints behind ws; classes: offsets[1..K], int64)
+template <typename T>
+__global__ void __launch_bounds__(1024) aug_scan_kernel(int* __restrict__ ws, int nblk, T* __restrict__ totals) {
     __shared__ int seg[1024];
     const int per = (nblk + 1023) / 1024;
     const int b0 = min(nblk, (int)threadIdx.x * per), b1 = min(nblk, b0 + per);
     const int* cnt = ws + (long)blockIdx.x * nblk;
-    int* off = ws + ((long)K + blockIdx.x) * nblk;
+    int* off = ws + ((long)gridDim.x + blockIdx.x) * nblk;
     int s = 0;
     for (int b = b0; b < b1; ++b) s += cnt[b];
     seg[threadIdx.x] = s;
@@ -294,7 +230,7 @@ __global__ void __launch_bounds__(1024) aug_class_scan_kernel(int* __restrict__ 
     if (threadIdx.x == 0) {
         int run = 0;
         for (int t = 0; t < 1024; ++t) { const int v = seg[t]; seg[t] = run; run += v; }
-        offsets[blockIdx.x + 1] = run;
+        totals[blockIdx.x] = run;
     }
     __syncthreads();
     int run = seg[threadIdx.x];
@@ -311,38 +247,41 @@ __global__ void aug_class_offsets_kernel(long long* __restrict__ offsets, int K)
     }
 }
 
-// The slot of a voxel in the list of its class: where the list starts (offsets), the scanned offset of the chunk, what earlier
-// rounds of the chunk put there (run), the waves before this one in the round (wtot) and the lanes below in the wave (ballot).
-// Every term counts voxels at lower ravel indices, so each list is ascending and the same on every run.
+// The slot of a voxel in its list: where the list starts (fg / bg: l0 and l1; classes: l0 + offsets[c]), the scanned offset of the
+// chunk plus what earlier rounds of the chunk put there (run), the waves before this one in the round (wtot) and the lanes below in
+// the wave (ballot).  Every term counts voxels at lower ravel indices, so each list is ascending and the same on every run.
+// run and wtot alternate between two copies, so a round needs one barrier: what round i writes was last read in round i - 1.
+template <int KT>
 __global__ void __launch_bounds__(256)
-aug_class_scatter_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lbl, int C, int L, int K, long V, int masked,
-                         float thr, const int* __restrict__ ws, int nblk, const long long* __restrict__ offsets,
-                         int* __restrict__ lists) {
-    __shared__ int wtot[AUG_MAXK][4];
-    __shared__ int run[AUG_MAXK];
+aug_scatter_kernel(AugMember m, const int* __restrict__ ws, int nblk, int* __restrict__ l0, int* __restrict__ l1,
+                   const long long* __restrict__ offsets) {
+    const int K = KT ? KT : m.K;
+    __shared__ int wtot[2][AUG_MAXK][4];
+    __shared__ int run[2][AUG_MAXK];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const unsigned long long below = (1ull << lane) - 1ull;
-    if (threadIdx.x < K) run[threadIdx.x] = ws[((long)K + threadIdx.x) * nblk + blockIdx.x];
+    if (threadIdx.x < K) run[0][threadIdx.x] = ws[((long)K + threadIdx.x) * nblk + blockIdx.x];
     const long base = (long)blockIdx.x * AUG_CHUNK;
     for (int i = 0; i < AUG_CHUNK / 256; ++i) {
+        const int q = i & 1;
         const long v = base + i * 256 + threadIdx.x;
-        const unsigned bits = v < V ? class_bits(img, lbl, C, L, K, V, masked, thr, v) : 0u;
+        const unsigned bits = aug_list_bits<KT>(m, v);
         for (int c = 0; c < K; ++c) {
             const int n = __popcll(__ballot(bits >> c & 1u));
-            if (lane == 0) wtot[c][wv] = n;
+            if (lane == 0) wtot[q][c][wv] = n;
         }
         __syncthreads();
+        if (threadIdx.x < K)
+            run[q ^ 1][threadIdx.x] = run[q][threadIdx.x] + wtot[q][threadIdx.x][0] + wtot[q][threadIdx.x][1] + wtot[q][threadIdx.x][2] +
+                                      wtot[q][threadIdx.x][3];
         for (int c = 0; c < K; ++c) {
-            const unsigned long long m = __ballot(bits >> c & 1u);
-            if (bits >> c & 1u) {
-                int p = run[c] + __popcll(m & below);
-                for (int k = 0; k < wv; ++k) p += wtot[c][k];
-                lists[offsets[c] + p] = (int)v;
-            }
+            const unsigned long long mk = __ballot(bits >> c & 1u);
+            if (!mk) continue;                               // (wave-uniform) no voxel of list c in this wave's 64
+            int p = run[q][c] + __popcll(mk & below);
+            for (int k = 0; k < wv; ++k) p += wtot[q][c][k];
+            int* list = KT ? (c ? l1 : l0) : l0 + offsets[c];
+            if (bits >> c & 1u) list[p] = (int)v;
         }
-        __syncthreads();
-        if (threadIdx.x < K) run[threadIdx.x] += wtot[threadIdx.x][0] + wtot[threadIdx.x][1] + wtot[threadIdx.x][2] + wtot[threadIdx.x][3];
-        __syncthreads();                                     // the next round overwrites wtot
     }
 }
 
@@ -469,12 +408,6 @@ aug_sample_kernel(UnetrAugDesc d, UnetrAugAffineDesc af, const long long* __rest
 }
 
 // ---------------------------------------------------------------- per call: gather (+ normalize partials)
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // crop position p of output voxel o: back through np.rot90(k, axes=(ra, rb)) (n = S[ra] = S[rb]), then the flips
 __device__ __forceinline__ void aug_crop_pos(const int o[3], const int S[3], int k, int ra, int rb, int n, int flips, int p[3]) {
     p[0] = o[0]; p[1] = o[1]; p[2] = o[2];
@@ -1004,7 +937,7 @@ extern "C" int unetr_aug_prep(float* img, const float* lbl, int C, int L, int D,
     const int grid = (int)std::min<long>(cdiv(V, 256), 2048);
     hipLaunchKernelGGL(aug_prep_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, img, lbl, C, L, D, H, W, scale_mode,
                        a_min, a_range, b_range, b_min, b_max, do_box, box, flag);
-    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+    return unetr_check_launch();
 }
 
 extern "C" int unetr_aug_crop(const float* img, const float* lbl, int C, int L, int D, int H, int W, int z0, int y0, int x0,
@@ -1014,7 +947,7 @@ extern "C" int unetr_aug_crop(const float* img, const float* lbl, int C, int L, 
         return UNETR_ERR_ARG;
     hipLaunchKernelGGL(aug_crop_kernel, dim3(cdiv(w, 256), h, d * (C + L)), dim3(256), 0, (hipStream_t)stream, img, lbl, C, L,
                        D, H, W, z0, y0, x0, d, h, w, oimg, olbl);
-    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+    return unetr_check_launch();
 }
 
 extern "C" int unetr_aug_index_count(const float* img, const uint8_t* lbl, int C, int L, long V, float thr, int* ws,
@@ -1023,9 +956,9 @@ extern "C" int unetr_aug_index_count(const float* img, const uint8_t* lbl, int C
     if ((long)ws_ints < unetr_aug_index_ws_ints(V)) return UNETR_ERR_WORKSPACE;
     const int nblk = cdiv(V, AUG_CHUNK);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(aug_count_kernel, dim3(nblk), dim3(256), 0, st, img, lbl, C, L, V, thr, ws, nblk);
-    hipLaunchKernelGGL(aug_scan_kernel, dim3(1), dim3(1024), 0, st, ws, nblk);
-    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+    hipLaunchKernelGGL(aug_count_kernel<2>, dim3(nblk), dim3(256), 0, st, AugMember{img, lbl, C, L, 2, V, 0, thr}, ws, nblk);
+    hipLaunchKernelGGL(aug_scan_kernel<int>, dim3(2), dim3(1024), 0, st, ws, nblk, ws + 4L * nblk);
+    return unetr_check_launch();
 }
 
 extern "C" int unetr_aug_index_scatter(const float* img, const uint8_t* lbl, int C, int L, long V, float thr, const int* ws,
@@ -1033,9 +966,9 @@ extern "C" int unetr_aug_index_scatter(const float* img, const uint8_t* lbl, int
     if (!img || !lbl || !ws || !fg || !bg || C <= 0 || L <= 0 || V <= 0 || V > 0x7fffffffL) return UNETR_ERR_ARG;
     if ((long)ws_ints < unetr_aug_index_ws_ints(V)) return UNETR_ERR_WORKSPACE;
     const int nblk = cdiv(V, AUG_CHUNK);
-    hipLaunchKernelGGL(aug_scatter_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, img, lbl, C, L, V, thr, ws, nblk,
-                       fg, bg);
-    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+    hipLaunchKernelGGL(aug_scatter_kernel<2>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, AugMember{img, lbl, C, L, 2, V, 0, thr},
+                       ws, nblk, fg, bg, (const long long*)nullptr);
+    return unetr_check_launch();
 }
 
 extern "C" long unetr_aug_class_ws_ints(long V, int K) {
@@ -1053,10 +986,10 @@ extern "C" int unetr_aug_class_count(const float* img, const uint8_t* lbl, int C
     if ((long)ws_ints < unetr_aug_class_ws_ints(V, K)) return UNETR_ERR_WORKSPACE;
     const int nblk = cdiv(V, AUG_CHUNK);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(aug_class_count_kernel, dim3(nblk), dim3(256), 0, st, img, lbl, C, L, K, V, image_mask, thr, ws, nblk);
-    hipLaunchKernelGGL(aug_class_scan_kernel, dim3(K), dim3(1024), 0, st, ws, nblk, K, offsets);
+    hipLaunchKernelGGL(aug_count_kernel<0>, dim3(nblk), dim3(256), 0, st, AugMember{img, lbl, C, L, K, V, image_mask, thr}, ws, nblk);
+    hipLaunchKernelGGL(aug_scan_kernel<long long>, dim3(K), dim3(1024), 0, st, ws, nblk, offsets + 1);
     hipLaunchKernelGGL(aug_class_offsets_kernel, dim3(1), dim3(64), 0, st, offsets, K);
-    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+    return unetr_check_launch();
 }
 
 extern "C" int unetr_aug_class_scatter(const float* img, const uint8_t* lbl, int C, int L, int K, long V, int image_mask, float thr,
@@ -1064,9 +997,9 @@ extern "C" int unetr_aug_class_scatter(const float* img, const uint8_t* lbl, int
     if (!aug_class_args_ok(img, lbl, C, L, K, V, image_mask) || !ws || !offsets || !lists) return UNETR_ERR_ARG;
     if ((long)ws_ints < unetr_aug_class_ws_ints(V, K)) return UNETR_ERR_WORKSPACE;
     const int nblk = cdiv(V, AUG_CHUNK);
-    hipLaunchKernelGGL(aug_class_scatter_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, img, lbl, C, L, K, V, image_mask,
-                       thr, ws, nblk, offsets, lists);
-    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+    hipLaunchKernelGGL(aug_scatter_kernel<0>, dim3(nblk), dim3(256), 0, (hipStream_t)stream,
+                       AugMember{img, lbl, C, L, K, V, image_mask, thr}, ws, nblk, lists, (int*)nullptr, offsets);
+    return unetr_check_launch();
 }
 
 extern "C" int unetr_aug_sample(const UnetrAugDesc* d, const long long* vols, int nvol, const int* order, long long* state,
@@ -1074,7 +1007,7 @@ extern "C" int unetr_aug_sample(const UnetrAugDesc* d, const long long* vols, in
     if (!aug_desc_ok(d) || d->sampling == 2 || !vols || nvol <= 0 || !order || !state || !params) return UNETR_ERR_ARG;
     hipLaunchKernelGGL((aug_sample_kernel<false, false>), dim3(1), dim3(256), 0, (hipStream_t)stream, *d, UnetrAugAffineDesc{}, vols,
                        nvol, order, state, params, (float*)nullptr, AugClassArgs{});
-    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+    return unetr_check_launch();
 }
 
 extern "C" int unetr_aug_sample_affine(const UnetrAugDesc* d, const UnetrAugAffineDesc* a, const long long* vols, int nvol,
@@ -1083,7 +1016,7 @@ extern "C" int unetr_aug_sample_affine(const UnetrAugDesc* d, const UnetrAugAffi
         return UNETR_ERR_ARG;
     hipLaunchKernelGGL((aug_sample_kernel<true, false>), dim3(1), dim3(256), 0, (hipStream_t)stream, *d, *a, vols, nvol, order, state,
                        params, affine, AugClassArgs{});
-    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+    return unetr_check_launch();
 }
 
 extern "C" int unetr_aug_sample_classes(const UnetrAugDesc* d, const UnetrAugAffineDesc* a, const long long* vols, int nvol,
@@ -1100,7 +1033,7 @@ extern "C" int unetr_aug_sample_classes(const UnetrAugDesc* d, const UnetrAugAff
     else
         hipLaunchKernelGGL((aug_sample_kernel<false, true>), dim3(1), dim3(256), 0, (hipStream_t)stream, *d, UnetrAugAffineDesc{},
                            vols, nvol, order, state, params, (float*)nullptr, cl);
-    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+    return unetr_check_launch();
 }
 
 extern "C" size_t unetr_aug_gather_ws_bytes(const UnetrAugDesc* d) {
@@ -1109,22 +1042,27 @@ extern "C" size_t unetr_aug_gather_ws_bytes(const UnetrAugDesc* d) {
     return (size_t)d->B * d->C * cdiv(V, AUG_TILE) * 3 * sizeof(double);
 }
 
+// the gather over nblk workgroups per sample (affine: the table of aug_sample_kernel<true, .>, else null) and, with normalize, the
+// pass that reduces its partials
+static int aug_launch_gather(const UnetrAugDesc* d, const long long* vols, int nvol, const int* params, const float* affine, int nblk,
+                             float* x, float* y, void* ws, hipStream_t st) {
+    const dim3 grid(nblk, d->B);
+    double* part = d->normalize ? (double*)ws : nullptr;
+    if (d->normalize && affine) hipLaunchKernelGGL((aug_gather_kernel<true, true>), grid, dim3(256), 0, st, *d, vols, nvol, params, affine, x, y, part);
+    else if (d->normalize) hipLaunchKernelGGL((aug_gather_kernel<true, false>), grid, dim3(256), 0, st, *d, vols, nvol, params, affine, x, y, part);
+    else if (affine) hipLaunchKernelGGL((aug_gather_kernel<false, true>), grid, dim3(256), 0, st, *d, vols, nvol, params, affine, x, y, part);
+    else hipLaunchKernelGGL((aug_gather_kernel<false, false>), grid, dim3(256), 0, st, *d, vols, nvol, params, affine, x, y, part);
+    if (d->normalize)
+        hipLaunchKernelGGL(aug_norm_kernel, dim3(AUG_NORM_WG, d->B * d->C), dim3(256), 0, st, x, (long)d->S0 * d->S1 * d->S2,
+                           (const double*)ws, nblk);
+    return unetr_check_launch();
+}
+
 extern "C" int unetr_aug_gather(const UnetrAugDesc* d, const long long* vols, int nvol, const int* params, float* x, float* y,
                                 void* ws, size_t ws_bytes, void* stream) {
     if (!aug_desc_ok(d) || !vols || nvol <= 0 || !params || !x || !y) return UNETR_ERR_ARG;
     if (d->normalize && (!ws || ws_bytes < unetr_aug_gather_ws_bytes(d))) return UNETR_ERR_WORKSPACE;
-    const long V = (long)d->S0 * d->S1 * d->S2;
-    const int nblk = cdiv(V, AUG_TILE);
-    hipStream_t st = (hipStream_t)stream;
-    if (d->normalize) {
-        hipLaunchKernelGGL((aug_gather_kernel<true, false>), dim3(nblk, d->B), dim3(256), 0, st, *d, vols, nvol, params,
-                           (const float*)nullptr, x, y, (double*)ws);
-        hipLaunchKernelGGL(aug_norm_kernel, dim3(AUG_NORM_WG, d->B * d->C), dim3(256), 0, st, x, V, (const double*)ws, nblk);
-    } else {
-        hipLaunchKernelGGL((aug_gather_kernel<false, false>), dim3(nblk, d->B), dim3(256), 0, st, *d, vols, nvol, params,
-                           (const float*)nullptr, x, y, (double*)nullptr);
-    }
-    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+    return aug_launch_gather(d, vols, nvol, params, nullptr, cdiv((long)d->S0 * d->S1 * d->S2, AUG_TILE), x, y, ws, (hipStream_t)stream);
 }
 
 extern "C" size_t unetr_aug_gather_affine_ws_bytes(const UnetrAugDesc* d) {
@@ -1136,25 +1074,14 @@ extern "C" int unetr_aug_gather_affine(const UnetrAugDesc* d, const long long* v
                                        const float* affine, float* x, float* y, void* ws, size_t ws_bytes, void* stream) {
     if (!aug_desc_ok(d) || !vols || nvol <= 0 || !params || !affine || !x || !y) return UNETR_ERR_ARG;
     if (d->normalize && (!ws || ws_bytes < unetr_aug_gather_affine_ws_bytes(d))) return UNETR_ERR_WORKSPACE;
-    const long V = (long)d->S0 * d->S1 * d->S2;
-    const int nblk = aug_affine_blocks(d);
-    hipStream_t st = (hipStream_t)stream;
-    if (d->normalize) {
-        hipLaunchKernelGGL((aug_gather_kernel<true, true>), dim3(nblk, d->B), dim3(256), 0, st, *d, vols, nvol, params, affine, x,
-                           y, (double*)ws);
-        hipLaunchKernelGGL(aug_norm_kernel, dim3(AUG_NORM_WG, d->B * d->C), dim3(256), 0, st, x, V, (const double*)ws, nblk);
-    } else {
-        hipLaunchKernelGGL((aug_gather_kernel<false, true>), dim3(nblk, d->B), dim3(256), 0, st, *d, vols, nvol, params, affine, x,
-                           y, (double*)nullptr);
-    }
-    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+    return aug_launch_gather(d, vols, nvol, params, affine, aug_affine_blocks(d), x, y, ws, (hipStream_t)stream);
 }
 
 extern "C" int unetr_aug_intensity_sample(const UnetrAugDesc* d, const UnetrAugIntensityDesc* it, const long long* state, int* table,
                                           void* stream) {
     if (!aug_desc_ok(d) || !aug_intensity_desc_ok(it) || !state || !table) return UNETR_ERR_ARG;
     hipLaunchKernelGGL(aug_intensity_sample_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *d, *it, state, table);
-    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+    return unetr_check_launch();
 }
 
 extern "C" size_t unetr_aug_intensity_ws_bytes(const UnetrAugDesc* d) {
@@ -1185,5 +1112,5 @@ extern "C" int unetr_aug_intensity_apply(const UnetrAugDesc* d, const int* table
     hipLaunchKernelGGL(aug_intensity_point_kernel, dim3(nblk, d->C, d->B), dim3(256), 0, st, *d, table, x, psum, pmin, pmax);
     hipLaunchKernelGGL(aug_intensity_tone_kernel, dim3(cdiv(V, AUG_TONE_TILE), d->C, d->B), dim3(256), 0, st, *d, table, x, (const double*)psum,
                        (const float*)pmin, (const float*)pmax, nblk);
-    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
+    return unetr_check_launch();
 }

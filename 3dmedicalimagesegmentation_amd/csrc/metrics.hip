@@ -43,22 +43,6 @@ constexpr int SM_TARGETS = 2 * SM_MAXPCT;     // order statistics per direction 
 constexpr int SM_PASSES = 8;          // radix select: 8 bits per pass over a 64-bit pattern
 constexpr int SM_ACC = 6;             // 64-bit words per slot: count[2], max bits[2], within[2] (index = direction)
 
-__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // class word of one voxel: bit c set where the mask of class c is 1.  FORM 0: one-hot float channels (== 1), 1: float logits
 // and float class ids, 2: uint8 class ids for both (one byte per voxel, never inflated to one-hot)
 enum { HD_ONEHOT = 0, HD_LOGITS = 1, HD_IDS = 2 };
@@ -301,9 +285,9 @@ struct HdF64 {
         for (int o = 32; o > 0; o >>= 1) {                   // a fixed tree: the sum is reproducible
             lmax = fmax(lmax, __shfl_xor(lmax, o, 64));
             lsum = __dadd_rn(lsum, __shfl_xor(lsum, o, 64));
-            lcnt += __shfl_xor(lcnt, o, 64);
-            lwithin += __shfl_xor(lwithin, o, 64);
         }
+        lcnt = wave_sum_u(lcnt);
+        lwithin = wave_sum_u(lwithin);
         if (lane == 0) { red[wave] = lmax; red[4 + wave] = lsum; redc[wave] = lcnt; redc[4 + wave] = lwithin; }
         __syncthreads();
         if (threadIdx.x == 0) {

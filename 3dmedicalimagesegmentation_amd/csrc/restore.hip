@@ -1,6 +1,6 @@
 // The way back from the 1 mm RAS working grid to a scan's own voxel grid: the inverse of
 // Spacingd -> Orientationd -> CropForegroundd (MONAI 0.6.0's Spacingd.inverse / Orientationd.inverse / CropForegroundd.inverse as
-// restated in tests/restore_ref.py) as ONE gather, the twin of csrc/preprocess.hip.  The host (preprocess.Geometry) inverts the
+// restated in tests/restore_ref.py) as ONE gather, the twin of csrc/preprocess.hip: what the two share is csrc/resample.hpp.  The host (preprocess.Geometry) inverts the
 // forward 4x4, so every NATIVE voxel i reads the prediction, which lives on the foreground crop of the resampled grid, at
 //
 //     s = clamp(Minv @ [i, 1], 0, full - 1)        border padding on the un-spaced grid, fp64
@@ -18,27 +18,16 @@
 //                    returns the source's bits.
 #include <math.h>
 #include <stdint.h>
-#include "common.hpp"
+#include "resample.hpp"
 #include "../../include/unetr_hip.h"
 
 namespace {
 
-constexpr int RST_VPT = 4;                    // voxels per thread along x: one float4 / one packed uchar4 store
 constexpr int RST_MAXC = 16;                  // source channels, as unetr_sw_finalize_post's argmax
 enum { RST_POST_NONE = 0, RST_POST_ARGMAX = 1, RST_POST_SIGMOID = 2 };
 
 __device__ __forceinline__ float rst_zero(float) { return 0.f; }
 __device__ __forceinline__ uint8_t rst_zero(uint8_t) { return 0; }
-
-// a + t * (b - a) as two fmas, the instructions of pre_lerp: exact at t = 0 and t = 1
-__device__ __forceinline__ float rst_lerp(float a, float b, float t) { return fmaf(t, b, fmaf(-t, a, a)); }
-
-__device__ __forceinline__ void rst_store4(float* dst, const float* v) {
-    *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-}
-__device__ __forceinline__ void rst_store4(uint8_t* dst, const uint8_t* v) {
-    *reinterpret_cast<uchar4*>(dst) = make_uchar4(v[0], v[1], v[2], v[3]);
-}
 
 // Loads want consecutive lanes on consecutive voxels (lane lx reads voxels xb + lx + TX * k: a wave-wide load then touches the
 // fewest cache lines whatever the source's step; DESIGN.md section 17 has the A/B), stores want 4 consecutive voxels per lane.
@@ -52,7 +41,7 @@ __device__ __forceinline__ uint8_t rst_shfl4(uint8_t v, int lane) { return (uint
 
 template <typename T>
 __device__ __forceinline__ void rst_quad_transpose(T* v, int r) {
-    T out[RST_VPT];
+    T out[RS_VPT];
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
         const int j = (r - d) & 3;                                   // lane j sends its v[(j + d) & 3] = v[r of the receiver]
@@ -65,19 +54,11 @@ __device__ __forceinline__ void rst_quad_transpose(T* v, int r) {
     for (int e = 0; e < 4; ++e) v[e] = out[e];
 }
 
-// one 4-voxel group of one output channel (v in the load layout): an aligned vector store inside the row, voxel by voxel at the
-// row's ends
+// one 4-voxel group of one output channel, v in the load layout
 template <typename T>
 __device__ __forceinline__ void rst_put(T* plane, long chan_off, long o, int x0, int W, bool full, int r, T* v) {
     rst_quad_transpose(v, r);
-    T* dst = plane + chan_off + o + x0;
-    if (full && (chan_off & 3) == 0) {
-        rst_store4(dst, v);
-    } else {
-#pragma unroll
-        for (int k = 0; k < RST_VPT; ++k)
-            if (x0 + k >= 0 && x0 + k < W) dst[k] = v[k];
-    }
+    rs_store_group(plane, chan_off, o, x0, W, full, v);
 }
 
 // SrcT float / uint8_t.  NEAREST: one tap per voxel (mode nearest, or an all-integer matrix).  post / brats are uniform over the
@@ -85,28 +66,24 @@ __device__ __forceinline__ void rst_put(T* plane, long chan_off, long o, int x0,
 template <typename SrcT, bool NEAREST, int BX, int BY, int BZ>
 __global__ __launch_bounds__(256) void restore_kernel(const SrcT* __restrict__ src, int C, unetr_restore_geom G, int N0, int N1,
                                                       int N2, int post, int brats, void* __restrict__ out, int vec_ok) {
-    constexpr int TX = BX / RST_VPT;
-    static_assert(BX % RST_VPT == 0 && TX * BY * BZ == 256, "a brick is 256 threads x 4 voxels");
-    const int t = threadIdx.x;
-    const int y = blockIdx.y * BY + (t / TX) % BY;
-    const int z = blockIdx.z * BZ + t / (TX * BY);
-    if (y >= N1 || z >= N0) return;
-    const long o = ((long)z * N1 + y) * N2;
-    const int lx = t % TX, ql = lx & 3;                          // lane along x, and its place in its quad
+    constexpr int TX = BX / RS_VPT;
+    int y, z;
+    long o;
+    if (!rs_brick_row<BX, BY, BZ>(N0, N1, N2, y, z, o)) return;
+    const int lx = threadIdx.x % TX, ql = lx & 3;                  // lane along x, and its place in its quad
     const int xb = blockIdx.x * BX - (int)(o & 3);               // the row's first (shifted) group of this brick
     if (xb >= N2) return;
     // loads: voxel k of this lane is xb + lx + TX * k.  stores (after the quad transpose): the 4 voxels from x0
-    const int x0 = xb + RST_VPT * ((TX / 4) * ql + (lx >> 2));
-    const bool full = vec_ok && x0 >= 0 && x0 + RST_VPT <= N2;
+    const int x0 = xb + RS_VPT * ((TX / 4) * ql + (lx >> 2));
+    const bool full = vec_ok && x0 >= 0 && x0 + RS_VPT <= N2;
 
     const int c0 = G.crop[0], c1 = G.crop[1], c2 = G.crop[2];
     const long s1 = c2, s0 = (long)c1 * c2, Vin = s0 * c0;
-    bool in[RST_VPT];                         // rint(s) lies inside the crop box
-    int onear[RST_VPT];                       // nearest source voxel (0 for a background voxel: loaded, never used)
-    int obase[RST_VPT], dz[RST_VPT], dy[RST_VPT], dx[RST_VPT];
-    float tz[RST_VPT], ty[RST_VPT], tx[RST_VPT];
+    bool in[RS_VPT];                          // rint(s) lies inside the crop box
+    int onear[RS_VPT];                        // nearest source voxel (0 for a background voxel: loaded, never used)
+    RsTaps tp;
 #pragma unroll
-    for (int k = 0; k < RST_VPT; ++k) {
+    for (int k = 0; k < RS_VPT; ++k) {
         // every source index below is clamped into the crop, so the loads of a voxel off the row's ends (never stored) and of a
         // background voxel (replaced by 0) stay in bounds
         const double i0 = (double)z, i1 = (double)y, i2 = (double)(xb + lx + TX * k);
@@ -115,8 +92,7 @@ __global__ __launch_bounds__(256) void restore_kernel(const SrcT* __restrict__ s
         bool inside = true;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            s[a] = fma(G.m[4 * a], i0, fma(G.m[4 * a + 1], i1, fma(G.m[4 * a + 2], i2, G.m[4 * a + 3])));
-            s[a] = fmin(fmax(s[a], 0.0), (double)(G.full[a] - 1));
+            s[a] = fmin(fmax(rs_affine_row(G.m, a, i0, i1, i2), 0.0), (double)(G.full[a] - 1));
             r[a] = (long)rint(s[a]) - G.origin[a];
             inside = inside && r[a] >= 0 && r[a] < G.crop[a];
         }
@@ -126,50 +102,34 @@ __global__ __launch_bounds__(256) void restore_kernel(const SrcT* __restrict__ s
             const double p0 = fmin(fmax(s[0] - G.origin[0], 0.0), (double)(c0 - 1));
             const double p1 = fmin(fmax(s[1] - G.origin[1], 0.0), (double)(c1 - 1));
             const double p2 = fmin(fmax(s[2] - G.origin[2], 0.0), (double)(c2 - 1));
-            const double f0 = floor(p0), f1 = floor(p1), f2 = floor(p2);
-            const int j0 = (int)f0, j1 = (int)f1, j2 = (int)f2;
-            tz[k] = (float)(p0 - f0); ty[k] = (float)(p1 - f1); tx[k] = (float)(p2 - f2);
-            obase[k] = (int)(j0 * s0 + j1 * s1 + j2);
-            dz[k] = j0 + 1 < c0 ? (int)s0 : 0;
-            dy[k] = j1 + 1 < c1 ? (int)s1 : 0;
-            dx[k] = j2 + 1 < c2 ? 1 : 0;
+            rs_taps(tp, k, p0, p1, p2, c0, c1, c2, s0, s1);
         }
     }
 
     const long Vout = (long)N0 * N1 * N2;
     const bool bytes_out = post != RST_POST_NONE || brats;
-    float best[RST_VPT];
-    int arg[RST_VPT];
-    unsigned set[RST_VPT];                    // bit c: channel c of the discrete result is set (brats)
+    float best[RS_VPT];
+    int arg[RS_VPT];
+    unsigned set[RS_VPT];                     // bit c: channel c of the discrete result is set (brats)
 #pragma unroll
-    for (int k = 0; k < RST_VPT; ++k) { best[k] = 0.f; arg[k] = 0; set[k] = 0u; }
+    for (int k = 0; k < RS_VPT; ++k) { best[k] = 0.f; arg[k] = 0; set[k] = 0u; }
 
     for (int c = 0; c < C; ++c) {
         const SrcT* sc = src + c * Vin;
-        SrcT v[RST_VPT];
+        SrcT v[RS_VPT];
 #pragma unroll
-        for (int k = 0; k < RST_VPT; ++k) {
-            if constexpr (NEAREST) {
-                v[k] = sc[onear[k]];
-            } else {
-                const long b = obase[k];
-                const float a000 = sc[b], a001 = sc[b + dx[k]];
-                const float a010 = sc[b + dy[k]], a011 = sc[b + dy[k] + dx[k]];
-                const float a100 = sc[b + dz[k]], a101 = sc[b + dz[k] + dx[k]];
-                const float a110 = sc[b + dz[k] + dy[k]], a111 = sc[b + dz[k] + dy[k] + dx[k]];
-                const float l00 = rst_lerp(a000, a001, tx[k]), l01 = rst_lerp(a010, a011, tx[k]);
-                const float l10 = rst_lerp(a100, a101, tx[k]), l11 = rst_lerp(a110, a111, tx[k]);
-                v[k] = rst_lerp(rst_lerp(l00, l01, ty[k]), rst_lerp(l10, l11, ty[k]), tz[k]);
-            }
+        for (int k = 0; k < RS_VPT; ++k) {
+            if constexpr (NEAREST) v[k] = sc[onear[k]];
+            else v[k] = rs_trilinear(sc, tp, k);
             if (!in[k]) v[k] = rst_zero(v[k]);            // a select, never a product: a NaN outside the box stays outside
         }
         if (!bytes_out) {
             rst_put<SrcT>((SrcT*)out, c * Vout, o, x0, N2, full, ql, v);
             continue;
         }
-        uint8_t bit[RST_VPT];
+        uint8_t bit[RS_VPT];
 #pragma unroll
-        for (int k = 0; k < RST_VPT; ++k) {
+        for (int k = 0; k < RS_VPT; ++k) {
             const float f = (float)v[k];
             if (c == 0 || f > best[k]) { best[k] = f; arg[k] = c; }      // first maximal channel, as unetr_sw_finalize_post
             bit[k] = post == RST_POST_SIGMOID ? (in[k] && f >= 0.f) : (f == 1.f);
@@ -178,9 +138,9 @@ __global__ __launch_bounds__(256) void restore_kernel(const SrcT* __restrict__ s
         if (post == RST_POST_SIGMOID && !brats) rst_put<uint8_t>((uint8_t*)out, c * Vout, o, x0, N2, full, ql, bit);
     }
     if (!bytes_out || (post == RST_POST_SIGMOID && !brats)) return;
-    uint8_t b[RST_VPT];
+    uint8_t b[RS_VPT];
 #pragma unroll
-    for (int k = 0; k < RST_VPT; ++k) {
+    for (int k = 0; k < RS_VPT; ++k) {
         if (post == RST_POST_ARGMAX) set[k] = in[k] ? 1u << arg[k] : 0u;
         // channels BG / TC / WT / ET -> 1 where WT, then 2 where TC, then 3 where ET: the later rule wins
         b[k] = brats ? ((set[k] & 8u) ? 3 : (set[k] & 2u) ? 2 : (set[k] & 4u) ? 1 : 0) : (uint8_t)(in[k] ? arg[k] : 0);
@@ -190,22 +150,12 @@ __global__ __launch_bounds__(256) void restore_kernel(const SrcT* __restrict__ s
 
 struct RstArgs { const void* src; int C; unetr_restore_geom G; int n0, n1, n2, post, brats; void* out; int vec_ok; };
 
-template <typename SrcT, bool NEAREST, int BX, int BY, int BZ>
-int rst_launch_brick(const RstArgs& a, hipStream_t st) {
-    const long gx = cdiv(a.n2 + RST_VPT - 1, BX), gy = cdiv(a.n1, BY), gz = cdiv(a.n0, BZ);    // + 3: the shifted groups
-    if (gy > 65535 || gz > 65535) return UNETR_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((restore_kernel<SrcT, NEAREST, BX, BY, BZ>), dim3(gx, gy, gz), dim3(256), 0, st, (const SrcT*)a.src, a.C,
-                       a.G, a.n0, a.n1, a.n2, a.post, a.brats, a.out, a.vec_ok);
-    return hipGetLastError() == hipSuccess ? UNETR_OK : UNETR_ERR_LAUNCH;
-}
-
-// axis = the native axis along which the source's fastest axis changes most; the brick shapes are the ones DESIGN.md section 13
-// timed for the forward gather (not re-timed per shape here: section 17)
+// the brick shapes are the ones DESIGN.md section 13 timed for the forward gather (not re-timed per shape here: section 17)
 template <typename SrcT, bool NEAREST>
 int rst_launch(int axis, const RstArgs& a, hipStream_t st) {
-    if (axis == 2) return rst_launch_brick<SrcT, NEAREST, 64, 4, 4>(a, st);
-    if (axis == 1) return rst_launch_brick<SrcT, NEAREST, 16, 8, 8>(a, st);
-    return rst_launch_brick<SrcT, NEAREST, 16, 4, 16>(a, st);
+    RS_BRICK_DISPATCH(axis, a.n0, a.n1, a.n2,
+                      hipLaunchKernelGGL((restore_kernel<SrcT, NEAREST, BX, BY, BZ>), grid, dim3(256), 0, st, (const SrcT*)a.src, a.C,
+                                         a.G, a.n0, a.n1, a.n2, a.post, a.brats, a.out, a.vec_ok));
 }
 
 }  // namespace
@@ -222,17 +172,11 @@ extern "C" int unetr_restore_native(const void* src, int src_u8, int C, unetr_re
         if (vfull > 0x7fffffffL) return UNETR_ERR_UNSUPPORTED;                    // the box lies inside the grid: no more voxels
     }
     if ((long)n0 * n1 * n2 > 0x7fffffffL) return UNETR_ERR_UNSUPPORTED;
-    bool integer = true;
-    for (int i = 0; i < 12; ++i) {
-        if (!isfinite(g.m[i])) return UNETR_ERR_ARG;
-        integer = integer && g.m[i] == rint(g.m[i]);
-    }
+    const RsMatrix ms = rs_scan_matrix(g.m);
+    if (!ms.finite) return UNETR_ERR_ARG;
     const bool bytes_out = post || brats || src_u8;
     RstArgs a{src, C, g, n0, n1, n2, post, brats, out, ((uintptr_t)out & (bytes_out ? 3 : 15)) == 0};
-    int axis = 2;                                  // row 2 of m = the source's fastest axis
-    for (int j = 0; j < 2; ++j)
-        if (fabs(g.m[8 + j]) > fabs(g.m[8 + axis])) axis = j;
     hipStream_t st = (hipStream_t)stream;
-    if (src_u8) return rst_launch<uint8_t, true>(axis, a, st);
-    return (!linear || integer) ? rst_launch<float, true>(axis, a, st) : rst_launch<float, false>(axis, a, st);
+    if (src_u8) return rst_launch<uint8_t, true>(ms.axis, a, st);
+    return (!linear || ms.integer) ? rst_launch<float, true>(ms.axis, a, st) : rst_launch<float, false>(ms.axis, a, st);
 }

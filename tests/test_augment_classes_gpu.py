@@ -9,7 +9,7 @@ import torch
 import augment_classes_ref as K
 import augment_ref as R
 from test_augment_classes_cpu import FREQ_RATIOS, FREQ_SEED
-from test_augment_gpu import _outputs
+from test_augment_gpu import _big_scan_volume, _outputs
 
 pytestmark = pytest.mark.gpu
 THR = 0.25
@@ -85,6 +85,23 @@ def test_class_lists_exact(pkg, dev, name, image_mask):
     assert table.dtype == torch.int64 and tuple(table.shape) == (1, 2)
     assert table.cpu().tolist()[0][1] == off.data_ptr()
     assert tuple(cache.table().shape) == (1, 12)                 # the volume table does not move
+
+
+def test_class_lists_exact_with_more_than_1024_chunks(pkg, dev):
+    """test_augment_gpu's volume of 1025 chunks: every class's scan walks two chunks per thread, the last chunk holds one voxel"""
+    img, lbl = _big_scan_volume()
+    V = lbl.numel()
+    assert -(-V // CHUNK) == 1025 and int(lbl.view(-1)[-1]) == 1 and float(img.view(-1)[-1]) > THR
+    cache = pkg.VolumeCache(dev, image_threshold=THR)
+    i = cache.add(img, lbl)
+    for image_mask in (False, True):
+        cache.build_class_indices(3, image_mask=image_mask)
+        ref = K.class_index_lists_ref(lbl.numpy(), img.numpy(), 3, image_mask, THR)
+        counts = cache.class_counts(i)
+        assert counts == [len(a) for a in ref] and all(counts) and int(ref[1][-1]) == V - 1
+        for c, a in enumerate(ref):
+            assert np.array_equal(cache.class_indices(i, c).cpu().numpy(), a), (image_mask, c)
+        assert cache.class_offsets(i).cpu().tolist() == [0, *np.cumsum(counts).tolist()]
 
 
 def test_lists_of_volumes_added_later(pkg, dev):

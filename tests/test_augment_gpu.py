@@ -1,6 +1,7 @@
 """GPU checks of VolumeCache and RandCropAugment (csrc/augment.hip) against the CPU restatements of tests/augment_ref.py:
 exact index lists and preprocessing, exact gathers for every flip mask x k, the sampler's params table replayed bit for bit,
 its statistics, the reference CT / MR configurations end to end, graph capture and a TrainStep fed by the augment."""
+import functools
 import math
 import struct
 
@@ -46,6 +47,40 @@ def test_index_lists_exact(pkg, dev, C, L, shape, thr):
     assert torch.equal(cache.image(i)[0].cpu(), img) and torch.equal(cache.label(i)[0].cpu(), lbl.to(torch.uint8))
     assert cache.label(i).dtype == torch.uint8 and cache.image(i).shape == (1, C, *shape)
     fg, bg = R.index_lists_ref(lbl, img, thr)
+    assert torch.equal(cache.fg_indices(i).cpu().long(), fg)
+    assert torch.equal(cache.bg_indices(i).cpu().long(), bg)
+
+
+BIG_SCAN_SHAPE = (1, 1, 4096 * 1024 + 1)    # 1025 chunks of 4096 voxels: the smallest volume whose scan walks more than one chunk per thread
+
+
+@functools.lru_cache(maxsize=None)
+def _big_scan_volume():
+    """image [1, *BIG_SCAN_SHAPE] with exact zeros and negatives, class ids 0..2 with about 20 % foreground; the last voxel (alone in
+    the last chunk) has id 1 and an image value above every threshold used, so it ends a list whichever lists are built.  Shared by
+    the tests of both list builders; nobody writes to it."""
+    g = torch.Generator().manual_seed(1025)
+    img = torch.randn(1, *BIG_SCAN_SHAPE, generator=g)
+    img[torch.rand(1, *BIG_SCAN_SHAPE, generator=g) < 0.3] = 0.0
+    r = torch.rand(1, *BIG_SCAN_SHAPE, generator=g)
+    lbl = (r < 0.1).to(torch.int64) + 2 * ((r >= 0.1) & (r < 0.2)).to(torch.int64)
+    lbl.view(-1)[-1] = 1
+    img.view(-1)[-1] = 1.0
+    return img, lbl
+
+
+def test_index_lists_exact_with_more_than_1024_chunks(pkg, dev):
+    """the scan's one workgroup of 1024 threads takes two chunks per thread here: threads 0..511 two each, thread 512 the last chunk
+    (one voxel), the threads above it none"""
+    img, lbl = _big_scan_volume()
+    V = lbl.numel()
+    nchunk = -(-V // 4096)
+    per = -(-nchunk // 1024)
+    assert nchunk == 1025 and per == 2 and -(-nchunk // per) == 513 and V - (nchunk - 1) * 4096 == 1
+    cache = pkg.VolumeCache(dev, image_threshold=0.0)
+    i = cache.add(img, lbl)
+    fg, bg = R.index_lists_ref(lbl, img, 0.0)
+    assert 0.18 * V < fg.numel() < 0.22 * V and bg.numel() > 0 and int(fg[-1]) == V - 1
     assert torch.equal(cache.fg_indices(i).cpu().long(), fg)
     assert torch.equal(cache.bg_indices(i).cpu().long(), bg)
 

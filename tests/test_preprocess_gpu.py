@@ -110,12 +110,12 @@ def test_identity_spacing_is_a_bit_exact_flip_transpose(pkg, dev, shape):
         assert np.abs(gaff - aff).max() <= 1e-12 and np.array_equal(R.io_orientation(gaff), [[0, 1], [1, 1], [2, 1]])
 
 
-def _raw_call(pkg, dev, x, lab, mat, out_shape, L=1, brats=0):
-    """unetr_resample_orient with an explicit matrix"""
+def _raw_call(pkg, dev, x, lab, mat, out_shape, L=1, brats=0, oi=None, ol=None):
+    """unetr_resample_orient with an explicit matrix, into oi / ol where given"""
     xd = x.to(dev).contiguous()
     ld = lab.to(dev).contiguous()
-    oi = torch.full((x.shape[0], *out_shape), float("nan"), device=dev)
-    ol = torch.full((L, *out_shape), 255, dtype=torch.uint8, device=dev)
+    oi = torch.full((x.shape[0], *out_shape), float("nan"), device=dev) if oi is None else oi
+    ol = torch.full((L, *out_shape), 255, dtype=torch.uint8, device=dev) if ol is None else ol
     m = (ctypes.c_double * 12)(*np.asarray(mat, dtype=np.float64).reshape(-1).tolist())
     pkg._capi.call("unetr_resample_orient", xd.data_ptr(), int(xd.dtype == torch.int16), ld.data_ptr(), x.shape[0], L, brats,
                    *x.shape[1:], m, *out_shape, oi.data_ptr(), ol.data_ptr(), torch.cuda.current_stream().cuda_stream)
@@ -140,6 +140,51 @@ def test_border_clamping_at_all_six_faces(pkg, dev, out_shape):
     assert np.abs(gi.numpy() - ref).max() / float(x.abs().max()) <= IMAGE_REL_BOUND
     # the corner output voxels are the source's corner voxels themselves
     assert gi[0, 0, 0, 0] == x[0, 0, -1, 0] and gi[1, -1, -1, -1] == x[1, -1, 0, -1]
+
+
+_ROW_SHAPES = [(5, 7, 1), (5, 3, 3), (3, 5, 4), (3, 3, 5), (2, 3, 7), (17, 9, 70), (2, 1, 70)]       # as test_restore_gpu's
+
+
+@pytest.mark.parametrize("axis", [0, 1, 2])
+def test_row_ends_unaligned_outputs_and_brick_choice(pkg, dev, axis):
+    """output rows of 1, 3, 4, 5, 7 and 70 voxels (row offsets of every residue mod 4), volumes below one brick and across brick
+    edges, each of the three brick shapes (`axis` is the output axis the source's fastest axis moves along), two image and two label
+    channels so that channel planes start off the 4-voxel boundary, and outputs that start one element past the vector alignment:
+    element-wise stores must write the same values and nothing else"""
+    rng = np.random.default_rng(60 + axis)
+    residues, rows = set(), set()
+    for n, out_shape in enumerate(_ROW_SHAPES):
+        perm = {0: (2, 1, 0), 1: (0, 2, 1), 2: (0, 1, 2)}[axis]                      # source axis a follows output axis perm[a]
+        scale = (0.83, 1.21, 0.91)
+        shape = tuple(max(2, int(round(out_shape[perm[a]] * scale[a]))) for a in range(3))
+        mat = np.zeros((3, 4))
+        for a in range(3):
+            mat[a, perm[a]], mat[a, 3] = scale[a], 0.125 + 0.25 * a      # no j * scale + offset is a half-integer
+        M4 = np.vstack([mat, [0, 0, 0, 1]])
+        assert int(np.argmax(np.abs(mat[2, :3]))) == axis                            # the brick the entry point chooses
+        assert R.tie_mask(M4, out_shape, shape).mean() == 0
+        residues |= {((z * out_shape[1] + y) * out_shape[2]) % 4 for z in range(out_shape[0]) for y in range(out_shape[1])}
+        rows.add(out_shape[2])
+        lab = torch.as_tensor(rng.integers(0, 200, (2, *shape)), dtype=torch.uint8)
+        sources = [torch.as_tensor(rng.random((2, *shape)) * 400 - 200, dtype=torch.float32)]
+        if n == 5:                                                                    # the int16 source once per axis, on several bricks
+            sources.append(torch.as_tensor(rng.integers(-1024, 3000, (2, *shape)), dtype=torch.int16))
+        want_l = R.fused_gather(lab.numpy(), M4, out_shape, "nearest")
+        for x in sources:
+            gi, gl = _raw_call(pkg, dev, x, lab, mat, out_shape, L=2)
+            err = np.abs(gi.numpy() - R.fused_gather(x.numpy(), M4, out_shape, "bilinear")).max() / float(x.float().abs().max())
+            print(f"axis {axis} out {out_shape} {x.dtype}: image max|gpu - ref| / max|input| = {err:.3e}")
+            assert np.array_equal(gl.numpy().astype(np.float64), want_l), out_shape
+            assert err <= IMAGE_REL_BOUND, (out_shape, err)
+            nf, nb = gi.numel(), gl.numel()
+            fbuf = torch.full((nf + 9,), float("nan"), device=dev)
+            bbuf = torch.full((nb + 9,), 0x5A, dtype=torch.uint8, device=dev)
+            fo, bo = fbuf[1:1 + nf].view(gi.shape), bbuf[1:1 + nb].view(gl.shape)
+            assert fo.data_ptr() % 16 == 4 and bo.data_ptr() % 4 == 1
+            ui, ul = _raw_call(pkg, dev, x, lab, mat, out_shape, L=2, oi=fo, ol=bo)
+            assert torch.equal(_bits(ui), _bits(gi)) and torch.equal(ul, gl), out_shape
+            assert fbuf[0].isnan() and fbuf[1 + nf:].isnan().all() and (bbuf[0] == 0x5A) and (bbuf[1 + nb:] == 0x5A).all()
+    assert residues == {0, 1, 2, 3} and rows == {1, 3, 4, 5, 7, 70}
 
 
 def test_brats_converter_exact(pkg, dev):

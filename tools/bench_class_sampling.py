@@ -6,6 +6,8 @@
     sizes) against the torch route on the same GPU, [torch.nonzero(label.view(-1) == c) for c in range(14)]: host clock around
     work that ends in a synchronise, two warm-up rounds, then --rounds rounds alternating the two; every list is compared with
     torch.nonzero's.
+    The fg / bg index lists of VolumeCache.add on the same volume: unetr_aug_index_count + unetr_aug_index_scatter back to back
+    between two HIP events (add itself reads the two lengths back in between), the lists compared with the cache's.
 (2) One aug(x, y) call at 8 x 96^3 with sampling="label_classes" against "pos_neg": HIP events around --calls calls, --rounds
     windows per mode, alternating.
 --trace runs five builds and nothing else, for `rocprofv3 --kernel-trace --stats -- python tools/bench_class_sampling.py --trace`.
@@ -67,6 +69,23 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t) * 1e3, r
 
+    img, nfg, nbg = cache.image(0), cache.fg_indices(0).numel(), cache.bg_indices(0).numel()
+    nws = pkg._capi.load().unetr_aug_index_ws_ints(u8.numel())
+    ws = torch.empty(nws, dtype=torch.int32, device=dev)
+    fg = torch.empty(max(nfg, 1), dtype=torch.int32, device=dev)
+    bg = torch.empty(max(nbg, 1), dtype=torch.int32, device=dev)
+
+    def index_lists():
+        st = torch.cuda.current_stream().cuda_stream
+        lists = (img.data_ptr(), u8.data_ptr(), 1, 1, u8.numel(), cache.image_threshold, ws.data_ptr(), nws)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        pkg._capi.call("unetr_aug_index_count", *lists, st)
+        pkg._capi.call("unetr_aug_index_scatter", *lists, fg.data_ptr(), bg.data_ptr(), st)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
     if args.trace:
         for _ in range(5):
             build()
@@ -74,16 +93,20 @@ def main():
     for _ in range(2):
         build()
         torch_route()
-    tb, tt = [], []
+        index_lists()
+    tb, tt, ti = [], [], []
     for _ in range(args.rounds):
         tb.append(build())
+        ti.append(index_lists())
         ms, r = torch_route()
         tt.append(ms)
     equal = all(torch.equal(cache.class_indices(0, c).long(), r[c].view(-1)) for c in range(K))
     listed = sum(cache.class_counts(0))
     print(f"lists equal torch.nonzero: {equal}; class counts {cache.class_counts(0)}")
     print(f"voxels {u8.numel()}, listed {listed}: 2 label reads + 4 B per entry = {(2 * u8.numel() + 4 * listed) / 1e6:.1f} MB")
-    for name, v in (("build_class_indices", tb), ("torch.nonzero x %d" % K, tt)):
+    same = torch.equal(fg[:nfg], cache.fg_indices(0)) and torch.equal(bg[:nbg], cache.bg_indices(0))
+    print(f"index lists equal the cache's: {same}; fg {nfg}, bg {nbg}, ws total {ws[nws - 2:].tolist()}")
+    for name, v in (("build_class_indices", tb), ("torch.nonzero x %d" % K, tt), ("index count + scatter", ti)):
         print(f"{name:22s} ms: median {statistics.median(v):.3f} min {min(v):.3f} max {max(v):.3f}")
 
     kw = dict(spatial_size=96, num_samples=4, batch_size=8, seed=1)
