@@ -14,11 +14,13 @@ from .inference import DiceMetric, SlidingWindowInferer, sliding_window_inferenc
 from .metrics import (ConfusionMatrixMetric, HausdorffDistanceMetric, SurfaceDiceMetric, SurfaceDistanceMetric,  # noqa: F401
                       surface_metrics)
 from .postprocess import KeepLargestConnectedComponent, connected_components, remove_small_components  # noqa: F401
+from .morphology import (FillHoles, binary_closing, binary_contour, binary_dilation, binary_erosion, binary_fill_holes,  # noqa: F401
+                         binary_opening)
 from .train_step import TrainStep  # noqa: F401
 from .augment import IntensityAugment, RandCropAugment, VolumeCache  # noqa: F401
 from .preprocess import Geometry, resample_orient, restore_native  # noqa: F401
 from .functional import invalidate_weight_shadows, refresh_derived_weights  # noqa: F401
-from . import _capi, augment, ddp, distance, functional, inference, metrics, postprocess, preprocess, seg_losses, topk_loss, train_step  # noqa: F401
+from . import _capi, augment, ddp, distance, functional, inference, metrics, morphology, postprocess, preprocess, seg_losses, topk_loss, train_step  # noqa: F401
 
 __all__ = ["UNETR", "UNETRLogits", "DiceCELoss", "ranking_loss", "AdamW", "default_precision", "sliding_window_inference",
            "SlidingWindowInferer", "DiceMetric", "ConfusionMatrixMetric", "HausdorffDistanceMetric", "TrainStep", "invalidate_weight_shadows",
@@ -27,4 +29,5 @@ __all__ = ["UNETR", "UNETRLogits", "DiceCELoss", "ranking_loss", "AdamW", "defau
            "remove_small_components", "surface_metrics", "SurfaceDistanceMetric", "SurfaceDiceMetric",
            "SegLoss", "DiceLoss", "TverskyLoss", "GeneralizedDiceLoss", "FocalLoss", "DiceFocalLoss",
            "distance_transform_edt", "signed_distance_map", "BoundaryLoss", "HausdorffDTLoss",
-           "TopKLoss", "DiceTopKLoss", "kth_value", "percentile"]
+           "TopKLoss", "DiceTopKLoss", "kth_value", "percentile",
+           "binary_dilation", "binary_erosion", "binary_opening", "binary_closing", "binary_contour", "binary_fill_holes", "FillHoles"]

@@ -727,6 +727,39 @@ int unetr_ccl(const float* in, float* out, int* labels, int* sizes, int* ncomp, 
               unsigned applied, int independent, int connectivity, int rule, int min_size, void* ws, size_t ws_bytes, int group,
               void* stream);
 
+/* ---- binary morphology on bit-packed masks and hole filling (csrc/morphology.hip; scipy.ndimage.binary_dilation / _erosion /
+ * _opening / _closing / binary_fill_holes and the fill_holes rule of MONAI) ----
+ * unetr_morph treats in [B,C,D,H,W] (float32, or one byte per voxel -- uint8 / bool -- when u8) as N = B*C masks [D,H,W], set
+ * where in != 0, or where in == class_id when class_id >= 0 (a class-id map), and writes 0 / 1 in the same type and layout to
+ * out (which must not be in).  The masks are packed to one bit per voxel (uint64 [N,D,H,ceil(W/64)], bit b of word w = voxel
+ * x = 64 w + b), stepped in that form and unpacked once:
+ *   op 0  dilation: `iterations` steps with the structuring element scipy.ndimage.generate_binary_structure(3, connectivity)
+ *         (connectivity 1, 2, 3 = 6, 18, 26 neighbours and the centre); every voxel outside the volume reads as border_value;
+ *   op 1  erosion, likewise;
+ *   op 2  opening = erosion then dilation, `iterations` steps each, border_value 0 for both (scipy.ndimage.binary_opening);
+ *   op 3  closing = dilation then erosion, likewise (so it erodes at the faces of the volume, as scipy's does);
+ *   op 4  contour = in & ~erosion(in, 1 step, border_value 0); iterations and border_value are not read.
+ * Up to 4 steps run in one launch on tiles held in LDS, so an operation takes ceil(iterations / 4) launches besides pack and
+ * unpack.  ws holds unetr_morph_workspace_bytes(D, H, W, N) bytes (0 for an unsupported shape): two packed images.
+ *
+ * unetr_fill_holes fills the holes of in given labels [B,C,D,H,W] (int32) = the canonical labels unetr_ccl gives the
+ * components of the background in == 0 under `connectivity`.  A hole is a labelled component with no voxel on the six faces.
+ *   class_map 0  N = B*C masks: out = 1 where in != 0 or the voxel lies in a hole, else 0 (scipy.ndimage.binary_fill_holes);
+ *   class_map 1  class-id map [B,1,D,H,W], integral ids 0..31: a hole becomes id l when the non-zero values among the
+ *                neighbours (under `connectivity`) of its voxels are all l and bit l of applied is set (bit 0 must be clear);
+ *                every other voxel keeps its value.
+ * ws holds unetr_fill_holes_workspace_bytes(D, H, W, N, class_map) bytes: one flag byte per voxel, and with class_map one
+ * 32-bit word of neighbour ids per voxel, both addressed by canonical label and zeroed by a memset in the stream.
+ *
+ * Both: C <= 16; D, H, W <= 1024, D*H*W < 2^31 - 1 and B*C <= 65535, else UNETR_ERR_UNSUPPORTED.  Integer atomics only; fixed
+ * grids; no allocation, no host synchronisation.  (Additions: no existing signature moved, UNETR_ABI_VERSION stays.) */
+size_t unetr_morph_workspace_bytes(int D, int H, int W, int N);
+int unetr_morph(const void* in, void* out, int u8, int B, int C, int D, int H, int W, int class_id, int op, int iterations,
+                int connectivity, int border_value, void* ws, size_t ws_bytes, void* stream);
+size_t unetr_fill_holes_workspace_bytes(int D, int H, int W, int N, int class_map);
+int unetr_fill_holes(const void* in, void* out, int u8, const int* labels, int B, int C, int D, int H, int W, int class_map,
+                     unsigned applied, int connectivity, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- fused AdamW over one flat fp32 buffer (torch.optim.AdamW semantics; unetr_segmentation_3d.py:522) */
 int unetr_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                 float eps, float weight_decay, const float* step_dev,
