@@ -10,6 +10,7 @@ from .seg_losses import DiceFocalLoss, DiceLoss, FocalLoss, GeneralizedDiceLoss,
 from .distance import BoundaryLoss, HausdorffDTLoss, distance_transform_edt, signed_distance_map  # noqa: F401
 from .topk_loss import DiceTopKLoss, TopKLoss, kth_value, percentile  # noqa: F401
 from .optim import AdamW  # noqa: F401
+from .grad_clip import clip_grad_norm_  # noqa: F401
 from .inference import DiceMetric, SlidingWindowInferer, sliding_window_inference  # noqa: F401
 from .metrics import (ConfusionMatrixMetric, HausdorffDistanceMetric, SurfaceDiceMetric, SurfaceDistanceMetric,  # noqa: F401
                       surface_metrics)
@@ -20,7 +21,7 @@ from .train_step import TrainStep  # noqa: F401
 from .augment import IntensityAugment, RandCropAugment, VolumeCache  # noqa: F401
 from .preprocess import Geometry, resample_orient, restore_native  # noqa: F401
 from .functional import invalidate_weight_shadows, refresh_derived_weights  # noqa: F401
-from . import _capi, augment, ddp, distance, functional, inference, metrics, morphology, postprocess, preprocess, seg_losses, topk_loss, train_step  # noqa: F401
+from . import _capi, augment, ddp, distance, functional, grad_clip, inference, metrics, morphology, postprocess, preprocess, seg_losses, topk_loss, train_step  # noqa: F401
 
 __all__ = ["UNETR", "UNETRLogits", "DiceCELoss", "ranking_loss", "AdamW", "default_precision", "sliding_window_inference",
            "SlidingWindowInferer", "DiceMetric", "ConfusionMatrixMetric", "HausdorffDistanceMetric", "TrainStep", "invalidate_weight_shadows",
@@ -30,4 +31,5 @@ __all__ = ["UNETR", "UNETRLogits", "DiceCELoss", "ranking_loss", "AdamW", "defau
            "SegLoss", "DiceLoss", "TverskyLoss", "GeneralizedDiceLoss", "FocalLoss", "DiceFocalLoss",
            "distance_transform_edt", "signed_distance_map", "BoundaryLoss", "HausdorffDTLoss",
            "TopKLoss", "DiceTopKLoss", "kth_value", "percentile",
-           "binary_dilation", "binary_erosion", "binary_opening", "binary_closing", "binary_contour", "binary_fill_holes", "FillHoles"]
+           "binary_dilation", "binary_erosion", "binary_opening", "binary_closing", "binary_contour", "binary_fill_holes", "FillHoles",
+           "clip_grad_norm_"]

@@ -265,6 +265,13 @@ _SIGNATURES = {
     "unetr_adamw": [P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_float, P, P, P],
     "unetr_adamw_reduced": [P, P, c_int, c_float, P, P, c_long, c_float, c_float, c_float, c_float, c_float, P, P, P, P],
     "unetr_adamw_hyper": [P, P, c_int, c_float, P, P, c_long, P, c_float, c_float, c_float, P, P, P, P],
+    "unetr_adamw_hyper_clip": [P, P, c_int, c_float, P, P, c_long, P, c_float, c_float, c_float, P, P, P, P, P],
+    "unetr_grad_sumsq_ranges": [P, c_int, P, c_int, c_long, P, c_size_t, P],
+    "unetr_grad_sumsq": [P, c_int, c_long, P, c_size_t, P],
+    "unetr_grad_clip_finalize": [P, c_long, c_float, P, P],
+    "unetr_grad_clip_set": [P, c_float, P],
+    "unetr_grad_scale_ranges": [P, P, c_int, c_long, P, P],
+    "unetr_grad_scale": [P, c_long, P, P],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + ("unetr_conv3_packed_bytes", "unetr_conv3_packed_1x1_bytes", "unetr_ranking_workspace_floats",

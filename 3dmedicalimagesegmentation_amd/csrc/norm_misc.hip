@@ -1655,25 +1655,39 @@ __global__ void outconv_final_kernel(const float* __restrict__ part, int R, int 
 
 // -------------------------------------------------------------------------------------------- AdamW
 // GB16: gradients come as bf16 (the data-parallel communication buffer after the all-reduce); gscale = 1 / world size
-template <bool GB16>
+// CLIP: the gradient is also multiplied by the clip coefficient in device memory (grad_clip.hip: the clip row's coef, written by
+// unetr_grad_clip_finalize earlier on the stream), g_eff = (g * gscale) * coef -- two roundings, in this order, so that the update
+// equals AdamW on gradients scaled that way beforehand.  Both products are spelled in one contraction-off scope (common.hpp on
+// adamw_elem).  One wave-uniform load; the unclipped instantiations keep their own `* gscale` and are what they were.
+__device__ __forceinline__ float clip_scale(float g, float gscale, float coef) {
+#pragma clang fp contract(off)
+    const float gs = g * gscale;
+    return gs * coef;
+}
+template <bool GB16, bool CLIP>
 __global__ void __launch_bounds__(256)
 adamw_kernel(float* __restrict__ p, const void* __restrict__ gsrc, float gscale, float* __restrict__ m, float* __restrict__ v,
              long n4, long n, float lr, float b1, float b2, float eps, float wd, const float* __restrict__ step_dev,
-             uint16_t* __restrict__ shadow, uint32_t* __restrict__ words, const float* __restrict__ hyper) {
+             uint16_t* __restrict__ shadow, uint32_t* __restrict__ words, const float* __restrict__ hyper, const float* __restrict__ gcoef) {
     const AdamWCoef c = adamw_coef_at(hyper, lr, b1, b2, eps, wd, *step_dev);
+    float coef = 1.f;
+    if (CLIP) coef = *gcoef;
     auto grad1 = [&](long i) -> float {
-        if (GB16) { uint32_t u = (uint32_t)((const uint16_t*)gsrc)[i] << 16; return __builtin_bit_cast(float, u) * gscale; }
-        return ((const float*)gsrc)[i] * gscale;
+        float g;
+        if (GB16) { uint32_t u = (uint32_t)((const uint16_t*)gsrc)[i] << 16; g = __builtin_bit_cast(float, u); }
+        else g = ((const float*)gsrc)[i];
+        return CLIP ? clip_scale(g, gscale, coef) : g * gscale;
     };
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         // streamed once per step: non-temporal accesses keep the 2.8 GB of optimizer traffic from evicting what the next forward reads
         f32x4 pv = __builtin_nontemporal_load((f32x4*)p + i), mv = __builtin_nontemporal_load((f32x4*)m + i), vv = __builtin_nontemporal_load((f32x4*)v + i), gv;
-        if (GB16) gv = __builtin_convertvector(__builtin_nontemporal_load((const bf16x4*)gsrc + i), f32x4) * gscale;
-        else gv = __builtin_nontemporal_load((const f32x4*)gsrc + i) * gscale;
+        if (GB16) gv = __builtin_convertvector(__builtin_nontemporal_load((const bf16x4*)gsrc + i), f32x4);
+        else gv = __builtin_nontemporal_load((const f32x4*)gsrc + i);
+        if (!CLIP) gv = gv * gscale;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float pe = pv[e], me = mv[e], ve = vv[e];
-            adamw_elem(pe, me, ve, gv[e], c);
+            adamw_elem(pe, me, ve, CLIP ? clip_scale(gv[e], gscale, coef) : gv[e], c);
             pv[e] = pe; mv[e] = me; vv[e] = ve;
         }
         __builtin_nontemporal_store(pv, (f32x4*)p + i); __builtin_nontemporal_store(mv, (f32x4*)m + i); __builtin_nontemporal_store(vv, (f32x4*)v + i);
@@ -2267,7 +2281,7 @@ extern "C" int unetr_outconv_in_bwd(const float* dlogits, const void* c2, long l
 
 static int adamw_launch(float* p, const void* g, int g_bf16, float gscale, float* m, float* v, long n, float lr, float beta1,
                         float beta2, float eps, float weight_decay, const float* step_dev, void* shadow_bf16, void* shadow_x3, void* stream,
-                        const float* hyper = nullptr) {
+                        const float* hyper = nullptr, const float* gcoef = nullptr) {
     if (!p || !g || !m || !v || !step_dev || n <= 0 || (reinterpret_cast<uintptr_t>(shadow_bf16) & 7) || (reinterpret_cast<uintptr_t>(shadow_x3) & 15)) return UNETR_ERR_ARG;
     if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) return UNETR_ERR_ARG;
     if (reinterpret_cast<uintptr_t>(g) & (g_bf16 ? 7 : 15)) return UNETR_ERR_ARG;
@@ -2278,12 +2292,12 @@ static int adamw_launch(float* p, const void* g, int g_bf16, float gscale, float
     int cap = 4096;
     if (const char* e = getenv("UNETR_ADAMW_GRID")) { const int v = atoi(e); if (v >= 64) cap = v; }
     dim3 grid(grid_for(std::max<long>(n4, 1), 256, cap));
-    if (g_bf16)
-        hipLaunchKernelGGL(adamw_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p, g, gscale, m, v, n4, n, lr, beta1, beta2, eps,
-                           weight_decay, step_dev, (uint16_t*)shadow_bf16, (uint32_t*)shadow_x3, hyper);
-    else
-        hipLaunchKernelGGL(adamw_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p, g, gscale, m, v, n4, n, lr, beta1, beta2, eps,
-                           weight_decay, step_dev, (uint16_t*)shadow_bf16, (uint32_t*)shadow_x3, hyper);
+#define ADAMW_LAUNCH(GB16, CLIP)                                                                                                        \
+    hipLaunchKernelGGL((adamw_kernel<GB16, CLIP>), grid, dim3(256), 0, (hipStream_t)stream, p, g, gscale, m, v, n4, n, lr, beta1, beta2, eps, \
+                       weight_decay, step_dev, (uint16_t*)shadow_bf16, (uint32_t*)shadow_x3, hyper, gcoef)
+    if (gcoef) { if (g_bf16) ADAMW_LAUNCH(true, true); else ADAMW_LAUNCH(false, true); }
+    else { if (g_bf16) ADAMW_LAUNCH(true, false); else ADAMW_LAUNCH(false, false); }
+#undef ADAMW_LAUNCH
     return unetr_check_launch();
 }
 
@@ -2315,4 +2329,12 @@ extern "C" int unetr_adamw_hyper(float* p, const void* g, int g_is_bf16, float g
                                  float beta1, float beta2, float eps, const float* step_dev, void* shadow_bf16, void* shadow_x3, void* stream) {
     if (!hyper_dev || ((uintptr_t)hyper_dev & 3)) return UNETR_ERR_ARG;
     return adamw_launch(p, g, g_is_bf16, gscale, m, v, n, 0.f, beta1, beta2, eps, 0.f, step_dev, shadow_bf16, shadow_x3, stream, hyper_dev);
+}
+
+// unetr_adamw_hyper with the gradient also multiplied by the clip coefficient at gcoef_dev (device memory, read when the kernel runs)
+extern "C" int unetr_adamw_hyper_clip(float* p, const void* g, int g_is_bf16, float gscale, float* m, float* v, long n, const float* hyper_dev,
+                                      float beta1, float beta2, float eps, const float* step_dev, void* shadow_bf16, void* shadow_x3,
+                                      const float* gcoef_dev, void* stream) {
+    if (!hyper_dev || ((uintptr_t)hyper_dev & 3) || !gcoef_dev || ((uintptr_t)gcoef_dev & 3)) return UNETR_ERR_ARG;
+    return adamw_launch(p, g, g_is_bf16, gscale, m, v, n, 0.f, beta1, beta2, eps, 0.f, step_dev, shadow_bf16, shadow_x3, stream, hyper_dev, gcoef_dev);
 }

@@ -13,7 +13,12 @@ The scalars that change during a run live on the device too: one ``hyper`` row `
 read by every AdamW kernel when it RUNS.  ``sync_hyper()`` uploads ``group["lr"]`` / ``group["weight_decay"]`` when they changed (a
 ``torch.optim.lr_scheduler`` keeps working under hipGraph replay), ``set_schedule()`` moves the schedule itself into the captured
 step (it rides on the step-counter launch), and ``state_dict()`` / ``load_state_dict()`` speak torch.optim.AdamW's schema in both
-modes, loading in place so that captured graphs stay valid."""
+modes, loading in place so that captured graphs stay valid.
+
+``max_grad_norm=``: the gradients are clipped by their global L2 norm (torch.nn.utils.clip_grad_norm_ semantics, grad_clip.py) inside
+``step()``: a sum-of-squares launch over exactly the gradients about to be applied and a one-workgroup finalize write the clip row
+``{norm, coef, max_norm, nonfinite}`` in device memory, and every AdamW launch multiplies its gradients by ``coef`` as it reads them
+(``unetr_adamw_hyper_clip``) -- the gradients themselves are not rewritten.  Two launches more per step, none when it is off."""
 import ctypes
 import math
 import struct
@@ -21,6 +26,7 @@ import struct
 import torch
 
 from . import functional as Fn
+from . import grad_clip
 from ._capi import LrSchedule, call
 
 SCHEDULES = {"constant": 0, "warmup_cosine": 1, "poly": 2}
@@ -51,9 +57,16 @@ def schedule_lr(sched, s):
 
 
 class AdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, flat=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, flat=None, max_grad_norm=None):
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
             raise ValueError("invalid AdamW hyper-parameter")
+        # None: no clipping, no extra launch; a positive number: clip the global gradient norm to it; float("inf"): measure only
+        self.max_grad_norm = None if max_grad_norm is None else grad_clip.check_max_norm(max_grad_norm)
+        self._clip = None        # device tensor [4]: the clip row {norm, coef, max_norm, nonfinite}, written by the finalize launch
+        self._clip_uploaded = None   # max_norm as last written to the row by the host
+        self._clip_ws = None     # per-tensor path: the float64 workspace of the sum-of-squares launches
+        self._clip_ws_outgrown = []   # smaller workspaces it replaced, kept alive: a captured step may still write them
+        self._clip_tables = {}   # arena paths: pattern -> (table, rows, blocks, workspace)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._steps = {}   # group index -> flat device tensor of per-parameter step counts
         self._masks = {}   # (group index, pattern) -> 0/1 increment tensor
@@ -150,6 +163,96 @@ class AdamW(torch.optim.Optimizer):
         if self._hyper is None:
             return self.schedule_lr(0, group)
         return float(self._hyper[group, 0])
+
+    # ---- gradient clipping by global norm ----------------------------------------------------------------------------------
+    def set_max_grad_norm(self, max_norm):
+        """Change the clipping threshold: a stream-ordered single-thread write of the clip row's ``max_norm`` (no host
+        synchronisation), which the finalize launch READS when it runs -- legal between replays of a captured step, which then
+        clips to the new value.  ``float("inf")`` = measure, never scale.  While the current stream is capturing the write would
+        become part of the graph, so it raises there (the rule of ``sync_hyper``).  Switching clipping on or off (``None``) changes
+        which launches a step makes: only before a TrainStep captures."""
+        on = max_norm is not None
+        v = grad_clip.check_max_norm(max_norm) if on else None
+        if on != (self.max_grad_norm is not None) and self._captured:
+            raise RuntimeError("set_max_grad_norm: a captured step already uses this optimizer (whether it clips is frozen in the "
+                               "graph); switch clipping on or off before TrainStep captures")
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing() and v != self.max_grad_norm:
+            raise RuntimeError("AdamW.set_max_grad_norm: called while a hipGraph is being captured -- the write would be replayed with "
+                               "every step; call it before the capture or between replays")
+        self.max_grad_norm = v
+        if on and self._clip is not None:
+            self._sync_clip()
+
+    def _sync_clip(self):
+        """the clip row exists and holds the host's max_norm (created / uploaded outside capture only)"""
+        if self._clip is not None and self._clip_uploaded == self.max_grad_norm:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("AdamW: the clip row does not exist yet (or max_grad_norm changed on the host) and cannot be written while a "
+                               "hipGraph is being captured; run one eager step before the capture")
+        if self._clip is None:
+            self._clip = grad_clip.new_row(self._device(), self.max_grad_norm)
+        else:
+            call("unetr_grad_clip_set", self._clip.data_ptr(), self.max_grad_norm, torch.cuda.current_stream().cuda_stream)
+        self._clip_uploaded = self.max_grad_norm
+
+    def _clip_row(self):
+        if self.max_grad_norm is None:
+            raise RuntimeError("AdamW was built without max_grad_norm: no gradient norm is measured")
+        if self._clip is None:
+            self._sync_clip()
+        return self._clip
+
+    def grad_norm(self):
+        """the global gradient norm of the last step: a 0-d DEVICE view of the clip row (no synchronisation; ``float()`` it to read)"""
+        return self._clip_row()[0]
+
+    def clip_coef(self):
+        """the factor the last step multiplied its gradients by, min(1, max_norm / (norm + 1e-6)): a 0-d device view"""
+        return self._clip_row()[1]
+
+    def nonfinite_steps(self):
+        """how many steps so far had an inf / NaN gradient norm (a host read: it synchronises; meant for the end of an epoch)"""
+        return int(self._clip_row()[3])
+
+    def _gcoef_ptr(self):
+        return self._clip.data_ptr() + 4
+
+    def _clip_arena(self, pattern, src, gscale):
+        """norm + coefficient of the gradients of ``pattern`` read from ``src``, a flat fp32 / bf16 tensor laid out like the arena (the
+        gradient arena itself, or the all-reduced communication buffer: gscale = 1 / world): one table-driven launch + finalize"""
+        self._sync_clip()
+        ent = self._clip_tables.get(pattern)
+        if ent is None:
+            flat = self._flat
+            table, nr, blocks = grad_clip.range_table(flat["offsets"], flat["params"], pattern, flat["param"].device)
+            ent = self._clip_tables[pattern] = (table, nr, blocks, torch.zeros(max(blocks, 1), dtype=torch.float64, device=flat["param"].device))
+        table, nr, blocks, ws = ent
+        if not nr:
+            return
+        grad_clip.sumsq_ranges(src, table, nr, blocks, ws)
+        grad_clip.finalize(ws, blocks, gscale, self._clip)
+
+    def _clip_tensors(self, grads):
+        """the same over a list of contiguous gradient tensors: one partial launch per tensor, each into its own workspace slots"""
+        self._sync_clip()
+        grads = [g for g in grads if g.numel()]
+        need = sum(grad_clip.blocks_of(g.numel()) for g in grads)
+        if not need:
+            return
+        if self._clip_ws is None or self._clip_ws.numel() < need:
+            if self._clip_ws is not None:
+                self._clip_ws_outgrown.append(self._clip_ws)      # (a captured step may still write the smaller one)
+            self._clip_ws = torch.zeros(need, dtype=torch.float64, device=grads[0].device)
+        grad_clip.finalize(self._clip_ws, grad_clip.sumsq_tensors(grads, self._clip_ws), 1.0, self._clip)
+
+    def _adamw(self, p, g, g_bf16, gscale, m, v, n, gi, b1, b2, eps, step_ptr, sptr, wptr, stream):
+        """one streaming AdamW launch; with clipping on, the form that also reads the coefficient of the clip row"""
+        if self.max_grad_norm is None:
+            call("unetr_adamw_hyper", p, g, g_bf16, gscale, m, v, n, self._hyper_ptr(gi), b1, b2, eps, step_ptr, sptr, wptr, stream)
+        else:
+            call("unetr_adamw_hyper_clip", p, g, g_bf16, gscale, m, v, n, self._hyper_ptr(gi), b1, b2, eps, step_ptr, sptr, wptr,
+                 self._gcoef_ptr(), stream)
 
     # ---- checkpoints in torch.optim.AdamW's schema ------------------------------------------------------------------------
     def _arena_mode(self):
@@ -300,6 +403,25 @@ class AdamW(torch.optim.Optimizer):
                 loss = closure()
         stream = torch.cuda.current_stream().cuda_stream
         per_tensor = False
+        contig = {}          # clipping, per-tensor path: the contiguous copies of non-contiguous gradients the norm was taken over
+        if self.max_grad_norm is not None:
+            # the norm is global over all groups and is taken before the first update
+            group0 = self.param_groups[0]
+            pattern0 = tuple(p.grad is not None for p in group0["params"])
+            if self._flat is not None and any(pattern0) and self._grads_in_arena(group0["params"], pattern0):
+                self._clip_arena(pattern0, self._flat["grad"], 1.0)
+            else:
+                grads = []
+                for group in self.param_groups:
+                    for p in group["params"]:
+                        if p.grad is not None:
+                            if not p.grad.is_cuda:
+                                raise RuntimeError("HIP AdamW needs fp32 parameters on a ROCm device (no CPU fallback)")
+                            g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                            contig[id(p)] = g
+                            grads.append(g)
+                if grads:
+                    self._clip_tensors(grads)
         for gi, group in enumerate(self.param_groups):
             b1, b2 = group["betas"]
             params = group["params"]
@@ -320,13 +442,13 @@ class AdamW(torch.optim.Optimizer):
                 if not p.is_contiguous():
                     raise RuntimeError("HIP AdamW needs contiguous parameters")
                 if not g.is_contiguous():
-                    g = g.contiguous()
+                    g = contig[id(p)] if id(p) in contig else g.contiguous()
                 st = self.state[p]
                 if not st:
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                call("unetr_adamw_hyper", p.data_ptr(), g.data_ptr(), 0, 1.0, st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(),
-                     self._hyper_ptr(gi), b1, b2, group["eps"], steps.data_ptr() + 4 * i, Fn.shadow_ptr_for_update(p), None, stream)
+                self._adamw(p.data_ptr(), g.data_ptr(), 0, 1.0, st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(),
+                            gi, b1, b2, group["eps"], steps.data_ptr() + 4 * i, Fn.shadow_ptr_for_update(p), None, stream)
         if self._flat is not None and per_tensor:      # (per-tensor launches write neither the bf16x3 words nor the transposed twins)
             Fn.after_step(self._flat, [p for g in self.param_groups for p in g["params"] if p.grad is not None], arena=False, repack=False)
         Fn.refresh_conv_packs()          # one grouped launch: packed conv weights follow the update
@@ -360,21 +482,24 @@ class AdamW(torch.optim.Optimizer):
         sptr = shadow.data_ptr() + lo * 2 if shadow is not None else None
         words = flat.get("shadow_x3")          # bf16x3 mode: the word shadow (derived_weights.weight_x3), written by the same kernel
         wptr = words.data_ptr() + lo * 4 if words is not None else None
-        call("unetr_adamw_hyper", flat["param"].data_ptr() + lo * 4, gptr + lo * (2 if g_bf16 else 4), int(g_bf16), gscale,
-             m.data_ptr() + lo * 4, v.data_ptr() + lo * 4, hi - lo, self._hyper_ptr(0), b1, b2, group["eps"],
-             steps.data_ptr() + 4 * i, sptr, wptr, stream)
+        self._adamw(flat["param"].data_ptr() + lo * 4, gptr + lo * (2 if g_bf16 else 4), int(g_bf16), gscale,
+                    m.data_ptr() + lo * 4, v.data_ptr() + lo * 4, hi - lo, 0, b1, b2, group["eps"],
+                    steps.data_ptr() + 4 * i, sptr, wptr, stream)
         if torch.cuda.is_current_stream_capturing():
             self._runs_captured.add((i, j))
         for k in range(i, j + 1):
             self._host_steps[k] += 1
 
+    def _grads_in_arena(self, params, pattern):
+        gbase = self._flat["grad"].data_ptr()
+        return all(not has or p.grad.data_ptr() == gbase + o * 4 for p, o, has in zip(params, self._flat["offsets"], pattern))
+
     def _flat_step(self, group, params, pattern, dev, stream):
         """One launch per contiguous run of parameters with arena gradients and equal step counts."""
         flat = self._flat
         gbase = flat["grad"].data_ptr()
-        for p, o, has in zip(params, flat["offsets"], pattern):
-            if has and p.grad.data_ptr() != gbase + o * 4:
-                return False          # some gradient is not in the arena (e.g. accumulated): per-tensor path
+        if not self._grads_in_arena(params, pattern):
+            return False          # some gradient is not in the arena (e.g. accumulated): per-tensor path
         if self._flat_state is None:
             self._flat_state = (torch.zeros_like(flat["param"]), torch.zeros_like(flat["param"]))
         steps = self._advance_steps(0, params, pattern, dev)
@@ -392,6 +517,10 @@ class AdamW(torch.optim.Optimizer):
     def begin_fused_step(self, pattern):
         from . import _capi
         flat = self._flat
+        if self.max_grad_norm is not None:
+            raise RuntimeError("begin_fused_step: gradient clipping (max_grad_norm) cannot be combined with the fused update -- the "
+                               "weight-gradient epilogue updates the ViT weights inside the launch that produces their gradients, when "
+                               "no global gradient norm exists yet; use the unfused step")
         if flat is None or len(self.param_groups) != 1 or flat.get("state") is None:
             raise RuntimeError("begin_fused_step needs AdamW(..., flat=model.use_flat_buffers())")
         group = self.param_groups[0]
@@ -488,6 +617,14 @@ class AdamW(torch.optim.Optimizer):
         return self._advance_steps(0, self.param_groups[0]["params"], plan["pattern"], self._flat["param"].device)
 
     @torch.no_grad()
+    def clip_reduced(self, plan, gsrc, gscale):
+        """Clipping on: norm and coefficient of the planned gradients read from ``gsrc`` (the communication buffer once EVERY piece
+        has been reduced) times ``gscale``, on the current stream.  ``step_runs`` must follow it, not precede it: every rank measures
+        the same reduced buffer and gets the same coefficient.  A no-op when clipping is off."""
+        if self.max_grad_norm is not None:
+            self._clip_arena(plan["pattern"], gsrc, gscale)
+
+    @torch.no_grad()
     def step_runs(self, plan, ks, steps, gsrc, gscale):
         g_bf16 = gsrc.dtype == torch.bfloat16
         if not g_bf16 and gsrc.dtype != torch.float32:
@@ -512,7 +649,15 @@ class AdamW(torch.optim.Optimizer):
         if not g_bf16 and gsrc.dtype != torch.float32:
             raise RuntimeError("gradient source must be fp32 or bf16")
         runs = plan["runs"]
-        for k in (order if order is not None else range(len(runs))):      # order: the order the pieces finish reducing in
+        order = list(order if order is not None else range(len(runs)))      # order: the order the pieces finish reducing in
+        if self.max_grad_norm is not None:
+            # the global norm needs every range reduced: all the waits first, then the norm, then the updates
+            if before_run is not None:
+                for k in order:
+                    before_run(k, runs[k][2], runs[k][3])
+            before_run = None
+            self.clip_reduced(plan, gsrc, gscale)
+        for k in order:
             run = runs[k]
             if before_run is not None:
                 before_run(k, run[2], run[3])

@@ -54,7 +54,7 @@ def split_range(flat, lo, hi, pieces):
 class TrainStep:
     def __init__(self, model, criterion, optimizer, x, y, *, use_graph=True, data_parallel=False, process_group=None,
                  comm_dtype=torch.float32, tail_pieces=2, warmup=2, overlap_update=False, fuse_update=False, fuse_comm=True,
-                 handover="host", loss_fn=None, freeze_encoder=False, extra_cuts=()):
+                 handover="host", loss_fn=None, freeze_encoder=False, extra_cuts=(), max_grad_norm=None):
         """loss_fn(enc4, logits) -> scalar loss: replaces ``criterion(logits, y)`` (the ranking pre-training step,
         unetr_ranking_pretraining_3d.py:259-262, takes its loss from enc4 in the "feat" stage and from the logits in the "recon"
         stage); the model must then return the (enc4, logits) tuple.  freeze_encoder: the forward of this step runs
@@ -76,7 +76,19 @@ class TrainStep:
         cast per piece covers the other parameters.  Same bits in the communication buffer as the separate cast.
         overlap_update (single GPU): the data-parallel launch form without a process group -- backward in passes, AdamW on
         each pass's arena range on the side stream underneath the passes that follow -- captured as ONE hipGraph in which the
-        side stream is a branch: the bandwidth-bound optimizer kernels hide under the latency-bound ViT backward chain."""
+        side stream is a branch: the bandwidth-bound optimizer kernels hide under the latency-bound ViT backward chain.
+        max_grad_norm: shorthand for ``optimizer.set_max_grad_norm(v)`` before the warm-up; ``AdamW(max_grad_norm=...)`` is the same.
+        With clipping on (optim.AdamW, grad_clip.py) the gradients are clipped by their global L2 norm inside the step, captured
+        or not: single GPU, ``opt.step()`` measures the arena and its AdamW launches read the coefficient from device memory.  In the
+        data-parallel / overlap forms the all-reduces stay where they are, underneath backward, but the AdamW launches wait for the
+        last piece: on the communication stream the order is norm over the reduced buffer (every rank measures the same sums and
+        gets the same coefficient), every planned run, end of step.  Not available with fuse_update: the fused epilogue updates
+        the ViT weights inside the launch that produces their gradients, before any global norm exists."""
+        if (max_grad_norm is not None or getattr(optimizer, "max_grad_norm", None) is not None) and fuse_update:
+            raise ValueError("fuse_update cannot be combined with gradient clipping (max_grad_norm): the fused epilogue applies AdamW to "
+                             "the ViT weights inside the launch that produces their gradients, when no global gradient norm exists yet")
+        if max_grad_norm is not None:
+            optimizer.set_max_grad_norm(max_grad_norm)
         flat = getattr(model, "_flat", None)
         self.model, self.crit, self.opt, self.x, self.y = model, criterion, optimizer, x, y
         self.loss_fn = loss_fn
@@ -152,6 +164,13 @@ class TrainStep:
             self._capture()
             if self.dp:
                 optimizer.zero_grad(set_to_none=True)      # the captured passes attached arena views as .grad; replays never read them
+
+    @property
+    def clip(self):
+        """the optimizer clips: read when a step is launched, not at construction -- AdamW.set_max_grad_norm may switch clipping on or
+        off for an eager step later (it refuses once a capture has frozen the launches), and the data-parallel form must then put
+        the norm in front of the AdamW launches, or stop holding them back"""
+        return getattr(self.opt, "max_grad_norm", None) is not None
 
     # ------------------------------------------------------------------------------------------- single GPU
     def _loss_of(self, enc4, logits):
@@ -253,8 +272,15 @@ class TrainStep:
             for (lo, hi), work in zip(self.pieces[k], works):
                 if work is not None:
                     work.wait()
-                self.opt.step_runs(self._plan, self._runs_of[(lo, hi)], self._steps, src, 1.0 / self.world)
+                if not self.clip:
+                    self.opt.step_runs(self._plan, self._runs_of[(lo, hi)], self._steps, src, 1.0 / self.world)
             if k == len(self.pieces) - 1:
+                if self.clip:
+                    # clipping: the global norm needs every piece reduced, so all AdamW launches were held back until here
+                    self.opt.clip_reduced(self._plan, src, 1.0 / self.world)
+                    for st in self.pieces:
+                        for piece in st:
+                            self.opt.step_runs(self._plan, self._runs_of[piece], self._steps, src, 1.0 / self.world)
                 self.opt.end_reduced_step(self._plan)
         if k == len(self.pieces) - 1:
             main.wait_stream(self.comm_stream)        # the next forward reads the updated parameters
@@ -398,6 +424,12 @@ class TrainStep:
 
     @property
     def launch(self):
+        desc = self._launch_form()
+        if self.clip:
+            desc += "; gradients clipped by global norm on the device (norm + finalize launch, coefficient read by the AdamW kernels)"
+        return desc
+
+    def _launch_form(self):
         if self.graphs is None:
             return "eager"
         if not self.dp:

@@ -778,6 +778,34 @@ int unetr_adamw_reduced(float* p, const void* g, int g_is_bf16, float gscale, fl
 int unetr_adamw_hyper(float* p, const void* g, int g_is_bf16, float gscale, float* m, float* v, long n, const float* hyper_dev,
                       float beta1, float beta2, float eps, const float* step_dev, void* shadow_bf16, void* shadow_x3, void* stream);
 
+/* ---- gradient clipping by global L2 norm on the device (torch.nn.utils.clip_grad_norm_, error_if_nonfinite=False; grad_clip.hip) ----
+ * The clip row: four floats in DEVICE memory, {norm, coef, max_norm, nonfinite}, separate from the hyper row.
+ * unetr_grad_sumsq_ranges: sum of squares over n_ranges ranges of a flat gradient source (fp32, or bf16 when src_is_bf16; 16-byte
+ * aligned), every element widened to double.  table (DEVICE memory, 3 longs per range, the layout of unetr_cast_bf16_ranges):
+ * element offset lo, element offset hi, first block of the range in blocks of 8192 elements (running sum of ceil((hi - lo) / 8192));
+ * n_blocks = total.  Only [lo, hi) is read.  Workgroup b writes its sum to partials[b] (partials_bytes >= 8 n_blocks, else
+ * UNETR_ERR_WORKSPACE): no atomics, the same input gives the same bits.  unetr_grad_sumsq: one tensor of n elements at any
+ * element-aligned address, ceil(n / 8192) partials.
+ * unetr_grad_clip_finalize: ONE workgroup sums n_partials slots in a fixed order to S and writes the row: norm = (float)(gscale *
+ * sqrt(S)) (gscale = 1 / world size for an all-reduced SUM, else 1); coef in fp32 as torch computes it, c = max_norm / (norm + 1e-6f),
+ * coef = c < 1 ? c : 1, NaN for a NaN c; max_norm is READ from the row when the kernel runs (unetr_grad_clip_set: a stream-ordered
+ * single-thread write, max_norm > 0, +inf = measure only), so a captured step follows a change; nonfinite += 1 when norm is inf / NaN.
+ * unetr_adamw_hyper_clip: unetr_adamw_hyper with the gradient g_eff = (g * gscale) * *gcoef_dev (two fp32 roundings in that order;
+ * gcoef_dev = row + 1, read when the kernel runs).  Same bits as unetr_adamw_hyper on gradients scaled that way beforehand.
+ * unetr_grad_scale_ranges / unetr_grad_scale: g *= *coef_dev in place over the same table / one fp32 tensor (nothing is written
+ * when the coefficient is 1).
+ * (Additions: no existing signature or struct moved, UNETR_ABI_VERSION stays.) */
+int unetr_grad_sumsq_ranges(const void* src_arena, int src_is_bf16, const long* table_dev, int n_ranges, long n_blocks,
+                            double* partials, size_t partials_bytes, void* stream);
+int unetr_grad_sumsq(const void* src, int src_is_bf16, long n, double* partials, size_t partials_bytes, void* stream);
+int unetr_grad_clip_finalize(const double* partials, long n_partials, float gscale, float* clip_row, void* stream);
+int unetr_grad_clip_set(float* clip_row, float max_norm, void* stream);
+int unetr_adamw_hyper_clip(float* p, const void* g, int g_is_bf16, float gscale, float* m, float* v, long n, const float* hyper_dev,
+                           float beta1, float beta2, float eps, const float* step_dev, void* shadow_bf16, void* shadow_x3,
+                           const float* gcoef_dev, void* stream);
+int unetr_grad_scale_ranges(float* grad_arena, const long* table_dev, int n_ranges, long n_blocks, const float* coef_dev, void* stream);
+int unetr_grad_scale(float* g, long n, const float* coef_dev, void* stream);
+
 /* ---- the single-GPU step's optimizer fused into the producer of the gradients (train_step.TrainStep(fuse_update=True)) ------
  * The four arenas (parameters, gradients, both moments; fp32, `total` elements, identical layout) and the optional bf16 shadow
  * arena of the parameters; steps = per-parameter step counts (float, already advanced for this step). */
