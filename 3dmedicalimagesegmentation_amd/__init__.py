@@ -17,11 +17,12 @@ from .metrics import (ConfusionMatrixMetric, HausdorffDistanceMetric, SurfaceDic
 from .postprocess import KeepLargestConnectedComponent, connected_components, remove_small_components  # noqa: F401
 from .morphology import (FillHoles, binary_closing, binary_contour, binary_dilation, binary_erosion, binary_fill_holes,  # noqa: F401
                          binary_opening)
+from .lesion_metrics import LesionWiseMetric, lesion_wise_metrics, panoptic_quality  # noqa: F401
 from .train_step import TrainStep  # noqa: F401
 from .augment import IntensityAugment, RandCropAugment, VolumeCache  # noqa: F401
 from .preprocess import Geometry, resample_orient, restore_native  # noqa: F401
 from .functional import invalidate_weight_shadows, refresh_derived_weights  # noqa: F401
-from . import _capi, augment, ddp, distance, functional, grad_clip, inference, metrics, morphology, postprocess, preprocess, seg_losses, topk_loss, train_step  # noqa: F401
+from . import _capi, augment, ddp, distance, functional, grad_clip, inference, lesion_metrics, metrics, morphology, postprocess, preprocess, seg_losses, topk_loss, train_step  # noqa: F401
 
 __all__ = ["UNETR", "UNETRLogits", "DiceCELoss", "ranking_loss", "AdamW", "default_precision", "sliding_window_inference",
            "SlidingWindowInferer", "DiceMetric", "ConfusionMatrixMetric", "HausdorffDistanceMetric", "TrainStep", "invalidate_weight_shadows",
@@ -32,4 +33,4 @@ __all__ = ["UNETR", "UNETRLogits", "DiceCELoss", "ranking_loss", "AdamW", "defau
            "distance_transform_edt", "signed_distance_map", "BoundaryLoss", "HausdorffDTLoss",
            "TopKLoss", "DiceTopKLoss", "kth_value", "percentile",
            "binary_dilation", "binary_erosion", "binary_opening", "binary_closing", "binary_contour", "binary_fill_holes", "FillHoles",
-           "clip_grad_norm_"]
+           "clip_grad_norm_", "lesion_wise_metrics", "LesionWiseMetric", "panoptic_quality"]

@@ -260,6 +260,7 @@ _SIGNATURES = {
     "unetr_ccl": [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint, c_int, c_int, c_int, c_int, P, c_size_t, c_int, P],
     "unetr_morph": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P],
     "unetr_fill_holes": [P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint, c_int, P, c_size_t, P],
+    "unetr_label_overlaps": [P, P, P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, c_int, P],
     "unetr_ranking_loss_fwd": [P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P, P, P, c_size_t, P],
     "unetr_ranking_loss_bwd": [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P],
     "unetr_adamw": [P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_float, P, P, P],
@@ -280,7 +281,7 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES) + ("unetr_conv3_packed_bytes", "unetr_conv
                                             "unetr_surface_metrics_workspace_bytes", "unetr_aug_intensity_ws_bytes", "unetr_segloss_workspace_bytes",
                                             "unetr_aug_class_ws_ints", "unetr_edt_workspace_bytes", "unetr_distloss_workspace_bytes",
                                             "unetr_select_workspace_bytes", "unetr_topkce_workspace_bytes", "unetr_morph_workspace_bytes",
-                                            "unetr_fill_holes_workspace_bytes")
+                                            "unetr_fill_holes_workspace_bytes", "unetr_label_overlaps_workspace_bytes")
 
 _lib = None
 
@@ -346,6 +347,8 @@ def load():
     lib.unetr_morph_workspace_bytes.restype = c_size_t
     lib.unetr_fill_holes_workspace_bytes.argtypes = [c_int] * 5
     lib.unetr_fill_holes_workspace_bytes.restype = c_size_t
+    lib.unetr_label_overlaps_workspace_bytes.argtypes = [c_int] * 5
+    lib.unetr_label_overlaps_workspace_bytes.restype = c_size_t
     _lib = lib
     return lib
 

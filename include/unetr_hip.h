@@ -760,6 +760,34 @@ size_t unetr_fill_holes_workspace_bytes(int D, int H, int W, int N, int class_ma
 int unetr_fill_holes(const void* in, void* out, int u8, const int* labels, int B, int C, int D, int H, int W, int class_map,
                      unsigned applied, int connectivity, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- overlap table of two label maps and the instance-level metrics on it (csrc/lesion.hip) ----
+ * a, b: int32 [planes, D, H, W], 0 = not labelled, else a canonical label as unetr_ccl writes it (1 + the linear index of a
+ * voxel of the same plane; any other value reads as 0).  a_mask: optional float32 [planes, D, H, W]; where it is 0 a voxel
+ * still pairs its two labels but does not count towards the size of its a label or the masked count of the pair (NULL: every
+ * voxel counts).  Per plane an open-addressing table of the distinct pairs (a, b) that share a voxel is built in ws:
+ * slots = 2 * max_pairs rounded up to a power of two (at least 2), key (a << 32) | b with 0 = empty, slot = the 64-bit
+ * MurmurHash3 finalizer of the key & (slots - 1), linear probing, value {voxels, masked voxels} (int32 each).  ws begins with
+ * keys [group][slots] uint64, then (256-byte aligned) values [group][slots][2] int32; after a call with planes <= group these
+ * hold the tables of all planes.  A plane with more than max_pairs distinct pairs is flagged: overflow = 1, the first five
+ * values NaN and the counts that depend on the table -1.
+ *   mode 0  lesion-wise: an a label i is a lesion of gv_i masked voxels; every b label p paired with it is a match;
+ *           pv_i = sum of size(p) over its matches, inter_i = sum of the masked voxels of its pairs,
+ *           dice_i = 2 inter_i / (pv_i + gv_i), 0 without a match; lesions with gv_i < min_size are ignored.
+ *           counts = {lesions, tp, fn, fp, b labels, b labels matched to a lesion that is not ignored, overflow, distinct pairs},
+ *           values = {sum dice_i, lesion Dice = sum / (tp + fn + fp) or 1 for 0/0, precision, recall, f1}.
+ *   mode 1  panoptic: a pair matches when 2 n > size_a + size_b - n (IoU > 1/2, decided in integers);
+ *           counts = {a labels, tp, fn, fp, b labels, tp, overflow, distinct pairs}, values = {sum IoU, sq, rq, pq}.
+ * counts: int64 [planes][UNETR_LO_FIELDS], values: float64 [planes][UNETR_LO_FIELDS].  The float64 sums are taken over a fixed
+ * partition in a fixed order (no float atomics): bit-reproducible.  D, H, W <= 1024, D*H*W < 2^31 - 1 and max_pairs <= 2^24,
+ * else UNETR_ERR_UNSUPPORTED.  ws: 256-byte aligned, unetr_label_overlaps_workspace_bytes(D, H, W, max_pairs, group) bytes
+ * (0 for an unsupported shape): 16 B per slot and 20 B per voxel for each of the `group` planes processed together.  Five
+ * launches per group (the first clears the workspace); no allocation, no host synchronisation.
+ * (Additions: no existing signature moved, UNETR_ABI_VERSION stays.) */
+#define UNETR_LO_FIELDS 8
+size_t unetr_label_overlaps_workspace_bytes(int D, int H, int W, int max_pairs, int group);
+int unetr_label_overlaps(const int* a, const int* b, const float* a_mask, long planes, int D, int H, int W, int mode, int min_size,
+                         int max_pairs, long long* counts, double* values, void* ws, size_t ws_bytes, int group, void* stream);
+
 /* ---- fused AdamW over one flat fp32 buffer (torch.optim.AdamW semantics; unetr_segmentation_3d.py:522) */
 int unetr_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                 float eps, float weight_decay, const float* step_dev,
